@@ -11,7 +11,14 @@ The workload is the north-star's 32-molecule batch: at --gpus 1 all 32 molecules
 GPU; at N GPUs the SAME batch is sharded 32/N per rank (strong scaling over a fixed batch, no data-path collective --
 only the closing barrier / max-reduce of the timing).  value = molecules x steps / max-over-ranks time.
 
-Usage: python bench.py [--gpus N --steps K --warmup W --molecules M --no-cpu-baseline --profile-mode]
+Usage: python bench.py [--gpus N --steps K --warmup W --molecules M --full --dump-outputs DIR --no-cpu-baseline --profile-mode]
+A plain run does only what the headline needs: setup, W warm-up steps, K timed steps (one pass over the batch each, unless
+--min-seconds stretches them), the JSON line.  --full adds everything else the line used to carry: per-kernel HIP-event times
+and rooflines (with their in-process ceiling probes), the other drivers and density forms, the HF / deterministic / small-batch /
+direct / F-row legs, the CPU baselines and, at N > 1, the one-molecule-over-the-ranks leg; --full --profile-mode keeps
+only the per-kernel times and rooflines of these (the rocprofv3 passes of tools/profile_bench.sh).  --dump-outputs DIR writes what the
+last timed step returned to its caller: DIR/fock.npy, the Fock matrices of the batch (float64; DIR/fock_rank<r>.npy per rank at
+N > 1).  The density matrices fed to the timed steps are made in deterministic mode, so the same arguments give the same inputs.
 With --gpus N > 1 from a bare shell the script launches its own N ranks (torch.distributed.run, one per GPU, RCCL);
 started under a launcher (WORLD_SIZE set) it is one of the ranks.  ONE JSON line on rank 0 either way.
 """
@@ -50,6 +57,17 @@ def source_sha16():
 
 DEFAULT_J_CUS = 0  # compute units per XCD for a Coulomb-stream partition: OFF -- measured no better than ordinary streams
                    # (profiles/r06a_cu_partition_curves.txt, r06b_vxc_cus_streams_partition_sweep.txt: 714 against 726-738 it/s)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs, all ranks together
+
+
+def dump_outputs(path, name, mats, limit):
+    """path/<name>.npy: the (molecules, n, n) float64 stack of the matrices one step returned, cut to the first molecules of the
+    batch (whose order the arguments fix) that fit in `limit` bytes"""
+    assert all(m.shape == mats[0].shape for m in mats), "--dump-outputs: Fock matrices of different shapes %s" % sorted(
+        {tuple(m.shape) for m in mats})
+    os.makedirs(path, exist_ok=True)
+    keep = max(1, min(len(mats), limit // (mats[0].numel() * 8)))
+    np.save(os.path.join(path, name + ".npy"), torch.stack(mats[:keep]).to("cpu", torch.float64).numpy())
 
 
 def main():
@@ -58,8 +76,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--molecules", type=int, default=32, help="size of the batch (whole job; sharded over the ranks)")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="a step is repeated `repeats` times so that the timed region of K steps lasts at least this long")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="> 0: a step is repeated `repeats` times so that the timed region of K steps lasts at least this long "
+                         "(default 0: a step is one pass over the batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel times and rooflines, the extra legs, the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the Fock matrices the last timed step returned to DIR/fock.npy (float64)")
     ap.add_argument("--streams", type=int, default=8,
                     help="HIP streams the batch's Fock builds are dealt to (molecule k -> stream k %% S): independent molecules, so "
                          "the tail of one molecule's kernels overlaps the head of the next one's (SURVEY 8e: each rank, own streams)")
@@ -73,7 +96,7 @@ def main():
                     help="N > 1: skip the leg that spreads ONE C4 molecule over the ranks (HamiltonMI355.shard_over)")
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--profile-mode", action="store_true",
-                    help="only setup + warmup + the timed steps (for rocprofv3 passes: no extra legs, no CPU work)")
+                    help="with --full: no extra legs and no CPU work beside the per-kernel times (a plain run is leaner still)")
     ap.add_argument("--df", default=None, metavar="AUXBASIS",
                     help="density-fitted Coulomb operator (Mol.densityfit, e.g. --df etb) instead of the exact-J tile stream; "
                          "a different formulation, labelled as such in config")
@@ -85,6 +108,10 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="self-test of the N-rank launch path only (rendezvous + one all_reduce, no GPU work)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.profile_mode and not args.full:
+        ap.error("--profile-mode trims a --full run: give both (a plain run already has no extra legs)")
 
     if args.gpus > 1 and not (args.all_ranks_on_gpu0 or args.launch_check) and torch.cuda.device_count() < args.gpus:
         # fewer devices than ranks: ONE JSON line saying so (before any rendezvous: nothing can hang) and a non-zero exit
@@ -138,7 +165,7 @@ def main():
     nmol = args.molecules
     costs = [molecule_cost(208, 353400)] * nmol
     mine = shard_lpt(costs, world)[rank]
-    extras = not args.profile_mode
+    extras = args.full and not args.profile_mode
 
     # ---------------- one-off setup (not timed as part of the metric) ----------------
     t0 = time.perf_counter()
@@ -193,7 +220,10 @@ def main():
     del mols
     # density of the core-Hamiltonian guess ("1e", reference scf_qccalc.py:88-91) after one SCF update, for every molecule:
     # the occupied spaces come from the batched purification of the lockstep driver (no eigensolver)
+    # in deterministic mode (fixed-point cross-block sums): these densities are the timed steps' inputs, and with the same
+    # arguments they must be the same bits from run to run (--dump-outputs compares builds output for output)
     t = time.perf_counter()
+    det_prev = lib.set_deterministic(True)
     from dqc_amd.lockstep import LockstepSCF
     ls = LockstepSCF(qcs)
     n = engines[0].shape[-1]
@@ -206,6 +236,7 @@ def main():
         dms.append(eng.hamilton.ao_orb2dm(orbs[k], eng.orb_weight))
     del ls, q0, f1
     lap("two_fock_builds_and_projectors", t)
+    lib.set_deterministic(det_prev)
     torch.cuda.synchronize()
     setup_s = time.perf_counter() - t0
     brk = {k: round(v, 4) for k, v in brk.items()}
@@ -229,6 +260,7 @@ def main():
     torch.cuda.synchronize()
 
     def step(record=None, dense_dm=False, sel=None):
+        scps = []  # what the callers of dm2scp receive: the Fock matrices
         for k, (eng, dm, orb) in enumerate(zip(engines, dms, orbs)):
             if sel is not None and k >= sel:
                 break
@@ -238,10 +270,11 @@ def main():
             if record is None:
                 with torch.cuda.stream(streams[k % nstreams]) if (nstreams > 1 or partition is not None) else contextlib.nullcontext():  # independent molecules: dealt round-robin to the streams
                     d = dm.clone() if dense_dm else eng.hamilton.ao_orb2dm(orb, eng.orb_weight)
-                    eng.dm2scp(d)
+                    scps.append(eng.dm2scp(d))
             else:  # per-kernel events: one molecule at a time on the current stream
                 d = dm.clone() if dense_dm else eng.hamilton.ao_orb2dm(orb, eng.orb_weight)
                 record.append(eng.hamilton.timed_fock_kernels(d, eng.knvext.fullmatrix()))
+        return scps
 
     dense = args.dense_dm
     for _ in range(args.warmup):
@@ -252,26 +285,31 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # a step is repeated so that the timed region is long enough for the driver's samplers (>= --min-seconds)
-    barrier()
-    t0 = time.perf_counter()
-    step(dense_dm=dense)
-    barrier()
-    est = time.perf_counter() - t0
-    repeats = max(1, int(math.ceil(args.min_seconds / max(est * args.steps, 1e-9))))
-    if world > 1:
-        tr = torch.tensor([repeats], dtype=torch.int64, device=dev)
-        dist.all_reduce(tr, op=dist.ReduceOp.MAX)
-        repeats = int(tr)
+    # --min-seconds > 0: a step is repeated so that the timed region is long enough for the driver's samplers
+    repeats = 1
+    if args.min_seconds > 0:
+        barrier()
+        t0 = time.perf_counter()
+        step(dense_dm=dense)
+        barrier()
+        est = time.perf_counter() - t0
+        repeats = max(1, int(math.ceil(args.min_seconds / max(est * args.steps, 1e-9))))
+        if world > 1:
+            tr = torch.tensor([repeats], dtype=torch.int64, device=dev)
+            dist.all_reduce(tr, op=dist.ReduceOp.MAX)
+            repeats = int(tr)
 
     # ---------------- timed region: exactly K steps (each = `repeats` passes over the batch) ----------------
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         for _ in range(repeats):
-            step(dense_dm=dense)
+            last = step(dense_dm=dense)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "fock" if world == 1 else "fock_rank%d" % rank, last, DUMP_LIMIT_BYTES // world)
+    del last
     per_rank = {"setup_s": [setup_s], "timed_s": [elapsed]}
     if world > 1:
         # one row per rank (owned by it, zero elsewhere): a sum is a gather
@@ -282,14 +320,16 @@ def main():
         elapsed = float(tab_r[:, 1].max())
     passes = args.steps * repeats
 
-    # ---------------- per-kernel HIP-event timing (same stream as the launches), first 4 local molecules ----------------
-    rec = []
+    # ---------------- --full: per-kernel HIP-event timing (same stream as the launches), first 4 local molecules ----------------
     nsel = min(4, len(engines))
-    for _ in range(max(3, min(args.steps, 10))):
-        step(rec, dense_dm=dense, sel=nsel)
-    torch.cuda.synchronize()
-    names = rec[0][0]
-    ktime = {nm: sum(e[1][i].elapsed_time(e[1][i + 1]) for e in rec) / len(rec) for i, nm in enumerate(names)}  # ms / launch
+    ktime = {}
+    if args.full:
+        rec = []
+        for _ in range(max(3, min(args.steps, 10))):
+            step(rec, dense_dm=dense, sel=nsel)
+        torch.cuda.synchronize()
+        names = rec[0][0]
+        ktime = {nm: sum(e[1][i].elapsed_time(e[1][i + 1]) for e in rec) / len(rec) for i, nm in enumerate(names)}  # ms / launch
 
     out_extra = {}
     if extras:
@@ -463,52 +503,67 @@ def main():
             "grid_density": f_den, "grid_vxc": f_vxc, "grid_fused": f_den + f_vxc, "jk_tiles": 2.0 * float(nao) ** 4,
         }
         alg_bytes = {k: v for k, v in alg_bytes.items() if k in ktime}
-        # HBM bytes per launch from the committed rocprofv3 PMC pass of this same command (bench.py cannot sample
-        # counters itself): only reported when that pass was taken with these very sources (kernel code + this file)
-        traffic, traffic_note = {}, None
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-            sha = source_sha16()
-            if tj.get("csrc_sha16") != sha["csrc_sha16"] or tj.get("bench_py_sha16") != sha["bench_py_sha16"]:
-                traffic_note = "profiles/pmc_traffic.json was taken with other sources (%s / %s): not reported" % (
-                    tj.get("csrc_sha16"), tj.get("bench_py_sha16"))
-            elif tj["workload"] == {"nao": nao, "ngrid": ngrid, "xc": "gga"}:
-                traffic = dict(tj["hbm_read_bytes_per_launch"])
-        except Exception as e:  # noqa: BLE001
-            traffic_note = "no usable profiles/pmc_traffic.json (%s)" % type(e).__name__
-        mfma_ceiling = lib.probe_mfma_f64_tflops(dev)
-        hbm_ceiling = lib.probe_hbm_read_gbs(dev)
+        roofs = {}
+        if args.full:
+            # HBM bytes per launch from the committed rocprofv3 PMC pass of this same command (bench.py cannot sample
+            # counters itself): only reported when that pass was taken with these very sources (kernel code + this file)
+            traffic, traffic_note = {}, None
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+                sha = source_sha16()
+                if tj.get("csrc_sha16") != sha["csrc_sha16"] or tj.get("bench_py_sha16") != sha["bench_py_sha16"]:
+                    traffic_note = "profiles/pmc_traffic.json was taken with other sources (%s / %s): not reported" % (
+                        tj.get("csrc_sha16"), tj.get("bench_py_sha16"))
+                elif tj["workload"] == {"nao": nao, "ngrid": ngrid, "xc": "gga"}:
+                    traffic = dict(tj["hbm_read_bytes_per_launch"])
+            except Exception as e:  # noqa: BLE001
+                traffic_note = "no usable profiles/pmc_traffic.json (%s)" % type(e).__name__
+            mfma_ceiling = lib.probe_mfma_f64_tflops(dev)
+            hbm_ceiling = lib.probe_hbm_read_gbs(dev)
 
-        def roof(k):
-            t = ktime[k] * 1e-3
-            gbs, tfs = alg_bytes[k] / t / 1e9, alg_flops[k] / t / 1e12
-            # the binding roof is the one the kernel sits closer to
-            if k != "jk_tiles" and tfs / F64_MFMA_PEAK_TF > gbs / HBM_PEAK_GBS:
-                return {"bound": "mfma", "kernel": k, "achieved": tfs, "peak": F64_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                        "frac": tfs / F64_MFMA_PEAK_TF, "traffic": traffic.get(k), "algorithmic_flops_per_launch": alg_flops[k],
-                        "algorithmic_bytes_per_launch": alg_bytes[k], "hbm_gbs": gbs, "hbm_frac": gbs / HBM_PEAK_GBS,
-                        "measured_mfma_f64_ceiling_tflops": mfma_ceiling, "frac_of_measured_ceiling": tfs / mfma_ceiling,
+            def roof(k):
+                t = ktime[k] * 1e-3
+                gbs, tfs = alg_bytes[k] / t / 1e9, alg_flops[k] / t / 1e12
+                # the binding roof is the one the kernel sits closer to
+                if k != "jk_tiles" and tfs / F64_MFMA_PEAK_TF > gbs / HBM_PEAK_GBS:
+                    return {"bound": "mfma", "kernel": k, "achieved": tfs, "peak": F64_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                            "frac": tfs / F64_MFMA_PEAK_TF, "traffic": traffic.get(k), "algorithmic_flops_per_launch": alg_flops[k],
+                            "algorithmic_bytes_per_launch": alg_bytes[k], "hbm_gbs": gbs, "hbm_frac": gbs / HBM_PEAK_GBS,
+                            "measured_mfma_f64_ceiling_tflops": mfma_ceiling, "frac_of_measured_ceiling": tfs / mfma_ceiling,
+                            "avg_launch_ms": ktime[k]}
+                return {"bound": "hbm", "kernel": k, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": gbs / HBM_PEAK_GBS, "traffic": traffic.get(k), "algorithmic_bytes_per_launch": alg_bytes[k],
+                        "measured_hbm_read_ceiling_gbs": hbm_ceiling, "frac_of_measured_ceiling": gbs / hbm_ceiling,
+                        "standalone_read_ceiling_gbs": UBENCH_READ_GBS, "frac_of_standalone_ceiling": gbs / UBENCH_READ_GBS,
                         "avg_launch_ms": ktime[k]}
-            return {"bound": "hbm", "kernel": k, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": gbs / HBM_PEAK_GBS, "traffic": traffic.get(k), "algorithmic_bytes_per_launch": alg_bytes[k],
-                    "measured_hbm_read_ceiling_gbs": hbm_ceiling, "frac_of_measured_ceiling": gbs / hbm_ceiling,
-                    "standalone_read_ceiling_gbs": UBENCH_READ_GBS, "frac_of_standalone_ceiling": gbs / UBENCH_READ_GBS,
-                    "avg_launch_ms": ktime[k]}
 
-        dom = max(alg_bytes, key=lambda k: ktime[k])
-        # the whole molecule-iteration against the HBM roof: algorithmic bytes of ALL its kernels x the rate the timed region achieved
-        # (with several streams the kernels of different molecules share the chip and each one's own duration stretches: this entry
-        # is the figure that does not depend on how the launches overlap)
-        it_bytes = sum(alg_bytes.values())
-        it_rate = nmol * passes / elapsed / world
-        whole_iteration = {"bound": "hbm", "kernel": "whole_iteration", "achieved": it_bytes * it_rate / 1e9, "peak": HBM_PEAK_GBS,
-                           "unit": "GB/s", "frac": it_bytes * it_rate / 1e9 / HBM_PEAK_GBS, "traffic": None,
-                           "algorithmic_bytes_per_molecule_iteration": it_bytes, "iterations_per_s_per_gpu": it_rate,
-                           "measured_hbm_read_ceiling_gbs": hbm_ceiling, "frac_of_measured_ceiling": it_bytes * it_rate / 1e9 / hbm_ceiling,
-                           "standalone_read_ceiling_gbs": UBENCH_READ_GBS, "frac_of_standalone_ceiling": it_bytes * it_rate / 1e9 / UBENCH_READ_GBS,
-                           "streams_per_gpu": nstreams,
-                           "note": "sum of the kernels' algorithmic bytes per molecule-iteration x the timed region's rate; the per-kernel "
-                                   "entries are HIP-event durations of one molecule at a time on one stream"}
+            dom = max(alg_bytes, key=lambda k: ktime[k])
+            # the whole molecule-iteration against the HBM roof: algorithmic bytes of ALL its kernels x the rate the timed region achieved
+            # (with several streams the kernels of different molecules share the chip and each one's own duration stretches: this entry
+            # is the figure that does not depend on how the launches overlap)
+            it_bytes = sum(alg_bytes.values())
+            it_rate = nmol * passes / elapsed / world
+            whole_iteration = {"bound": "hbm", "kernel": "whole_iteration", "achieved": it_bytes * it_rate / 1e9, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": it_bytes * it_rate / 1e9 / HBM_PEAK_GBS, "traffic": None,
+                               "algorithmic_bytes_per_molecule_iteration": it_bytes, "iterations_per_s_per_gpu": it_rate,
+                               "measured_hbm_read_ceiling_gbs": hbm_ceiling, "frac_of_measured_ceiling": it_bytes * it_rate / 1e9 / hbm_ceiling,
+                               "standalone_read_ceiling_gbs": UBENCH_READ_GBS, "frac_of_standalone_ceiling": it_bytes * it_rate / 1e9 / UBENCH_READ_GBS,
+                               "streams_per_gpu": nstreams,
+                               "note": "sum of the kernels' algorithmic bytes per molecule-iteration x the timed region's rate; the per-kernel "
+                                       "entries are HIP-event durations of one molecule at a time on one stream"}
+            roofs = {
+                "kernel_ms_per_molecule": ktime,
+                "roofline": roof(dom),
+                "roofline_other_kernels": [roof(k) for k in alg_bytes if k != dom] + [whole_iteration],
+                "measured_ceilings_note": "measured_hbm_read_ceiling_gbs = dqc_probe_stream_read on a 2 GB buffer (contiguous 32 KB tiles per block, "
+                                          "16-byte non-temporal loads, four tiles in flight, two blocks per CU).  Until round 6 the probe ended in 16384 "
+                                          "fp64 atomicAdds of its checksum on one address (~75 us per launch) and read 5.2-5.3 TB/s on 2 GB -- the "
+                                          "'in-process ceiling' of rounds 2-5, which profiles/r06a_hbm_ceiling_bisect.txt showed to be independent of "
+                                          "the process state and profiles/r06c_read_shape.txt traced to those atomics; with one atomic per block it "
+                                          "reads 6.15-6.25 TB/s, like plain read kernels in any access shape the grid kernels use.  "
+                                          "standalone_read_ceiling_gbs = 6450 is the large-buffer asymptote (tools/ubench/read_bw.hip)",
+                "traffic_note": traffic_note,
+            }
         out = {
             "metric": "SCF iterations/sec (Fock build + XC grid) per GPU, cc-pVDZ 20-atom",
             "value": nmol * passes / elapsed,
@@ -525,7 +580,6 @@ def main():
                        "coulomb": ("density-fitted J, auxbasis %s (naux %d)" % (args.df, int(h0.df.j2c.shape[0]))) if args.df
                                   else "exact J from stored ERI tiles",
                        "molecules_per_gpu": len(mine), "global_batch": nmol, "nao": nao, "ngrid": ngrid, "streams_per_gpu": nstreams,
-                       "grid_pass": "fused density+XC+Vxc kernel" if fused else "density, XC, Vxc kernels",
                        "parallelism": "molecule-sharded x%d, no data-path collective" % world},
             "per_gpu_value": nmol * passes / elapsed / world,
             "density_matrix_input": "full matrix (no factor)" if dense else
@@ -540,19 +594,11 @@ def main():
                           "process_warmup = first-use loading of the vendor libraries' and this library's code objects, on a water "
                           "molecule, also once per process; setup_s_batch_only_rank0 = the batch's own setup (tables, orthogonalisers, "
                           "ERI fill, grid, AO, two Fock builds) without those two",
-            "kernel_ms_per_molecule": ktime,
-            "roofline": roof(dom),
-            "roofline_other_kernels": [roof(k) for k in alg_bytes if k != dom] + [whole_iteration],
-            "measured_ceilings_note": "measured_hbm_read_ceiling_gbs = dqc_probe_stream_read on a 2 GB buffer (contiguous 32 KB tiles per block, "
-                                      "16-byte non-temporal loads, four tiles in flight, two blocks per CU).  Until round 6 the probe ended in 16384 "
-                                      "fp64 atomicAdds of its checksum on one address (~75 us per launch) and read 5.2-5.3 TB/s on 2 GB -- the "
-                                      "'in-process ceiling' of rounds 2-5, which profiles/r06a_hbm_ceiling_bisect.txt showed to be independent of "
-                                      "the process state and profiles/r06c_read_shape.txt traced to those atomics; with one atomic per block it "
-                                      "reads 6.15-6.25 TB/s, like plain read kernels in any access shape the grid kernels use.  "
-                                      "standalone_read_ceiling_gbs = 6450 is the large-buffer asymptote (tools/ubench/read_bw.hip)",
-            "traffic_note": traffic_note,
             "sources": source_sha16(),
         }
+        if args.full:  # (named from the per-kernel pass)
+            out["config"]["grid_pass"] = "fused density+XC+Vxc kernel" if fused else "density, XC, Vxc kernels"
+        out.update(roofs)
         out.update(out_extra)
         if world == 1 and extras and not args.no_cpu_baseline:
             out["cpu_baseline"], par = cpu_baseline(args.cpu_steps, engines[0], dms[0])

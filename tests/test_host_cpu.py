@@ -234,6 +234,24 @@ def test_bench_launches_its_own_ranks_from_a_bare_shell():
     assert rec["n_gpus"] == 2 and rec["n_ranks_seen"] == 2
 
 
+def test_bench_dump_outputs_cut_and_shapes(tmp_path):
+    """bench.dump_outputs: one float64 stack of the step's matrices, cut to the first molecules that fit in the byte limit (always
+    at least one); matrices of different shapes are refused with a message"""
+    import bench
+    mats = [torch.full((64, 64), float(k), dtype=torch.float64) for k in range(5)]  # 32 KiB each
+    bench.dump_outputs(str(tmp_path / "all"), "fock", mats, bench.DUMP_LIMIT_BYTES)
+    a = np.load(str(tmp_path / "all" / "fock.npy"))
+    assert a.dtype == np.float64 and a.shape == (5, 64, 64) and (a[:, 0, 0] == np.arange(5)).all()
+    bench.dump_outputs(str(tmp_path / "cut"), "fock", mats, 3 * 32768 + 100)
+    c = np.load(str(tmp_path / "cut" / "fock.npy"))
+    assert c.shape == (3, 64, 64) and np.array_equal(c, a[:3])
+    bench.dump_outputs(str(tmp_path / "one"), "fock", mats, 1000)
+    assert np.load(str(tmp_path / "one" / "fock.npy")).shape == (1, 64, 64)
+    assert 32 * 208 * 208 * 8 <= bench.DUMP_LIMIT_BYTES <= 64 << 20  # the default C5 batch is dumped whole
+    with pytest.raises(AssertionError, match="different shapes"):
+        bench.dump_outputs(str(tmp_path / "bad"), "fock", mats[:2] + [torch.zeros(63, 63, dtype=torch.float64)], bench.DUMP_LIMIT_BYTES)
+
+
 def test_run_lockstep_buckets_and_groups_on_cpu(monkeypatch):
     """host logic of batch.run_lockstep: calculations are bucketed by (device, nao, n_occ, occupation), cut into equal groups of at
     most group_size (at least `inflight` of them), and whatever does not qualify -- unrestricted, non-uniform occupations, raw

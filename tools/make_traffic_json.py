@@ -28,7 +28,7 @@ def main():
                 # FETCH_SIZE is in KB and, on gfx950, reports half of a wide coalesced read (MI355X_MICROARCH.md, HBM section)
                 out[key] = int(float(m.group(2)) * 1024 * 2)
                 break
-    doc = {"_how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python bench.py --profile-mode ... (own pass, no other trace "
+    doc = {"_how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python bench.py --full --profile-mode ... (own pass, no other trace "
                    "domains); per-dispatch average; bytes = FETCH_SIZE[KB] * 1024 * 2 (gfx950: FETCH_SIZE reports half of a wide "
                    "coalesced read; calibrated in round 1 on dqc_probe_stream_read: 1.04859e6 KB for a 2 GiB read). Source: " +
                    os.path.basename(src),
