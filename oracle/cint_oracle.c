@@ -81,7 +81,7 @@ static void boys(int mmax, double T, double *F)
 /* Hermite expansion coefficients E^{ij}_t (one Cartesian direction)  */
 /* E[i][j][t], i<=la, j<=lb, t<=i+j ; includes exp(-mu X_AB^2)        */
 /* ------------------------------------------------------------------ */
-#define EDIM (2 * LMAX + 3)  /* +2 so that kinetic can use j+2 */
+#define EDIM (2 * LMAX + 4)  /* +2 so that kinetic can use j+2, +1 for the bra derivative (i+1) */
 typedef double Ecoef[LMAX1 + 2][LMAX1 + 2][EDIM];
 
 static void hermite_E(int la, int lb, double a, double b, double XAB, Ecoef E)
@@ -115,7 +115,7 @@ static void hermite_E(int la, int lb, double a, double b, double XAB, Ecoef E)
 /* ------------------------------------------------------------------ */
 /* Hermite Coulomb integrals R_{tuv} = R^0_{tuv}, t+u+v <= L          */
 /* ------------------------------------------------------------------ */
-#define RL (4 * LMAX + 1)
+#define RL (4 * LMAX + 2)  /* +1: derivative integrals (bra shell raised to l+1) */
 typedef double Rtens[RL][RL][RL];
 
 static void hermite_R(int L, double alpha, double X, double Y, double Z, Rtens R)
@@ -398,9 +398,10 @@ void orc_int1e(int which, double *out, const int *atm, int natm, const int *bas,
 /* ------------------------------------------------------------------ */
 /* Hermite-basis expansion of a primitive pair: Hc[ca*nb+cb][tuv-linear] */
 #define NHERM(L) (((L) + 1) * ((L) + 2) * ((L) + 3) / 6)
-#define MAXHERM NHERM(2 * LMAX)
+#define HMAX (2 * LMAX + 1)  /* Hermite order of a pair: la + lb (+1 with the bra derivative) */
+#define MAXHERM NHERM(HMAX)
 
-static int herm_index[2 * LMAX + 1][2 * LMAX + 1][2 * LMAX + 1];
+static int herm_index[HMAX + 1][HMAX + 1][HMAX + 1];
 static int herm_tuv[MAXHERM][3];
 static int herm_ready = 0;
 static void init_herm(void)
@@ -408,7 +409,7 @@ static void init_herm(void)
     if (herm_ready) return;
     int n = 0;
     /* ordered by total degree so that NHERM(L) prefix = all t+u+v<=L */
-    for (int N = 0; N <= 2 * LMAX; N++)
+    for (int N = 0; N <= HMAX; N++)
         for (int t = N; t >= 0; t--)
             for (int u = N - t; u >= 0; u--) {
                 int v = N - t - u;
@@ -421,7 +422,8 @@ static void init_herm(void)
 
 typedef struct {
     double p, P[3];
-    double *H; /* [ncart_a*ncart_b][nherm] includes coefficient product and exp prefactor */
+    int L;     /* Hermite order: la + lb, or la + lb + 1 for the derivative pairs of build_prim_pairs_ip */
+    double *H; /* [ncart_a*ncart_b][nherm] includes coefficient product and exp prefactor (ncomp such blocks) */
 } PrimPair;
 
 static void build_prim_pairs(Shell A, Shell B, PrimPair *pp, double *Hbuf)
@@ -439,6 +441,7 @@ static void build_prim_pairs(Shell A, Shell B, PrimPair *pp, double *Hbuf)
             hermite_E(la, lb, a, b, AB[1], Ey);
             hermite_E(la, lb, a, b, AB[2], Ez);
             pp[n].p = p;
+            pp[n].L = la + lb;
             for (int d = 0; d < 3; d++) pp[n].P[d] = (a * A.r[d] + b * B.r[d]) / p;
             pp[n].H = Hbuf + (size_t)n * na * nb * nh;
             double cc = A.coefs[ip] * B.coefs[jp];
@@ -456,17 +459,20 @@ static void build_prim_pairs(Shell A, Shell B, PrimPair *pp, double *Hbuf)
         }
 }
 
-/* out: spherical block [sa][sb][sc][sd] row-major */
-static void eri_quartet(Shell A, Shell B, Shell C, Shell D, const PrimPair *bra, int nbra,
-                        const PrimPair *ket, int nket, double *sph, double *work)
+/* ncomp blocks [ncart_a][ncart_b][ncart_c][ncart_d] of the bra Hermite tables (ncomp = 3: the derivative pairs of
+ * build_prim_pairs_ip, all with the same R) -> ncomp output blocks; axis x is solid-harmonic transformed when bit x of
+ * sphmask is set, left Cartesian otherwise.  work: ncomp * MAXCART^4 + ERI_WORK1 doubles. */
+#define ERI_WORK1 ((size_t)MAXCART * MAXCART * MAXCART * MAXCART + (size_t)MAXHERM * MAXCART * MAXCART)
+static void eri_quartet_n(Shell A, Shell B, Shell C, Shell D, const PrimPair *bra, int nbra,
+                          const PrimPair *ket, int nket, int ncomp, int sphmask, double *sph, double *work)
 {
     int la = A.l, lb = B.l, lc = C.l, ld = D.l;
     int nab = NCART(la) * NCART(lb), ncd = NCART(lc) * NCART(ld);
-    int Lb = la + lb, Lk = lc + ld, L = Lb + Lk;
+    int Lb = bra[0].L, Lk = ket[0].L, L = Lb + Lk;
     int nhb = NHERM(Lb), nhk = NHERM(Lk);
-    double *cart = work;                 /* nab*ncd */
-    double *W = cart + (size_t)nab * ncd; /* nhb*ncd */
-    memset(cart, 0, sizeof(double) * nab * ncd);
+    double *cart = work;                 /* ncomp * nab*ncd */
+    double *W = cart + (size_t)ncomp * nab * ncd; /* nhb*ncd */
+    memset(cart, 0, sizeof(double) * ncomp * nab * ncd);
     static __thread Rtens R;
     for (int ib = 0; ib < nbra; ib++)
         for (int ik = 0; ik < nket; ik++) {
@@ -491,7 +497,7 @@ static void eri_quartet(Shell A, Shell B, Shell C, Shell D, const PrimPair *bra,
                     W[(size_t)hb * ncd + cd] = s * pref;
                 }
             }
-            for (int ab = 0; ab < nab; ab++) {
+            for (int ab = 0; ab < ncomp * nab; ab++) {
                 const double *hbp = bra[ib].H + (size_t)ab * nhb;
                 double *dst = cart + (size_t)ab * ncd;
                 for (int hb = 0; hb < nhb; hb++) {
@@ -504,11 +510,14 @@ static void eri_quartet(Shell A, Shell B, Shell C, Shell D, const PrimPair *bra,
         }
     /* cart [ca][cb][cc][cd] -> sph, one index at a time */
     int n[4] = {NCART(la), NCART(lb), NCART(lc), NCART(ld)};
-    int s[4] = {2 * la + 1, 2 * lb + 1, 2 * lc + 1, 2 * ld + 1};
-    int ls[4] = {la, lb, lc, ld};
-    double *src = cart, *dst = W; /* W buffer is large enough: see alloc */
+    int s[4], ls[4] = {la, lb, lc, ld};
+    for (int ax = 0; ax < 4; ax++) s[ax] = (sphmask >> ax & 1) ? 2 * ls[ax] + 1 : n[ax];
+    size_t osz = (size_t)s[0] * s[1] * s[2] * s[3];
+    for (int comp = 0; comp < ncomp; comp++) {
+    double *src = cart + (size_t)comp * nab * ncd, *dst = W; /* W buffer is large enough: see alloc */
     int dims[4] = {n[0], n[1], n[2], n[3]};
     for (int ax = 0; ax < 4; ax++) {
+        if (!(sphmask >> ax & 1)) continue;
         const double *Cm = c2s_table(ls[ax]);
         int outer = 1, inner = 1;
         for (int k = 0; k < ax; k++) outer *= dims[k];
@@ -525,7 +534,15 @@ static void eri_quartet(Shell A, Shell B, Shell C, Shell D, const PrimPair *bra,
         dims[ax] = ns;
         double *tmp = src; src = dst; dst = tmp;
     }
-    memcpy(sph, src, sizeof(double) * s[0] * s[1] * s[2] * s[3]);
+    memcpy(sph + comp * osz, src, sizeof(double) * osz);
+    }
+}
+
+/* out: spherical block [sa][sb][sc][sd] row-major */
+static void eri_quartet(Shell A, Shell B, Shell C, Shell D, const PrimPair *bra, int nbra,
+                        const PrimPair *ket, int nket, double *sph, double *work)
+{
+    eri_quartet_n(A, B, C, D, bra, nbra, ket, nket, 1, 15, sph, work);
 }
 
 /* Packed s4 ERI: out[(ij),(kl)], ij = i(i+1)/2+j (i>=j), npair x npair, exactly the
@@ -961,4 +978,358 @@ int orc_num_threads(void)
 #else
     return 1;
 #endif
+}
+
+/* ------------------------------------------------------------------ */
+/* Derivative integrals (the reference's "ip" integrals,               */
+/* dqc/hamilton/intor/molintor.py:463-500), for the gradient checks.   */
+/* d/dA_x of x_A^i e^{-a r_A^2} = 2a x_A^{i+1} e^{..} - i x_A^{i-1} e^{..}  */
+/* on the raw Cartesian monomials (env coefficients), then the c2s     */
+/* table of the original l -- or no transform at all (cart = 1: the    */
+/* Cartesian AO basis, raw monomial times contraction).  All outputs   */
+/* are d/dA (derivative with respect to the centre, NOT libcint's      */
+/* nabla-of-the-function sign).                                        */
+/* ------------------------------------------------------------------ */
+static int ao_dim(int l, int cart) { return cart ? NCART(l) : 2 * l + 1; }
+
+static int make_loc(int nbas, const int *bas, int cart, int *loc)
+{
+    loc[0] = 0;
+    for (int i = 0; i < nbas; i++) loc[i + 1] = loc[i] + ao_dim(bas[i * BAS_SLOTS + ANG_OF], cart);
+    return loc[nbas];
+}
+
+/* ncomp Cartesian blocks (na, nb) -> (sa, sb) or unchanged */
+static void c2s_2index_n(int la, int lb, int ncomp, int cart, const double *cartb, double *out)
+{
+    int na = NCART(la), nb = NCART(lb), sa = ao_dim(la, cart), sb = ao_dim(lb, cart);
+    for (int c = 0; c < ncomp; c++) {
+        if (cart) memcpy(out + c * sa * sb, cartb + c * na * nb, sizeof(double) * na * nb);
+        else c2s_2index(la, lb, cartb + c * na * nb, out + c * sa * sb);
+    }
+}
+
+/* one shell pair, 3 components d = x, y, z:
+ *   which 0: <d_A a|b>   1: <d_A a|T|b>   2: <d_A a|V|b> (V = sum_C -Z_C/|r - C|, basis-centre derivative only)
+ *   which 3: d/dC <a|-Z_C/|r - C||b> for the one nucleus `opc` (operator derivative, computed directly from R_{t+1,u,v}) */
+static void int1e_ip_pair(int which, int cart, Shell A, Shell B, int natm, const int *atm, const double *env,
+                          const double *zs, int opc, double *out)
+{
+    int la = A.l, lb = B.l, na = NCART(la), nb = NCART(lb);
+    int pa[MAXCART][3], pb[MAXCART][3];
+    cart_powers(la, pa); cart_powers(lb, pb);
+    double cb3[3 * MAXCART * MAXCART];
+    memset(cb3, 0, sizeof(cb3));
+    double AB[3] = {A.r[0] - B.r[0], A.r[1] - B.r[1], A.r[2] - B.r[2]};
+    static __thread Rtens R;
+    for (int ip = 0; ip < A.nprim; ip++)
+        for (int jp = 0; jp < B.nprim; jp++) {
+            double a = A.exps[ip], b = B.exps[jp], p = a + b;
+            double cc = A.coefs[ip] * B.coefs[jp];
+            Ecoef E[3];
+            for (int d = 0; d < 3; d++) hermite_E(la + 1, lb + 2, a, b, AB[d], E[d]);
+            if (which <= 1) {
+                double pref = cc * pow(M_PI / p, 1.5);
+                for (int ca = 0; ca < na; ca++)
+                    for (int cbi = 0; cbi < nb; cbi++) {
+                        double S[3], T[3], dS[3], dT[3];
+                        for (int d = 0; d < 3; d++) {
+                            int i = pa[ca][d], j = pb[cbi][d];
+                            /* 1D overlap and kinetic of bra power ii */
+#define S1(ii) (E[d][ii][j][0])
+#define T1(ii) (-2.0 * b * b * E[d][ii][j + 2][0] + b * (2 * j + 1) * E[d][ii][j][0] - (j >= 2 ? 0.5 * j * (j - 1) * E[d][ii][j - 2][0] : 0.0))
+                            S[d] = S1(i);
+                            T[d] = T1(i);
+                            dS[d] = 2.0 * a * S1(i + 1) - (i ? i * S1(i - 1) : 0.0);
+                            dT[d] = 2.0 * a * T1(i + 1) - (i ? i * T1(i - 1) : 0.0);
+#undef S1
+#undef T1
+                        }
+                        for (int d = 0; d < 3; d++) {
+                            int e = (d + 1) % 3, f = (d + 2) % 3;
+                            double v = which == 0 ? dS[d] * S[e] * S[f]
+                                                  : dT[d] * S[e] * S[f] + dS[d] * T[e] * S[f] + dS[d] * S[e] * T[f];
+                            cb3[(d * na + ca) * nb + cbi] += pref * v;
+                        }
+                    }
+            } else {
+                double P[3] = {(a * A.r[0] + b * B.r[0]) / p, (a * A.r[1] + b * B.r[1]) / p,
+                               (a * A.r[2] + b * B.r[2]) / p};
+                double pref = cc * 2.0 * M_PI / p;
+                int L = la + lb + 1;
+                for (int ic = (which == 3 ? opc : 0); ic < (which == 3 ? opc + 1 : natm); ic++) {
+                    const double *C = env + atm[ic * ATM_SLOTS + PTR_COORD];
+                    double Z = zs ? zs[ic] : (double)atm[ic * ATM_SLOTS + 0];
+                    if (Z == 0.0) continue;
+                    hermite_R(L, p, P[0] - C[0], P[1] - C[1], P[2] - C[2], R);
+                    for (int ca = 0; ca < na; ca++)
+                        for (int cbi = 0; cbi < nb; cbi++) {
+                            int iv[3] = {pa[ca][0], pa[ca][1], pa[ca][2]}, jv[3] = {pb[cbi][0], pb[cbi][1], pb[cbi][2]};
+                            for (int d = 0; d < 3; d++) {
+                                /* Hermite coefficients per direction: the derivative direction takes 2a E^{i+1} - i E^{i-1}
+                                 * (which 2); the operator derivative keeps E and shifts R (d/dC_d R_tuv(P - C) = -R_{t+1..}) */
+                                double h[3][2 * LMAX + 4];
+                                int tmax[3];
+                                for (int x = 0; x < 3; x++) {
+                                    int i = iv[x], j = jv[x];
+                                    int dx = which == 2 && x == d;
+                                    tmax[x] = i + j + dx;
+                                    for (int t = 0; t <= tmax[x]; t++) {
+                                        if (dx) h[x][t] = 2.0 * a * E[x][i + 1][j][t] - (i && t <= i - 1 + j ? i * E[x][i - 1][j][t] : 0.0);
+                                        else h[x][t] = E[x][i][j][t];
+                                    }
+                                }
+                                double v = 0;
+                                for (int t = 0; t <= tmax[0]; t++)
+                                    for (int u = 0; u <= tmax[1]; u++)
+                                        for (int w = 0; w <= tmax[2]; w++) {
+                                            double r = which == 2 ? R[t][u][w]
+                                                                  : -(d == 0 ? R[t + 1][u][w] : d == 1 ? R[t][u + 1][w] : R[t][u][w + 1]);
+                                            v += h[0][t] * h[1][u] * h[2][w] * r;
+                                        }
+                                cb3[(d * na + ca) * nb + cbi] -= Z * pref * v;
+                            }
+                        }
+                }
+            }
+        }
+    c2s_2index_n(la, lb, 3, cart, cb3, out);
+}
+
+/* which 0 / 1 / 2: out (3, n, n), out[d][i][j] = <d/dA_d i|O|j>, A the centre of i (O = 1, T, V of all nuclei);
+ * which 3: out (natm, 3, n, n), out[C][d][i][j] = d/dC_d <i|-Z_C/|r - C||j> (operator derivative, Hellmann-Feynman).
+ * n = nao (cart = 0) or ncart (cart = 1).  zs: optional fractional charges (NULL: atm[:, 0]). */
+void orc_int1e_ip(int which, int cart, double *out, const int *atm, int natm, const int *bas, int nbas,
+                  const double *env, const double *zs)
+{
+    int *loc = (int *)malloc(sizeof(int) * (nbas + 1));
+    size_t n = make_loc(nbas, bas, cart, loc);
+    int nblk = which == 3 ? natm : 1;
+#pragma omp parallel for schedule(dynamic) collapse(2)
+    for (int ic = 0; ic < nblk; ic++)
+        for (int ish = 0; ish < nbas; ish++) {
+            double blk[3 * MAXCART * MAXCART];
+            for (int jsh = 0; jsh < nbas; jsh++) {
+                Shell A = get_shell(ish, atm, bas, env), B = get_shell(jsh, atm, bas, env);
+                int sa = ao_dim(A.l, cart), sb = ao_dim(B.l, cart);
+                int1e_ip_pair(which, cart, A, B, natm, atm, env, zs, ic, blk);
+                for (int d = 0; d < 3; d++)
+                    for (int i = 0; i < sa; i++)
+                        for (int j = 0; j < sb; j++)
+                            out[(((size_t)ic * 3 + d) * n + loc[ish] + i) * n + loc[jsh] + j] = blk[(d * sa + i) * sb + j];
+            }
+        }
+    free(loc);
+}
+
+/* primitive pairs of (d/dA_d a) b, d = x, y, z: three Hermite blocks per pair (order la + lb + 1) */
+static void build_prim_pairs_ip(Shell A, Shell B, PrimPair *pp, double *Hbuf)
+{
+    int la = A.l, lb = B.l, na = NCART(la), nb = NCART(lb), nh = NHERM(la + lb + 1);
+    int pa[MAXCART][3], pb[MAXCART][3];
+    cart_powers(la, pa); cart_powers(lb, pb);
+    double AB[3] = {A.r[0] - B.r[0], A.r[1] - B.r[1], A.r[2] - B.r[2]};
+    int n = 0;
+    for (int ip = 0; ip < A.nprim; ip++)
+        for (int jp = 0; jp < B.nprim; jp++, n++) {
+            double a = A.exps[ip], b = B.exps[jp], p = a + b;
+            Ecoef E[3];
+            for (int d = 0; d < 3; d++) hermite_E(la + 1, lb, a, b, AB[d], E[d]);
+            pp[n].p = p;
+            pp[n].L = la + lb + 1;
+            for (int d = 0; d < 3; d++) pp[n].P[d] = (a * A.r[d] + b * B.r[d]) / p;
+            pp[n].H = Hbuf + (size_t)n * 3 * na * nb * nh;
+            double cc = A.coefs[ip] * B.coefs[jp];
+            memset(pp[n].H, 0, sizeof(double) * 3 * na * nb * nh);
+            for (int d = 0; d < 3; d++)
+                for (int ca = 0; ca < na; ca++)
+                    for (int cb = 0; cb < nb; cb++) {
+                        int iv[3] = {pa[ca][0], pa[ca][1], pa[ca][2]}, jv[3] = {pb[cb][0], pb[cb][1], pb[cb][2]};
+                        double h[3][2 * LMAX + 4];
+                        for (int x = 0; x < 3; x++) {
+                            int i = iv[x], j = jv[x];
+                            for (int t = 0; t <= i + j + 1; t++) {
+                                if (x == d) h[x][t] = 2.0 * a * E[x][i + 1][j][t] - (i && t <= i - 1 + j ? i * E[x][i - 1][j][t] : 0.0);
+                                else h[x][t] = t <= i + j ? E[x][i][j][t] : 0.0;
+                            }
+                        }
+                        double *hh = pp[n].H + ((size_t)(d * na + ca) * nb + cb) * nh;
+                        for (int t = 0; t <= iv[0] + jv[0] + 1; t++)
+                            for (int u = 0; u <= iv[1] + jv[1] + 1; u++)
+                                for (int v = 0; v <= iv[2] + jv[2] + 1; v++)
+                                    if (t + u + v <= la + lb + 1) hh[herm_index[t][u][v]] = cc * h[0][t] * h[1][u] * h[2][v];
+                    }
+        }
+}
+
+/* (d/dA a b|c d) of one quartet, three components: out (3, da, db, dc, dd); sphmask as eri_quartet_n */
+static void eri_ip_quartet(Shell S[4], int sphmask, double *out, double *work)
+{
+    PrimPair *pp[2];
+    double *hb[2];
+    int np[2];
+    for (int x = 0; x < 2; x++) {
+        Shell A = S[2 * x], B = S[2 * x + 1];
+        np[x] = A.nprim * B.nprim;
+        pp[x] = (PrimPair *)malloc(sizeof(PrimPair) * np[x]);
+        size_t nh = NHERM(A.l + B.l + (x == 0));
+        hb[x] = (double *)malloc(sizeof(double) * (size_t)np[x] * (x == 0 ? 3 : 1) * NCART(A.l) * NCART(B.l) * nh);
+        if (x == 0) build_prim_pairs_ip(A, B, pp[x], hb[x]);
+        else build_prim_pairs(A, B, pp[x], hb[x]);
+    }
+    eri_quartet_n(S[0], S[1], S[2], S[3], pp[0], np[0], pp[1], np[1], 3, sphmask, out, work);
+    for (int x = 0; x < 2; x++) { free(pp[x]); free(hb[x]); }
+}
+
+#define ERI_IP_WORK (3 * (size_t)MAXCART * MAXCART * MAXCART * MAXCART + ERI_WORK1)
+
+/* listed quartets: block q = (3, da, db, dc, dd) at out + offs[q], derivative on the centre of the FIRST shell */
+void orc_int2e_ip_quartets(int cart, double *out, const long long *offs, const int *quartets, int nq, const int *atm,
+                           int natm, const int *bas, int nbas, const double *env)
+{
+    (void)natm; (void)nbas;
+    init_herm();
+#pragma omp parallel
+    {
+        double *work = (double *)malloc(sizeof(double) * ERI_IP_WORK);
+#pragma omp for schedule(dynamic)
+        for (int q = 0; q < nq; q++) {
+            Shell S[4];
+            for (int x = 0; x < 4; x++) S[x] = get_shell(quartets[4 * q + x], atm, bas, env);
+            eri_ip_quartet(S, cart ? 0 : 15, out + offs[q], work);
+        }
+        free(work);
+    }
+}
+
+/* g (natm, 3) += sum_{a in A} sum_bcd (d_A a b|c d) [2 jscale D_ab D_cd - kscale D_ac D_bd] over ALL ordered quartets
+ * (D symmetric, (n, n), n = nao or ncart): the contraction dqc_eri_grad performs, without storing the derivative tensor.
+ * The ket pair runs over k >= l with both orderings' weights folded in. */
+void orc_eri_grad(int cart, double *g, const double *Dm, double jscale, double kscale, const int *atm, int natm,
+                  const int *bas, int nbas, const double *env)
+{
+    init_herm();
+    int *loc = (int *)malloc(sizeof(int) * (nbas + 1));
+    size_t n = make_loc(nbas, bas, cart, loc);
+    int sphmask = cart ? 0 : 15;
+    /* ket pair tables k >= l, built once */
+    int nkp = nbas * (nbas + 1) / 2;
+    PrimPair **kpp = (PrimPair **)calloc(nkp, sizeof(PrimPair *));
+    double **khb = (double **)calloc(nkp, sizeof(double *));
+#pragma omp parallel for schedule(dynamic)
+    for (int k = 0; k < nbas; k++)
+        for (int l = 0; l <= k; l++) {
+            int kl = k * (k + 1) / 2 + l;
+            Shell C = get_shell(k, atm, bas, env), D = get_shell(l, atm, bas, env);
+            kpp[kl] = (PrimPair *)malloc(sizeof(PrimPair) * C.nprim * D.nprim);
+            khb[kl] = (double *)malloc(sizeof(double) * (size_t)C.nprim * D.nprim * NCART(C.l) * NCART(D.l) * NHERM(C.l + D.l));
+            build_prim_pairs(C, D, kpp[kl], khb[kl]);
+        }
+    double *gacc = (double *)calloc((size_t)natm * 3, sizeof(double));
+#pragma omp parallel
+    {
+        double *work = (double *)malloc(sizeof(double) * ERI_IP_WORK);
+        double *blk = (double *)malloc(sizeof(double) * 3 * (size_t)MAXCART * MAXCART * MAXCART * MAXCART);
+        double *gloc = (double *)calloc((size_t)natm * 3, sizeof(double));
+#pragma omp for schedule(dynamic)
+        for (int ij = 0; ij < nbas * nbas; ij++) {
+            int i = ij / nbas, j = ij % nbas;
+            Shell A = get_shell(i, atm, bas, env), B = get_shell(j, atm, bas, env);
+            int np = A.nprim * B.nprim;
+            PrimPair *bp = (PrimPair *)malloc(sizeof(PrimPair) * np);
+            double *bh = (double *)malloc(sizeof(double) * (size_t)np * 3 * NCART(A.l) * NCART(B.l) * NHERM(A.l + B.l + 1));
+            build_prim_pairs_ip(A, B, bp, bh);
+            int da = ao_dim(A.l, cart), db = ao_dim(B.l, cart);
+            double acc[3] = {0, 0, 0};
+            for (int k = 0; k < nbas; k++)
+                for (int l = 0; l <= k; l++) {
+                    int kl = k * (k + 1) / 2 + l;
+                    Shell C = get_shell(k, atm, bas, env), D = get_shell(l, atm, bas, env);
+                    int dc = ao_dim(C.l, cart), dd = ao_dim(D.l, cart);
+                    eri_quartet_n(A, B, C, D, bp, np, kpp[kl], C.nprim * D.nprim, 3, sphmask, blk, work);
+                    size_t bsz = (size_t)da * db * dc * dd;
+                    double fold = k == l ? 1.0 : 2.0;
+                    for (int a = 0; a < da; a++)
+                        for (int b = 0; b < db; b++) {
+                            size_t ia = loc[i] + a, ib = loc[j] + b;
+                            double dab = Dm[ia * n + ib];
+                            for (int c = 0; c < dc; c++)
+                                for (int d = 0; d < dd; d++) {
+                                    size_t ic = loc[k] + c, id = loc[l] + d;
+                                    double w = 2.0 * jscale * fold * dab * Dm[ic * n + id];
+                                    if (k == l) w -= kscale * Dm[ia * n + ic] * Dm[ib * n + id];
+                                    else w -= kscale * (Dm[ia * n + ic] * Dm[ib * n + id] + Dm[ia * n + id] * Dm[ib * n + ic]);
+                                    size_t e = ((size_t)(a * db + b) * dc + c) * dd + d;
+                                    for (int x = 0; x < 3; x++) acc[x] += w * blk[x * bsz + e];
+                                }
+                        }
+                }
+            int at = bas[i * BAS_SLOTS + ATOM_OF];
+            for (int x = 0; x < 3; x++) gloc[at * 3 + x] += acc[x];
+            free(bp); free(bh);
+        }
+#pragma omp critical
+        for (int x = 0; x < natm * 3; x++) gacc[x] += gloc[x];
+        free(work); free(blk); free(gloc);
+    }
+    for (int x = 0; x < natm * 3; x++) g[x] += gacc[x];
+    for (int kl = 0; kl < nkp; kl++) { free(kpp[kl]); free(khb[kl]); }
+    free(kpp); free(khb); free(gacc); free(loc);
+}
+
+/* density-fitting derivatives over the concatenated tables (orbital shells [sh0, sh1), auxiliary shells [k0, k1)):
+ *   which 0: out (3, n, n, naux) = (d/dA_i i j|k), A the centre of i
+ *   which 1: out (3, n, n, naux) = (i j|d/dC k), C the centre of k
+ *   which 2: out (3, naux, naux) = (d/dC k|l),   C the centre of k
+ * the unit function of the 3- and 2-centre integrals always gets its l = 0 factor (it is not an AO) */
+void orc_df_ip(int which, int cart, double *out, const int *atm, int natm, const int *bas, int nbas, const double *env,
+               int sh0, int sh1, int k0, int k1)
+{
+    (void)natm; (void)nbas;
+    init_herm();
+    const int nsh = sh1 - sh0, nk = k1 - k0;
+    int *loc = (int *)malloc(sizeof(int) * (nsh + 1)), *kloc = (int *)malloc(sizeof(int) * (nk + 1));
+    size_t n = make_loc(nsh, bas + sh0 * BAS_SLOTS, cart, loc), naux = make_loc(nk, bas + k0 * BAS_SLOTS, cart, kloc);
+    int sph = cart ? 0 : 15;
+    int nwork = which == 2 ? nk * nk : nsh * nsh * nk;
+#pragma omp parallel
+    {
+        double *work = (double *)malloc(sizeof(double) * ERI_IP_WORK);
+        double *blk = (double *)malloc(sizeof(double) * 3 * (size_t)MAXCART * MAXCART * MAXCART * MAXCART);
+#pragma omp for schedule(dynamic)
+        for (int w = 0; w < nwork; w++) {
+            Shell S[4];
+            if (which == 2) {
+                int k = w / nk, l = w % nk;
+                Shell C = get_shell(k0 + k, atm, bas, env), D = get_shell(k0 + l, atm, bas, env);
+                S[0] = C; S[1] = unit_shell(C.r); S[2] = D; S[3] = unit_shell(D.r);
+                eri_ip_quartet(S, sph | 10, blk, work);
+                int dc = ao_dim(C.l, cart), dd = ao_dim(D.l, cart);
+                for (int x = 0; x < 3; x++)
+                    for (int c = 0; c < dc; c++)
+                        for (int d = 0; d < dd; d++)
+                            out[((size_t)x * naux + kloc[k] + c) * naux + kloc[l] + d] = blk[(x * dc + c) * dd + d];
+                continue;
+            }
+            int i = w / (nsh * nk), j = (w / nk) % nsh, k = w % nk;
+            Shell A = get_shell(sh0 + i, atm, bas, env), B = get_shell(sh0 + j, atm, bas, env), C = get_shell(k0 + k, atm, bas, env);
+            int da = ao_dim(A.l, cart), db = ao_dim(B.l, cart), dc = ao_dim(C.l, cart);
+            if (which == 0) {
+                S[0] = A; S[1] = B; S[2] = C; S[3] = unit_shell(C.r);
+                eri_ip_quartet(S, sph | 8, blk, work);
+            } else {
+                S[0] = C; S[1] = unit_shell(C.r); S[2] = A; S[3] = B;
+                eri_ip_quartet(S, sph | 2, blk, work);
+            }
+            for (int x = 0; x < 3; x++)
+                for (int a = 0; a < da; a++)
+                    for (int b = 0; b < db; b++)
+                        for (int c = 0; c < dc; c++) {
+                            double v = which == 0 ? blk[((x * da + a) * db + b) * dc + c] : blk[((x * dc + c) * da + a) * db + b];
+                            out[(((size_t)x * n + loc[i] + a) * n + loc[j] + b) * naux + kloc[k] + c] = v;
+                        }
+        }
+        free(work); free(blk);
+    }
+    free(loc); free(kloc);
 }

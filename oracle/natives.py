@@ -147,3 +147,98 @@ def boys(mmax, T):
 
 def num_threads():
     return lib().orc_num_threads()
+
+
+# ------------------------------------------------------------------------------------------------
+# derivative integrals (gradient checks): d/dA with A the centre of the FIRST function, raw Cartesian
+# monomials (cart=True) or solid harmonics; see orc_int1e_ip / orc_int2e_ip_quartets / orc_df_ip
+# ------------------------------------------------------------------------------------------------
+def _ncart(l):
+    return (l + 1) * (l + 2) // 2
+
+
+def ao_count(t, cart=False, shells=None):
+    ls = t.bas[:, 1] if shells is None else t.bas[shells[0]:shells[1], 1]
+    return int(sum(_ncart(int(l)) if cart else 2 * int(l) + 1 for l in ls))
+
+
+def ao_atom(t, cart=False):
+    """owning atom of every AO (spherical or Cartesian)"""
+    return np.concatenate([[int(b[0])] * (_ncart(int(b[1])) if cart else 2 * int(b[1]) + 1) for b in t.bas]).astype(np.int64)
+
+
+def int1e_ip(which, t, zs=None, cart=False):
+    """which 'ovlp' | 'kin' | 'nuc' -> (3, n, n): out[d, i, j] = d/dA_d <i|O|j>, A the centre of i (for 'nuc' the basis-centre
+    term only, V = all nuclei); 'nuc_op' -> (natm, 3, n, n): d/dC_d <i|-Z_C/|r - C||j> (the operator term of nucleus C)"""
+    code = {"ovlp": 0, "kin": 1, "nuc": 2, "nuc_op": 3}[which]
+    n = ao_count(t, cart)
+    out = np.zeros(((t.natm,) if code == 3 else ()) + (3, n, n))
+    zp = None
+    if zs is not None:
+        zs = np.ascontiguousarray(zs, dtype=np.float64)
+        zp = _p(zs)
+    lib().orc_int1e_ip(ctypes.c_int(code), ctypes.c_int(int(cart)), _p(out), *_tab(t), zp)
+    return out
+
+
+def int2e_ip_quartets(t, quartets, cart=False):
+    """(d/dA a b|c d) of the listed shell quartets (nq, 4): blocks (3, da, db, dc, dd), A the centre of the first shell"""
+    q = np.ascontiguousarray(quartets, dtype=np.int32).reshape(-1, 4)
+    ls = t.bas[q, 1]
+    dims = (ls + 1) * (ls + 2) // 2 if cart else 2 * ls + 1
+    sizes = 3 * np.prod(dims, axis=1).astype(np.int64)
+    offs = np.zeros(len(q) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=offs[1:])
+    out = np.zeros(int(offs[-1]))
+    lib().orc_int2e_ip_quartets(ctypes.c_int(int(cart)), _p(out), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+                                _p(q, ctypes.c_int), ctypes.c_int(len(q)), *_tab(t))
+    return [out[offs[i]:offs[i + 1]].reshape((3,) + tuple(int(d) for d in dims[i])) for i in range(len(q))]
+
+
+def eri_grad(t, dm, jscale=1.0, kscale=1.0, cart=False):
+    """(natm, 3): sum_{a in A} sum_bcd (d_A a b|c d) [2 jscale D_ab D_cd - kscale D_ac D_bd], D symmetric (n, n)"""
+    dm = np.ascontiguousarray(dm, dtype=np.float64)
+    assert dm.shape == (ao_count(t, cart),) * 2
+    g = np.zeros((t.natm, 3))
+    lib().orc_eri_grad(ctypes.c_int(int(cart)), _p(g), _p(dm), ctypes.c_double(jscale), ctypes.c_double(kscale), *_tab(t))
+    return g
+
+
+def df_ip(which, tc, orb_range, aux_range, cart=False):
+    """concatenated tables: 'ij|k' -> (3, n, n, naux) = (d/dA_i i j|k); 'k' -> (3, n, n, naux) = (i j|d/dC k);
+    '2c' -> (3, naux, naux) = (d/dC k|l)"""
+    code = {"ij|k": 0, "k": 1, "2c": 2}[which]
+    (s0, s1), (k0, k1) = orb_range, aux_range
+    n, naux = ao_count(tc, cart, (s0, s1)), ao_count(tc, cart, (k0, k1))
+    out = np.zeros((3, naux, naux) if code == 2 else (3, n, n, naux))
+    lib().orc_df_ip(ctypes.c_int(code), ctypes.c_int(int(cart)), _p(out), *_tab(tc),
+                    *(ctypes.c_int(int(v)) for v in (s0, s1, k0, k1)))
+    return out
+
+
+def int1e_grad(t, dm, wm, zs=None, cart=False):
+    """(natm, 3): 2 sum_{a in A} sum_b [D_ab <d_A a|T + V|b> - W_ab <d_A a|b>] + sum_ab D_ab d/dC <a|V_C|b> -- the contraction
+    dqc_int1e_grad performs (D, W symmetric), the operator term from its own integrals (no translational invariance)"""
+    at = ao_atom(t, cart)
+    g = np.zeros((t.natm, 3))
+    h = int1e_ip("kin", t, cart=cart) + int1e_ip("nuc", t, zs, cart=cart)
+    s = int1e_ip("ovlp", t, cart=cart)
+    per_ao = 2.0 * (np.einsum("dij,ij->id", h, dm) - np.einsum("dij,ij->id", s, wm))
+    np.add.at(g, at, per_ao)
+    g += np.einsum("cdij,ij->cd", int1e_ip("nuc_op", t, zs, cart=cart), dm)
+    return g
+
+
+def df_grad(tc, orb_range, aux_range, dm, coef, cart=False):
+    """(natm_tc, 3) over the concatenated tables: sum D_ij c_k d(ij|k) - 1/2 c^T dM c (what dqc_df_grad adds), D symmetric"""
+    (s0, s1), (k0, k1) = orb_range, aux_range
+    at = ao_atom(tc, cart)
+    n = ao_count(tc, cart, (s0, s1))
+    ao0 = ao_count(tc, cart, (0, s0))
+    ax0 = ao_count(tc, cart, (0, k0))
+    orb_at, aux_at = at[ao0:ao0 + n], at[ax0:ax0 + len(coef)]
+    g = np.zeros((tc.natm, 3))
+    np.add.at(g, orb_at, 2.0 * np.einsum("dijk,ij,k->id", df_ip("ij|k", tc, orb_range, aux_range, cart), dm, coef))
+    np.add.at(g, aux_at, np.einsum("dijk,ij,k->kd", df_ip("k", tc, orb_range, aux_range, cart), dm, coef))
+    np.add.at(g, aux_at, -np.einsum("dkl,k,l->kd", df_ip("2c", tc, orb_range, aux_range, cart), coef, coef))
+    return g

@@ -64,3 +64,15 @@ def seeded_dm_ao(nao, nel, S, seed):
     A = rng.standard_normal((nao, max(nel // 2, 1)))
     D = A @ A.T
     return D * (nel / np.trace(D @ S))
+
+
+# gradient-term checks (tests/test_oracle_cpu.py, tests/test_gpu_gradient_terms.py): a distorted, non-symmetric three-atom
+# geometry and a small basis with one shell of every l = 0 ... 4 (contracted tight + diffuse where two exponents are given),
+# as raw (l, alphas, coeffs) lists per atom
+GRAD3 = ([8, 7, 1], [[0.1, -0.2, 0.3], [1.9, 0.4, -0.5], [-0.7, 1.6, 0.9]])
+GRAD3_BAS = [[(0, [4.0, 0.9], [0.5, 0.6]), (2, [1.1], [1.0]), (4, [1.3, 0.5], [0.6, 0.5])],
+             [(1, [1.7, 0.45], [0.6, 0.5]), (3, [0.9], [1.0])],
+             [(0, [0.6], [1.0]), (1, [0.7], [1.0])]]
+GRAD3_AUX = [[(0, [0.5], [1.0]), (2, [0.8], [1.0]), (4, [1.0], [1.0])],
+             [(1, [0.7], [1.0]), (3, [0.9], [1.0])],
+             [(0, [0.6], [1.0]), (4, [0.7], [1.0])]]

@@ -751,3 +751,178 @@ def test_ccpvtz_nitrogen_oxygen_tables_published_energies():
     assert abs(oh.run_scf(h2o, "cc-pvtz")[0] - (-76.0571)) < 2e-4
     assert abs(oh.run_scf(h2o, "cc-pvdz")[0] - (-76.0268)) < 2e-4
     assert abs(oh.run_scf("N 0 0 0; N 0 0 %.10f" % (1.0977 / 0.52917721), "cc-pvtz")[0] - (-108.9835)) < 2e-4
+
+
+# ------------------------------------------------------------------------------------------------
+# derivative integrals (orc_int1e_ip, orc_int2e_ip_quartets, orc_eri_grad, orc_df_ip) against 5-point central differences of the
+# oracle's own S, T, V, int2e, int3c2e and int2c2e (those are pinned to the reference-generated goldens above)
+# ------------------------------------------------------------------------------------------------
+def _fd5(f, h=2e-3):
+    return (-f(2 * h) + 8 * f(h) - 8 * f(-h) + f(-2 * h)) / (12 * h)
+
+
+def _moved(t, atoms, d, h):
+    """a copy of the tables with atoms `atoms` displaced by h along d (the env holds the coordinates)"""
+    import copy
+    t2 = copy.copy(t)
+    t2.env = t.env.copy()
+    for a in atoms:
+        t2.env[t.atm[a, 1] + d] += h
+    return t2
+
+
+def _ghost_tables(zs=None):
+    """GRAD3 with the shells on Z = 0 ghost atoms (0, 1, 2) and the nuclei on shell-less atoms (3, 4, 5) at the same positions:
+    moving a ghost moves basis centres only, moving a nucleus moves the operator only"""
+    zs_, pos = M.GRAD3
+    shells = [[(l, np.asarray(a, float), ob.wfnormalize(l, a, c)) for (l, a, c) in ab] for ab in M.GRAD3_BAS]
+    return ob.Tables([0, 0, 0] + list(zs_), list(pos) * 2, shells + [[], [], []])
+
+
+def _pair_deriv(ip, mask):
+    """d/dA O_ij of a symmetric one-electron matrix from <d_A i|O|j>: mask the first index, add the transpose"""
+    x = ip * mask[None, :, None]
+    return x + x.transpose(0, 2, 1)
+
+
+def _close(an, fd, tol=1e-7):
+    return np.abs(an - fd).max() <= tol * np.abs(an).max()
+
+
+def test_grad_oracle_int1e_derivatives_vs_finite_differences():
+    """<d a|b>, <d a|T|b>, <d a|V|b> (basis centres) and the operator derivative d/dC <a|V_C|b>, element by element, for
+    shells s ... g on a distorted three-atom geometry; the V split through ghost atoms; fractional charges"""
+    t = _ghost_tables()
+    at = nat.ao_atom(t)
+    zfrac = np.array([0.0, 0.0, 0.0, 7.7, 6.3, 1.4])
+    for which in ("ovlp", "kin", "nuc"):
+        ip = nat.int1e_ip(which, t, zfrac if which == "nuc" else None)
+        for a in range(3):
+            an = _pair_deriv(ip, (at == a).astype(float))
+            for d in range(3):
+                kw = {"zs": zfrac} if which == "nuc" else {}
+                fd = _fd5(lambda h: nat.int1e(which, _moved(t, [a], d, h), **kw))
+                assert _close(an[d], fd), (which, a, d, np.abs(an[d] - fd).max())
+    for zs in (None, zfrac):
+        op = nat.int1e_ip("nuc_op", t, zs)
+        assert np.abs(op[:3]).max() == 0.0  # ghosts carry no charge
+        for c in range(3, 6):
+            for d in range(3):
+                fd = _fd5(lambda h: nat.int1e("nuc", _moved(t, [c], d, h), zs))
+                assert _close(op[c, d], fd), (c, d, np.abs(op[c, d] - fd).max())
+    # the basis-centre nuclear term is linear in the charges; the operator term of a nucleus scales with its own charge
+    ip1, ip2 = nat.int1e_ip("nuc", t), nat.int1e_ip("nuc", t, 2.0 * np.array([0, 0, 0, 8, 7, 1.0]))
+    assert np.abs(ip2 - 2.0 * ip1).max() <= 1e-13 * np.abs(ip1).max()
+
+
+def _sph_to_cart(t):
+    """T (nao, ncart), block diagonal, from the oracle's own c2s tables"""
+    blocks = [nat.cart2sph(int(l)) for l in t.bas[:, 1]]
+    out = np.zeros((sum(b.shape[0] for b in blocks), sum(b.shape[1] for b in blocks)))
+    r = c = 0
+    for b in blocks:
+        out[r:r + b.shape[0], c:c + b.shape[1]] = b
+        r, c = r + b.shape[0], c + b.shape[1]
+    return out
+
+
+def _full_eri_ip(t, cart=False):
+    """I[d, i, j, k, l] = (d/dA_i i j|k l) over all ordered shell quartets"""
+    nb = t.nbas
+    q = np.array([(i, j, k, l) for i in range(nb) for j in range(nb) for k in range(nb) for l in range(nb)])
+    blocks = nat.int2e_ip_quartets(t, q, cart=cart)
+    n = nat.ao_count(t, cart)
+    loc = np.concatenate([[0], np.cumsum([nat._ncart(int(l)) if cart else 2 * int(l) + 1 for l in t.bas[:, 1]])])
+    out = np.zeros((3, n, n, n, n))
+    for (i, j, k, l), b in zip(q, blocks):
+        out[:, loc[i]:loc[i + 1], loc[j]:loc[j + 1], loc[k]:loc[k + 1], loc[l]:loc[l + 1]] = b
+    return out
+
+
+def test_grad_oracle_eri_derivatives_vs_finite_differences():
+    """(d_A a b|c d) for every ordered quartet of shells s ... g (h companions), element by element against central
+    differences of int2e; the C-side contraction orc_eri_grad against the numpy contraction of those integrals, for
+    jscale / kscale apart, in the spherical and the Cartesian AO basis"""
+    t = ob.make_tables(M.GRAD3, M.GRAD3_BAS)
+    at = nat.ao_atom(t)
+    I = _full_eri_ip(t)
+    perms = [(0, 1, 2, 3, 4), (0, 2, 1, 3, 4), (0, 3, 4, 1, 2), (0, 3, 4, 2, 1)]  # derivative on the i, j, k, l position
+    for a in range(3):
+        m = (at == a).astype(float)
+        an = sum(I.transpose(p) * m.reshape([1] + [-1 if x == pos else 1 for x in range(4)])
+                 for pos, p in enumerate(perms))
+        for d in range(3):
+            fd = _fd5(lambda h: nat.int2e(_moved(t, [a], d, h)))
+            assert _close(an[d], fd), (a, d, np.abs(an[d] - fd).max())
+    rng = np.random.default_rng(5)
+    D = rng.standard_normal((t.nao, t.nao))
+    D = D + D.T
+    Tm = _sph_to_cart(t)
+    for js, ks in ((1.0, 0.0), (0.0, 1.0), (0.7, -1.3)):
+        X = 2 * js * np.einsum("ab,cd->abcd", D, D) - ks * np.einsum("ac,bd->abcd", D, D)
+        per_ao = np.einsum("xabcd,abcd->ax", I, X)
+        ref = np.zeros((t.natm, 3))
+        np.add.at(ref, at, per_ao)
+        g = nat.eri_grad(t, D, js, ks)
+        gc = nat.eri_grad(t, Tm.T @ D @ Tm, js, ks, cart=True)
+        assert np.abs(g - ref).max() <= 1e-12 * np.abs(ref).max()
+        assert np.abs(gc - ref).max() <= 1e-12 * np.abs(ref).max()
+        assert np.abs(g.sum(0)).max() <= 1e-11 * np.abs(ref).max()
+    # linear in (jscale, kscale)
+    g10, g01 = nat.eri_grad(t, D, 1.0, 0.0), nat.eri_grad(t, D, 0.0, 1.0)
+    assert np.abs(nat.eri_grad(t, D, 0.7, -1.3) - (0.7 * g10 - 1.3 * g01)).max() <= 1e-12 * np.abs(g10).max()
+
+
+def test_grad_oracle_df_derivatives_vs_finite_differences():
+    """(d_A i j|k), (i j|d_C k) and (d_C k|l) with orbital and auxiliary shells s ... g: the concatenated tables list every
+    atom twice, so moving the orbital parent or the auxiliary parent alone isolates each derivative, element by element;
+    the contraction natives.df_grad against central differences of sum D c (ij|k) - 1/2 c M c"""
+    tc, orb, aux = ob.make_tables_df(M.GRAD3, M.GRAD3_BAS, M.GRAD3_AUX)
+    at = nat.ao_atom(tc)
+    n, naux = nat.ao_count(tc, shells=orb), nat.ao_count(tc, shells=aux)
+    oat, xat = at[:n], at[n:n + naux]
+    J0, J1, J2 = nat.df_ip("ij|k", tc, orb, aux), nat.df_ip("k", tc, orb, aux), nat.df_ip("2c", tc, orb, aux)
+    for a in range(3):
+        mo, mx = (oat == a).astype(float), (xat == a + 3).astype(float)
+        an3 = J0 * mo[None, :, None, None]
+        an3 = an3 + an3.transpose(0, 2, 1, 3)
+        anx = J1 * mx[None, None, None, :]
+        an2 = J2 * mx[None, :, None]
+        an2 = an2 + an2.transpose(0, 2, 1)
+        for d in range(3):
+            fd = _fd5(lambda h: nat.int3c2e(_moved(tc, [a], d, h), orb, aux))
+            assert _close(an3[d], fd), (a, d)
+            fd = _fd5(lambda h: nat.int3c2e(_moved(tc, [a + 3], d, h), orb, aux))
+            assert _close(anx[d], fd), (a, d)
+            fd = _fd5(lambda h: nat.int2c2e(_moved(tc, [a + 3], d, h), aux))
+            assert _close(an2[d], fd), (a, d)
+    rng = np.random.default_rng(2)
+    D = rng.standard_normal((n, n))
+    D = D + D.T
+    c = rng.standard_normal(naux) * 0.3
+    g = nat.df_grad(tc, orb, aux, D, c)
+    for a in range(6):
+        for d in range(3):
+            fd = _fd5(lambda h: (lambda tt: np.einsum("ijk,ij,k->", nat.int3c2e(tt, orb, aux), D, c)
+                                 - 0.5 * c @ nat.int2c2e(tt, aux) @ c)(_moved(tc, [a], d, h)))
+            assert abs(g[a, d] - fd) <= 1e-7 * np.abs(g).max(), (a, d)
+
+
+def test_grad_oracle_int1e_contraction_vs_finite_differences():
+    """natives.int1e_grad (what dqc_int1e_grad adds) against central differences of sum D (T + V) - sum W S, real atoms moving
+    with their nuclei, integer and fractional charges"""
+    t = ob.make_tables(M.GRAD3, M.GRAD3_BAS)
+    rng = np.random.default_rng(3)
+    D, W = rng.standard_normal((2, t.nao, t.nao))
+    D, W = D + D.T, W + W.T
+    for zs in (None, np.array([7.6, 6.9, 1.2])):
+        g = nat.int1e_grad(t, D, W, zs)
+        for a in range(3):
+            for d in range(3):
+                fd = _fd5(lambda h: (lambda tt: np.sum(D * (nat.int1e("kin", tt) + nat.int1e("nuc", tt, zs)))
+                                     - np.sum(W * nat.int1e("ovlp", tt)))(_moved(t, [a], d, h)))
+                assert abs(g[a, d] - fd) <= 1e-7 * np.abs(g).max(), (zs, a, d)
+        # Cartesian form: the same numbers from D_cart = T^T D T
+        Tm = _sph_to_cart(t)
+        gc = nat.int1e_grad(t, Tm.T @ D @ Tm, Tm.T @ W @ Tm, zs, cart=True)
+        assert np.abs(gc - g).max() <= 1e-12 * np.abs(g).max()
