@@ -339,6 +339,120 @@ __global__ __launch_bounds__(64) void int1e_grad_kernel(double *__restrict__ gra
         for (int d = 0; d < 3; d++) atomicAdd(&grad[blockIdx.y * 3 + d], -2.0 * gn[d]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// electronic electrostatic potential at points: V_C = sum_ab D_ab <a| 1/|r - P_C| |b>  (the alchemical derivative
+// dE/dZ_C = -V_C + ...; the Rys quadrature of the nuclear attraction, contracted with D on the fly)
+// ---------------------------------------------------------------------------------------------
+constexpr int PL1 = DQC_LMAX + 1;
+
+template <int N>
+DQC_DEV double nuc_pot_accumulate(int la, int lb, double p, const double *P, const double *A, const double *AB, const double *C,
+                                  const double *dab, const double *dba, size_t nc) {
+    // sum_{ca,cb} (D[ca][cb] + D^T[ca][cb]) (ca | 1/|r - C| | cb) / (pref) -- dba == nullptr on a diagonal shell pair
+    const double X = p * ((P[0] - C[0]) * (P[0] - C[0]) + (P[1] - C[1]) * (P[1] - C[1]) + (P[2] - C[2]) * (P[2] - C[2]));
+    double u[N], w[N];
+    rys_roots<N>(X, u, w);
+    double acc = 0.0;
+    for (int r = 0; r < N; r++) {
+        double g[3][2 * DQC_LMAX + 1][PL1];
+        const double b10 = 0.5 * (1.0 - u[r]) / p;
+        for (int d = 0; d < 3; d++) {
+            const double c00 = (P[d] - A[d]) - u[r] * (P[d] - C[d]);
+            g[d][0][0] = 1.0;
+            if (la + lb > 0) g[d][1][0] = c00;
+            for (int n = 1; n < la + lb; n++) g[d][n + 1][0] = c00 * g[d][n][0] + n * b10 * g[d][n - 1][0];
+            for (int j = 1; j <= lb; j++)
+                for (int i = 0; i <= la + lb - j; i++) g[d][i][j] = g[d][i + 1][j - 1] + AB[d] * g[d][i][j - 1];
+        }
+        double sr = 0.0;
+        int ca = 0;
+        for (int ax = la; ax >= 0; ax--)
+            for (int ay = la - ax; ay >= 0; ay--, ca++) {
+                const int az = la - ax - ay;
+                int cb = 0;
+                for (int bx = lb; bx >= 0; bx--)
+                    for (int by = lb - bx; by >= 0; by--, cb++) {
+                        const int bz = lb - bx - by;
+                        const double dd = dab[ca * nc + cb] + (dba != nullptr ? dba[cb * nc + ca] : 0.0);
+                        sr += dd * g[0][ax][bx] * g[1][ay][by] * g[2][az][bz];
+                    }
+            }
+        acc += w[r] * sr;
+    }
+    return acc;
+}
+
+// One thread per unordered shell pair (a >= b), 256 pairs per block; the points are split over grid.y (a block walks the points
+// blockIdx.y, blockIdx.y + gridDim.y, ...).  Per point the block's threads are summed in a fixed order (wave butterfly, then
+// the four wave sums in order) and the block's partial is STORED to part[point][blockIdx.x]: no atomics, and the second pass
+// (int1e_potential_sum) adds the partials of a point in block order, so the result is bit-reproducible.
+constexpr int POT_BLOCK = 256;
+__global__ __launch_bounds__(POT_BLOCK) void int1e_potential_kernel(double *__restrict__ part, DevShells sh, const int *__restrict__ cao,
+                                                                    const double *__restrict__ dcart, int ncart,
+                                                                    const double *__restrict__ pts, int npts) {
+    __shared__ double swave[POT_BLOCK / 64];
+    const long long npair = (long long)sh.nsh * (sh.nsh + 1) / 2;
+    const long long q = (long long)blockIdx.x * POT_BLOCK + threadIdx.x;
+    const bool live = q < npair;
+    int ish = 0, jsh = 0;
+    if (live) {
+        ish = (int)((sqrt(8.0 * (double)q + 1.0) - 1.0) * 0.5);
+        while ((long long)ish * (ish + 1) / 2 > q) ish--;
+        while ((long long)(ish + 1) * (ish + 2) / 2 <= q) ish++;
+        jsh = (int)(q - (long long)ish * (ish + 1) / 2);
+    }
+    const int la = sh.l[ish], lb = sh.l[jsh];
+    const size_t nc = ncart;
+    const double A[3] = {sh.xyz[ish * 3], sh.xyz[ish * 3 + 1], sh.xyz[ish * 3 + 2]};
+    const double B[3] = {sh.xyz[jsh * 3], sh.xyz[jsh * 3 + 1], sh.xyz[jsh * 3 + 2]};
+    const double AB[3] = {A[0] - B[0], A[1] - B[1], A[2] - B[2]};
+    const double ab2 = AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2];
+    const double *dab = dcart + (size_t)cao[ish] * nc + cao[jsh];
+    const double *dba = ish != jsh ? dcart + (size_t)cao[jsh] * nc + cao[ish] : nullptr;  // (V is symmetric: D_ab + D_ba)
+    const int nroots = (la + lb) / 2 + 1;
+    for (int ic = blockIdx.y; ic < npts; ic += gridDim.y) {
+        const double C[3] = {pts[ic * 3], pts[ic * 3 + 1], pts[ic * 3 + 2]};
+        double v = 0.0;
+        if (live) {
+            for (int ip = 0; ip < sh.nprim[ish]; ip++)
+                for (int jp = 0; jp < sh.nprim[jsh]; jp++) {
+                    const double a = sh.exps[sh.prim_off[ish] + ip], b = sh.exps[sh.prim_off[jsh] + jp];
+                    const double cc = sh.coefs[sh.prim_off[ish] + ip] * sh.coefs[sh.prim_off[jsh] + jp];
+                    const double p = a + b;
+                    const double pref = cc * exp(-a * b / p * ab2) * 2.0 * M_PI / p;
+                    double P[3];
+                    for (int d = 0; d < 3; d++) P[d] = (a * A[d] + b * B[d]) / p;
+                    double s;
+                    switch (nroots) {
+                    case 1: s = nuc_pot_accumulate<1>(la, lb, p, P, A, AB, C, dab, dba, nc); break;
+                    case 2: s = nuc_pot_accumulate<2>(la, lb, p, P, A, AB, C, dab, dba, nc); break;
+                    case 3: s = nuc_pot_accumulate<3>(la, lb, p, P, A, AB, C, dab, dba, nc); break;
+                    case 4: s = nuc_pot_accumulate<4>(la, lb, p, P, A, AB, C, dab, dba, nc); break;
+                    default: s = nuc_pot_accumulate<5>(la, lb, p, P, A, AB, C, dab, dba, nc); break;
+                    }
+                    v += pref * s;
+                }
+        }
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = 0.0;
+            for (int wv = 0; wv < POT_BLOCK / 64; wv++) t += swave[wv];
+            part[(size_t)ic * gridDim.x + blockIdx.x] = t;
+        }
+        __syncthreads();  // (swave is rewritten for the next point)
+    }
+}
+
+__global__ __launch_bounds__(64) void int1e_potential_sum(double *__restrict__ out, const double *__restrict__ part, int nblk, int npts) {
+    const int ic = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ic >= npts) return;
+    double t = 0.0;
+    for (int k = 0; k < nblk; k++) t += part[(size_t)ic * nblk + k];
+    out[ic] = t;
+}
+
 }  // namespace dqc
 
 extern "C" {
@@ -488,6 +602,45 @@ int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart,
                        ncart, natm, d_xyz, d_z);
     DQC_CHECK_LAUNCH();
     DQC_HIP(hipStreamSynchronize(st));
+    return DQC_OK;
+}
+
+int dqc_int1e_potential(double *d_out, const double *d_dcart, const double *d_points, int npts, const int *atm, int natm,
+                        const int *bas, int nbas, const double *env, int nenv, void *stream) {
+    // d_out[C] = sum_ab D_ab <a| 1/|r - P_C| |b>, C < npts; d_dcart (ncart, ncart) Cartesian-basis density, d_points (npts, 3)
+    // device coordinates.  Stream-ordered: this call only enqueues.
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    if (npts < 0) { set_error("dqc_int1e_potential: npts must be >= 0"); return DQC_EINVAL; }
+    Basis b;
+    int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, nullptr);
+    if (rc) return rc;
+    if (npts == 0) return DQC_OK;
+    if (nbas == 0) {
+        DQC_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * npts, st));
+        return DQC_OK;
+    }
+    std::vector<int> cao;
+    int ncart;
+    cart_offsets(b, nbas, cao, ncart);
+    DevPool pool(st);
+    DevShells ds;
+    int *d_cao = nullptr;
+    if ((rc = upload_shells(ds, b, pool, st)) || (rc = pool.upload(&d_cao, cao, st))) {
+        set_error("dqc_int1e_potential: device upload failed");
+        return rc;
+    }
+    const long long npair = (long long)nbas * (nbas + 1) / 2;
+    const long long nblk = (npair + POT_BLOCK - 1) / POT_BLOCK;
+    const int ny = npts < 65535 ? npts : 65535;
+    double *d_part = nullptr;
+    if ((rc = pool.alloc(&d_part, (size_t)nblk * npts))) { set_error("dqc_int1e_potential: out of memory"); return rc; }
+    hipLaunchKernelGGL(int1e_potential_kernel, dim3((unsigned)nblk, (unsigned)ny), dim3(POT_BLOCK), 0, st, d_part, ds, d_cao, d_dcart,
+                       ncart, d_points, npts);
+    DQC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(int1e_potential_sum, dim3((unsigned)((npts + 63) / 64)), dim3(64), 0, st, d_out, (const double *)d_part, (int)nblk,
+                       npts);
+    DQC_CHECK_LAUNCH();
     return DQC_OK;
 }
 

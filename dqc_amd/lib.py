@@ -80,6 +80,7 @@ def load():
     lib.dqc_cart2sph_matrix.argtypes = [dp, ip, c_int]
     lib.dqc_int1e_grad.argtypes = [c_dp, c_dp, c_dp] + tab + [dp, c_vp]
     lib.dqc_eri_grad.argtypes = [c_dp, c_dp, ctypes.c_double, ctypes.c_double] + tab + [c_vp]
+    lib.dqc_int1e_potential.argtypes = [c_dp, c_dp, c_dp, c_int] + tab + [c_vp]
     lib.dqc_df_grad.argtypes = [c_dp, c_dp, c_dp] + tab + [c_int, c_int, c_int, c_int, c_vp]
     lib.dqc_becke_weights.argtypes = [c_dp, c_dp, c_vp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.c_double, c_vp]
     lib.dqc_becke_weights_grad.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_vp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.c_double, c_vp]
@@ -355,6 +356,17 @@ def int1e_grad(grad, dcart, wcart, tab, zs=None):
     with _on(grad.device) as st_:
         _check(load().dqc_int1e_grad(_ptr(grad), _ptr(dcart), _ptr(wcart), *tab.args(), zp, st_), "dqc_int1e_grad")
     return grad
+
+
+def int1e_potential(dcart, points, tab):
+    """(npts,) = sum_ab D_ab <a| 1/|r - P_C| |b> at the points (npts, 3); dcart (ncart, ncart) Cartesian-basis density (T^T D T)"""
+    points = points.to(device=dcart.device, dtype=torch.float64).contiguous()
+    npts = int(points.shape[0])
+    assert points.shape == (npts, 3), "points must be (npts, 3)"
+    out = torch.empty(npts, dtype=torch.float64, device=dcart.device)
+    with _on(dcart.device) as st_:
+        _check(load().dqc_int1e_potential(_ptr(out), _ptr(dcart), _ptr(points), npts, *tab.args(), st_), "dqc_int1e_potential")
+    return out
 
 
 def eri_grad(grad, dcart, kscale, tab, jscale=1.0):

@@ -47,7 +47,8 @@ class _Engine:
         self.knvext = self.hamilton.get_kinnucl()
         self.shape = self.knvext.shape
         self.dtype, self.device = self.knvext.dtype, self.knvext.device
-        self._enuc = torch.as_tensor(system.get_nuclei_energy()).to(device=self.device, dtype=self.dtype)  # on the device once
+        # (detached: the energy's derivatives come from dqc_amd.autograd, not from a graph through the SCF)
+        self._enuc = torch.as_tensor(system.get_nuclei_energy()).detach().to(device=self.device, dtype=self.dtype)  # on the device once
         # Mol(orthogonalize_basis=False): the Fock matrix lives in the raw AO basis and `diagonalize` is the generalised problem
         # F C = S C e (hf.py:227-247: lsymeig(A=fock, M=ovlp)).  Solved through S^-1/2: C = S^-1/2 U, U from eigh(S^-1/2 F S^-1/2)
         self.ovlp, self._sinvh = None, None
@@ -386,11 +387,15 @@ class SCF_QCCalc:
                           % (self.niter, self.scf_error, opts["f_tol"]))
 
     def energy(self):
+        """the converged energy; differentiable (torch.autograd) with respect to the caller's positions, floating-point charges,
+        efield, vext, orb_weights and the parameters of a torch.nn.Module functional (dqc_amd/autograd.py) -- when none of them
+        requires grad, or grad mode is off, the plain detached tensor"""
         assert self._has_run
         e = getattr(self, "_energy", None)  # the lockstep driver keeps dm2energy(dm) of the final Fock build (same call, same dm)
-        if e is not None:
-            return e
-        return self._engine.dm2energy(self._dm)
+        if e is None:
+            e = self._engine.dm2energy(self._dm)
+        from . import autograd
+        return autograd.energy(self, e)
 
     def aodm(self):
         assert self._has_run

@@ -21,6 +21,12 @@ class Mol:
         self._basis_inp = basis
         self._grid = None
         atomzs, atompos = parse_moldesc(moldesc, dtype=dtype)
+        # the caller's tensors are kept for the energy's autograd node (dqc_amd/autograd.py); everything handed down to the
+        # Hamiltonian, the grid and the basis is detached, so the SCF runs on plain values (no graph, no grid autograd path)
+        self._grad_leaves = {"atompos": atompos}
+        if atomzs.is_floating_point():
+            self._grad_leaves["atomzs"] = atomzs
+        atomzs, atompos = atomzs.detach(), atompos.detach()
         self._atomzs, self._atompos = atomzs, atompos
         self._atombases = make_atombases(atomzs, atompos, basis)
         self._user_weights = None
@@ -32,6 +38,8 @@ class Mol:
                 raise TypeError("Specifying orb_weights must be in SpinParam type")
             assert orb_weights.u.ndim == 1 and orb_weights.d.ndim == 1 and len(orb_weights.u) == len(orb_weights.d)
             wu, wd = orb_weights.u.to(dtype), orb_weights.d.to(dtype)
+            self._grad_leaves["orb_weights"] = (wu, wd)
+            wu, wd = wu.detach(), wd.detach()
             if not (bool(torch.all(wu[:-1] - wu[1:] > -1e-4)) and bool(torch.all(wd[:-1] - wd[1:] > -1e-4))):
                 import warnings
                 warnings.warn("The orbitals should be ordered in a non-increasing manner. "
@@ -69,14 +77,16 @@ class Mol:
             self._ndn = (int(round(nelecs)) - spin) // 2
         if vext is not None:
             vext = vext.to(device=self._device, dtype=dtype)
+            self._grad_leaves["vext"] = vext
+            vext = vext.detach()
         # mol.py:445-474: a tensor -> 1-tuple; every element flattened ((3,), (3, 3) -> (9,), ...)
         if isinstance(efield, torch.Tensor):
             efield = (efield,)
         if efield is not None:
             for i, ef in enumerate(efield):
                 assert ef.numel() == 3 ** (i + 1), "The %d-th tuple element of efield must have %d elements" % (i, 3 ** (i + 1))
-            # no autograd path runs through the field here (the properties are Hellmann-Feynman expectation values): a
-            # requires_grad leaf, as the reference's fixtures pass, is detached
+            # the SCF sees detached, flattened copies; the caller's tensors (their own shapes) are the energy's autograd inputs
+            self._grad_leaves["efield"] = tuple(efield)
             efield = tuple(ef.detach().reshape(-1) for ef in efield)
         self._efield, self._vext = efield, vext
         self._orthogonalize_basis, self._aoparamzer = orthogonalize_basis, ao_parameterizer
@@ -189,8 +199,11 @@ class Mol:
         return self._grid
 
     def get_nuclei_energy(self):
-        z = self._atomzs.to(self._dtype)
-        r = torch.cdist(self._atompos, self._atompos) + torch.eye(len(z), dtype=self._dtype)
+        """E_nn of the caller's positions and charges (differentiable through them, as the reference's mol.py:252-260); the
+        SCF engine adds the detached value"""
+        pos = self._grad_leaves["atompos"]
+        z = self._grad_leaves.get("atomzs", self._atomzs).to(self._dtype)
+        r = torch.cdist(pos, pos) + torch.eye(len(z), dtype=self._dtype)
         q = (z.unsqueeze(0) * z.unsqueeze(1)) / r
         return (torch.sum(q) - torch.sum(torch.diagonal(q))) * 0.5
 

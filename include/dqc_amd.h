@@ -256,6 +256,12 @@ int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart,
                    const int *bas, int nbas, const double *env, int nenv, const double *zs, void *stream);
 int dqc_eri_grad(double *d_grad, const double *d_dcart, double jscale, double kscale, const int *atm, int natm, const int *bas,
                  int nbas, const double *env, int nenv, void *stream);
+/* electronic electrostatic potential at npts device points (the alchemical derivative dE/dZ_C = -V_C + ...):
+ *   d_out[C] = sum_ab D_ab <a| 1/|r - P_C| |b>,   d_points (npts, 3), d_out (npts,)
+ * D in the CARTESIAN AO basis as for dqc_int1e_grad (D_cart = T^T D_ao T).  Contracted on the fly; per-block partials are
+ * stored and summed in a fixed order (no atomics: bit-reproducible).  OVERWRITES d_out; enqueue only.  Shells up to g. */
+int dqc_int1e_potential(double *d_out, const double *d_dcart, const double *d_points, int npts, const int *atm, int natm,
+                        const int *bas, int nbas, const double *env, int nenv, void *stream);
 /* gradient of the density-fitted Coulomb energy E_J = 1/2 t^T M^-1 t (dfmol.py:60-79 differentiated):
  *   d_grad += sum D_ij c_k d(ij|k) - 1/2 sum c_k c_l d(k|l),  c = M^-1 t,
  * over the concatenated tables of dqc_int3c2e; d_dcart (ncart, ncart) / d_ccart (ncart): density matrix and fit
