@@ -126,13 +126,6 @@ class DeviceLoop:
         self._build_from(fmix)
         self.host.copy_(self.stats, non_blocking=True)
 
-    def _clear_memos(self):
-        h = self.eng.hamilton
-        h._jk_cache = None
-        h._jkpol_cache = None
-        h._dm_factor = None
-        h._energy_memo = None
-
     def _capture(self):
         dev = self.eng.device
         # warm-up on a side stream (allocator, lazy kernel attributes), from a scratch copy of the state; then capture
@@ -151,7 +144,7 @@ class DeviceLoop:
             self._iteration()
         for t, k in zip((self.fock, self.dm, self.etot, self.perr, self.fh, self.eh, self.gram, self.count), keep):
             t.copy_(k)  # (a capture does not execute: belt and braces)
-        self._clear_memos()
+        self.eng.hamilton.clear_memos()
 
     # ------------------------------------------------------------------ the loop
     def run(self, qc, opts):

@@ -22,7 +22,6 @@ class GraphedFock:
         if engine.polarized:
             raise NotImplementedError("GraphedFock covers the restricted engines; UHF/UKS run eagerly")
         self.engine = engine
-        h = engine.hamilton
         n, norb = engine.shape[-1], engine.norb
         self.orb = torch.zeros((n, norb), dtype=engine.dtype, device=engine.device)
         self.orb[:norb, :norb] = torch.eye(norb, dtype=engine.dtype, device=engine.device)  # any orthonormal start
@@ -39,10 +38,7 @@ class GraphedFock:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.dm, self.fock, self.energy = self._body()
-        h._jk_cache = None     # the memoised tensors belong to the graph's private pool
-        h._jkpol_cache = None
-        h._dm_factor = None
-        h._energy_memo = None
+        engine.hamilton.clear_memos()  # the memoised tensors belong to the graph's private pool
 
     def _body(self):
         dm = self.engine.hamilton.ao_orb2dm(self.orb, self.weight)
@@ -106,11 +102,7 @@ class GraphedSCFStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.fock, self.dm, self.err = self._body()
-        h = engine.hamilton
-        h._jk_cache = None
-        h._jkpol_cache = None
-        h._dm_factor = None
-        h._energy_memo = None
+        engine.hamilton.clear_memos()
 
     def _dm_of_projector(self, p, s_):
         """occ * P as ao_orb2dm(Q, occ) with Q an orthonormal basis of range(P) (Cholesky QR of P . Omega, one small launch:
@@ -119,7 +111,7 @@ class GraphedSCFStep:
         from . import lib
         r = self.nocc[s_]
         w = self.weights[s_]
-        if not (0 < r <= 128 and lib.padded_norb(r) > 0 and self.engine.hamilton._lowrank_density):
+        if not (0 < r <= 128 and lib.padded_norb(r) > 0):
             return p * self.occ[s_]
         y = p @ self.omega[s_]
         q = lib.orth_factor(y, y.transpose(-2, -1) @ y)

@@ -14,6 +14,7 @@ The reference orthogonalises the ERI tensor once (convert4, O(nao^5)); here the 
 and the density / J / K / Vxc matrices are transformed instead (D_ao = X D X^T, J = X^T J_ao X), which is
 algebraically identical.
 """
+from collections import namedtuple
 from typing import List, Optional
 
 import os
@@ -41,6 +42,42 @@ def register_coulomb_side_stream(grid_stream, side_stream):
     else:
         _COULOMB_SIDE[key] = side_stream
 
+
+class _Memo:
+    """values remembered for the last `size` keys, newest first; a key is the identity + in-place version of one or more tensors,
+    never a raw pointer (the caching allocator hands the addresses of freed tensors out again)"""
+
+    def __init__(self, size=1):
+        self.size, self.rows = size, []
+
+    def get(self, *keys):
+        for ks, vs, val in self.rows:
+            if all(a is b for a, b in zip(ks, keys)) and vs == tuple(k._version for k in keys):
+                return val
+        return None
+
+    def put(self, val, *keys):
+        self.rows = [(keys, tuple(k._version for k in keys), val)] + self.rows[:self.size - 1]
+        return val
+
+    def drop(self, val):
+        self.rows = [r for r in self.rows if r[2] is not val]
+
+    def clear(self):
+        self.rows = []
+
+
+class _Factor:
+    """ao_orb2dm's orbitals and weights of a density matrix until its first use checks the weights, then only `pairs`: the padded
+    AO-basis factor pairs (column panels of L = X orb sqrt(w))"""
+    __slots__ = ("orb", "w", "pairs")
+
+    def __init__(self, orb, w, pairs=None):
+        self.orb, self.w, self.pairs = orb, w, pairs
+
+
+# the two-electron energies that fall out of a Fock build (None: not formed by it)
+_Energies = namedtuple("_Energies", "j xc k", defaults=(None, None, None))
 
 
 try:  # inside a DQC installation the class IS a BaseHamilton (isinstance checks of dqc.qccalc / dqc.system pass)
@@ -117,15 +154,20 @@ class HamiltonMI355(_Base):
         self.xc = None
         self.xcfamily = 1
         self._fuse_k = False
-        self._jk_cache = None
-        self._dm_factor = None
-        self._w_checked = None
+        # remembered per density matrix (clear_memos): the J / K pair and the unrestricted pair of the last exchange calls, the
+        # two-electron energies of the last build, and the orbital factors of the last two ao_orb2dm results (the spin-up and
+        # spin-down matrices of an unrestricted iteration); per weight tensor: the last two occupation checks
+        self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors = _Memo(), _Memo(), _Memo(), _Memo(2)
+        self._w_checked = _Memo(2)
         # which density kernel the grid passes took: "factor" (rank-n_occ kernel, D = ao_orb2dm(...) recognised), "dense" (anonymous
         # full matrix: 0.84 instead of 0.50 ms on a 20-atom molecule).  A caller that forms more than two density matrices before
         # using them falls out of the two-entry memo silently otherwise -- read `grid_path_counts` to see it.
         self.grid_path_counts = {"factor": 0, "dense": 0}
-        # DQC_AMD_DENSITY=dense forces the full-matrix density kernel (A/B timing, parity tests)
-        self._lowrank_density = os.environ.get("DQC_AMD_DENSITY", "lr") != "dense"
+
+    def clear_memos(self):
+        """forget what was remembered per density matrix (a graph capture's tensors belong to its private pool)"""
+        for m in (self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors):
+            m.clear()
 
     # ------------------------------------------------------------------ properties
     @property
@@ -256,8 +298,8 @@ class HamiltonMI355(_Base):
             raise RuntimeError("unknown xc family %s" % family)
         if self.is_grid_set and getattr(self, "grid", None) is grid and family == self.xcfamily:
             if xc is not self.xc:  # another functional on the resident AO values: what was remembered of the old one goes
-                self._energy_memo = None
-                self._jk_cache = None
+                self._energy_memo.clear()
+                self._jk_memo.clear()
             self.xc = xc  # same grid, same derivative level: the AO values are already resident
             return
         self.xc = xc
@@ -343,21 +385,13 @@ class HamiltonMI355(_Base):
         """(J, K) in the orthogonalised basis for one (nao,nao) dm; one fused pass over the ERI tiles.
         The reference calls get_elrep(dm) and get_exchange(dm) back to back (dqc/qccalc/hf.py:198-199);
         the pair is memoised on the identity + version of the dm tensor so the tiles are streamed once."""
-        # the cache holds `dm` itself (identity + in-place version), never a raw pointer: the caching
-        # allocator reuses addresses of freed tensors
-        c = self._jk_cache
-        if c is not None and c[0] is dm and c[3] == dm._version and (c[2] is not None or not need_k):
-            return c[1], c[2]
+        c = self._jk_memo.get(dm)
+        if c is not None and (c[1] is not None or not need_k):
+            return c
         dao = self._unconvert_dm(dm)
         with_k = need_k or self._fuse_k
         J, K = self._jk_ao(dao, with_k)
-        J = self._convert2(J)
-        J = (J + J.transpose(-2, -1)) * 0.5
-        if K is not None:
-            K = self._convert2(K)
-            K = (K + K.transpose(-2, -1)) * 0.5
-        self._jk_cache = (dm, J, K, dm._version)
-        return J, K
+        return self._jk_memo.put((self._sym_orth(J), None if K is None else self._sym_orth(K)), dm)
 
     def use_direct_eri(self, on: bool = True):
         """before build(): keep no ERI tile store and re-evaluate the integrals in every Fock build (direct SCF) -- for bases
@@ -404,7 +438,14 @@ class HamiltonMI355(_Base):
     def sharded(self):
         return self._pworld > 1
 
+    @property
+    def tiles_resident(self):
+        """the exact-J/K integrals are the whole ERI tile store, resident on this device (no density fitting, no direct SCF, no store
+        spread over ranks): what the fused build ends and get_elrep_plus_vxc_pol stream"""
+        return self._df is None and not self._direct and self._tile_slice is None
+
     _deferred = None  # a list while a build collects its partial results for ONE all_reduce (_allsum_deferred)
+    _j_stream = None  # the second stream of get_elrep_plus_vxc_pol's Coulomb pass (_coulomb_side)
 
     def _allsum(self, t):
         """sum of the ranks' partial results, in place (no-op for an unsharded Hamiltonian)"""
@@ -477,14 +518,23 @@ class HamiltonMI355(_Base):
             return self._allsum(J), self._allsum(K)
         return lib.jk(self._tiles, dao, self._jkwork, with_k)
 
-    def _fused_fock_ok(self, dm):
-        """the small-matrix ends of this build through the fused kernels of csrc/fock.hip (dqc_fock_prep / dqc_fock_finish)?"""
-        if self._df is not None or self._direct or self._tile_slice is not None or not isinstance(dm, torch.Tensor):
-            return False
-        if dm.dim() != 2 or not dm.is_cuda or dm.dtype != torch.float64 or os.environ.get("DQC_AMD_FUSED_FOCK", "1") == "0":
+    def _fused_build_ok(self, dm):
+        """the small-matrix ends of this build through the fused kernels of csrc/fock.hip (dqc_fock_prep / dqc_fock_finish)?
+        (DQC_AMD_FUSED_FOCK=0: the torch form, which the fused kernels are tested against)"""
+        if not (self.tiles_resident and isinstance(dm, torch.Tensor) and dm.dim() == 2 and dm.is_cuda and dm.dtype == torch.float64):
             return False
         x = self._orthozer
-        return self._nao_ao <= lib.fock_max_nao() and x.is_contiguous() and x.shape[0] == self._nao_ao
+        return (self._nao_ao <= lib.fock_max_nao() and x.is_contiguous() and x.shape[0] == self._nao_ao
+                and os.environ.get("DQC_AMD_FUSED_FOCK", "1") != "0")
+
+    def _fused_factor_ok(self, x, orb, w):
+        """the orbital factor L = X orb sqrt(w) of ao_orb2dm through csrc/fock.hip (dqc_fock_orb2dm / dqc_fock_factor)?  Any other
+        input (another dtype or device, a wide or strided factor) takes the torch form"""
+        return (x is not None and orb.dim() == 2 and w.dim() == 1 and 0 < orb.shape[1] <= 128
+                and orb.is_cuda and orb.dtype == torch.float64 and (orb.shape[1] == 1 or orb.stride(1) == 1)
+                and w.device == orb.device and w.dtype == torch.float64 and w.is_contiguous()
+                and x.device == orb.device and x.is_contiguous() and orb.shape[0] == x.shape[1]
+                and self._nao_ao <= lib.fock_max_nao() and os.environ.get("DQC_AMD_FUSED_FOCK", "1") != "0")
 
     def _sym_orth(self, m_ao):
         m = self._convert2(m_ao)
@@ -502,25 +552,16 @@ class HamiltonMI355(_Base):
         the ERI tiles (dqc_jk_from_tiles_multi); orthogonalised basis in and out."""
         dj = None if dms_j is None else self._unconvert_dm(dms_j)
         dk = None if dms_k is None else self._unconvert_dm(dms_k)
-        if self._direct:  # one pass over the shell quartets per density
-            if j_is_sum_of_k and dj is not None and dk is not None and dj.shape[0] == 1:
-                # unrestricted Hartree-Fock: J[D_u + D_d] = J[D_u] + J[D_d], and a J + K pass yields J of its density anyway:
-                # two passes over the shell quartets instead of three
-                jk = [self._jk_direct(d, True, ("k", i)) for i, d in enumerate(dk)]
-                J = sum(x[0] for x in jk).unsqueeze(0)
-                K = torch.stack([x[1] for x in jk])
-                return self._sym_orth(J), self._sym_orth(K)
-            J = None if dj is None else torch.stack([self._jk_direct(d, False, ("j", i))[0] for i, d in enumerate(dj)])
-            K = None if dk is None else torch.stack([self._jk_direct(d, True, ("k", i))[1] for i, d in enumerate(dk)])
-            return (None if J is None else self._sym_orth(J)), (None if K is None else self._sym_orth(K))
-        if self._tile_slice is not None:  # (the several-densities-per-pass kernel streams the whole store only)
-            if j_is_sum_of_k and dj is not None and dk is not None and dj.shape[0] == 1:
-                jk = [self._jk_ao(d, True) for d in dk]
-                return self._sym_orth(sum(x[0] for x in jk).unsqueeze(0)), self._sym_orth(torch.stack([x[1] for x in jk]))
-            J = None if dj is None else torch.stack([self._jk_ao(d, False)[0] for d in dj])
-            K = None if dk is None else torch.stack([self._jk_ao(d, True)[1] for d in dk])
-            return (None if J is None else self._sym_orth(J)), (None if K is None else self._sym_orth(K))
-        J, K = lib.jk_multi(self._tiles, dj, dk, self._multi_work(0 if dj is None else dj.shape[0], 0 if dk is None else dk.shape[0]))
+        if not self._direct and self._tile_slice is None:
+            J, K = lib.jk_multi(self._tiles, dj, dk, self._multi_work(0 if dj is None else dj.shape[0], 0 if dk is None else dk.shape[0]))
+        elif j_is_sum_of_k and dj is not None and dk is not None and dj.shape[0] == 1:
+            # unrestricted Hartree-Fock: J[D_u + D_d] = J[D_u] + J[D_d], and a J + K pass yields J of its density anyway:
+            # two passes instead of three
+            jk = [self._jk_ao(d, True, ("k", i)) for i, d in enumerate(dk)]
+            J, K = sum(x[0] for x in jk).unsqueeze(0), torch.stack([x[1] for x in jk])
+        else:  # one pass per density over the shell quartets or this rank's slice of the store (the multi kernel streams it whole)
+            J = None if dj is None else torch.stack([self._jk_ao(d, False, ("j", i))[0] for i, d in enumerate(dj)])
+            K = None if dk is None else torch.stack([self._jk_ao(d, True, ("k", i))[1] for i, d in enumerate(dk)])
         return (None if J is None else self._sym_orth(J)), (None if K is None else self._sym_orth(K))
 
     def get_elrep(self, dm):
@@ -558,14 +599,12 @@ class HamiltonMI355(_Base):
         """unrestricted Hartree-Fock: J[D_u + D_d], -K[2 D_u]/2, -K[2 D_d]/2 (hcgto.py:238-241, hf.py:93-103, 198-199) from
         one pass over the tiles; memoised on the identity + version of the two spin matrices so that the reference's call
         sequence get_elrep(dm.u + dm.d), get_exchange(dm) streams the tiles once when routed through here"""
-        c = getattr(self, "_jkpol_cache", None)
-        if c is not None and c[0] is dm.u and c[1] is dm.d and c[2] == (dm.u._version, dm.d._version):
-            return c[3], c[4]
+        c = self._jkpol_memo.get(dm.u, dm.d)
+        if c is not None:
+            return c
         J, K = self._jk_many((dm.u + dm.d).unsqueeze(0), torch.stack([dm.u, dm.d]), j_is_sum_of_k=True)
         # K[2 D] = 2 K[D] and the operator is -K/2: the two factors cancel
-        out = (J[0], (-K[0], -K[1]))
-        self._jkpol_cache = (dm.u, dm.d, (dm.u._version, dm.d._version), out[0], out[1])
-        return out
+        return self._jkpol_memo.put((J[0], (-K[0], -K[1])), dm.u, dm.d)
 
     def get_elrep_exchange_pol(self, dm: SpinParam):
         """(J[D_u + D_d], SpinParam(-K[2 D_u]/2, -K[2 D_d]/2)) as plain tensors in the orthogonalised basis: the three
@@ -611,61 +650,53 @@ class HamiltonMI355(_Base):
     def ao_orb2dm(self, orb, orb_weight):
         """hcgto.py:272-281.  The factor L = orb sqrt(w) of the returned matrix is remembered (keyed on the identity
         + in-place version of the result) so that the grid pass can use the rank-n_occ density kernel."""
-        if (orb.dim() == 2 and orb_weight.dim() == 1 and self._lowrank_density and orb.is_cuda and orb.dtype == torch.float64
-                and (orb.shape[1] == 1 or orb.stride(1) == 1) and orb_weight.is_contiguous() and 0 < orb.shape[1] <= 128 and self._X is not None
-                and self._X.is_contiguous() and orb.shape[0] == self._X.shape[1] and self._nao_ao <= lib.fock_max_nao()
-                and os.environ.get("DQC_AMD_FUSED_FOCK", "1") != "0"):
+        if self._fused_factor_ok(self._X, orb, orb_weight):
             # D and its AO-basis factor L = X C sqrt(w) from ONE launch (csrc/fock.hip) instead of multiply + GEMM here and
             # sqrt + multiply + GEMM + padding copies at the factor's first use; the factor is only USED after the occupations were
             # checked to be >= 0 (_factor_of), as before
             dm, pair = lib.fock_orb2dm(self._X, orb, orb_weight, self._nao_ao, self._ld)
-            self._dm_factor = ([[dm, dm._version, orb, orb_weight, pair]] + (self._dm_factor or []))[:2]
+            self._factors.put(_Factor(orb, orb_weight, [pair]), dm)
             return dm
         orb_w = orb * orb_weight.unsqueeze(-2)
         dm = torch.matmul(orb, orb_w.transpose(-2, -1))
-        if orb.dim() == 2 and self._lowrank_density:
-            # occupations are >= 0 in every SCF caller; a negative weight simply disables the factor path.
-            # Two entries are kept: the spin-up and spin-down matrices of an unrestricted iteration.
-            self._dm_factor = ([[dm, dm._version, orb, orb_weight]] + (self._dm_factor or []))[:2]
+        if orb.dim() == 2:
+            # occupations are >= 0 in every SCF caller; a negative weight simply disables the factor path
+            self._factors.put(_Factor(orb, orb_weight), dm)
         return dm
 
     def _weights_nonneg(self, w):
         """occupations >= 0?  Checked ONCE per weight tensor (identity + version): the check reads the device, and a
         device->host sync in every SCF iteration would drain the launch queue."""
-        for c in self._w_checked or []:
-            if c[0] is w and c[1] == w._version:
-                return c[2]
-        ok = not bool((w < 0).any())
-        self._w_checked = ([(w, w._version, ok)] + (self._w_checked or []))[:2]
-        return ok
+        ok = self._w_checked.get(w)
+        return ok if ok is not None else self._w_checked.put(not bool((w < 0).any()), w)
 
     def _factor_of(self, dm):
         """list of padded AO-basis factor pairs (column panels of L) of `dm` if it came out of ao_orb2dm unmodified, else None"""
-        for c in self._dm_factor or []:
-            if c[0] is dm and c[1] == dm._version:
-                if len(c) >= 4 and not isinstance(c[2], list):  # first use: orthogonal basis -> AO basis (X . orb sqrt(w)), padded for the kernel
-                    orb, w = c[2], c[3]
-                    if not self._weights_nonneg(w):
-                        self._dm_factor.remove(c)
-                        return None
-                    if len(c) == 5:  # (ao_orb2dm's launch has formed the padded pair already)
-                        c[2:] = [[c[4]]]
-                        return c[2]
-                    x = self._orthozer
-                    if (orb.dim() == 2 and w.dim() == 1 and orb.is_cuda and (orb.shape[1] == 1 or orb.stride(1) == 1) and w.is_contiguous() and x.is_contiguous()
-                            and 0 < orb.shape[1] <= 128 and self._nao_ao <= lib.fock_max_nao() and os.environ.get("DQC_AMD_FUSED_FOCK", "1") != "0"):
-                        c[2:] = [[lib.fock_factor(x, orb, w, self._nao_ao, self._ld)]]  # (one launch: csrc/fock.hip)
-                        return c[2]
-                    l_ao = x @ (orb * torch.sqrt(w).unsqueeze(-2))
-                    r = l_ao.shape[-1]
-                    if lib.padded_norb(r) > 0:
-                        c[2:] = [[lib.pad_factor(l_ao, self._ld)]]
-                    else:  # wider than the kernel's widest instantiation: D = sum_p L_p L_p^T over column panels of L
-                        npan = (r + 127) // 128
-                        wid = (r + npan - 1) // npan
-                        c[2:] = [[lib.pad_factor(l_ao[:, i:i + wid].contiguous(), self._ld) for i in range(0, r, wid)]]
-                return c[2]
-        return None
+        f = self._factors.get(dm)
+        if f is None:
+            return None
+        if f.w is not None:  # first use: the occupations checked, the factor formed unless ao_orb2dm's launch has formed it
+            if not self._weights_nonneg(f.w):
+                self._factors.drop(f)
+                return None
+            if f.pairs is None:
+                f.pairs = self._ao_factor(f.orb, f.w)
+            f.orb = f.w = None
+        return f.pairs
+
+    def _ao_factor(self, orb, w):
+        """orthogonal basis -> AO basis (X . orb sqrt(w)), padded for the kernel: the list of factor pairs"""
+        x = self._orthozer
+        if self._fused_factor_ok(x, orb, w):
+            return [lib.fock_factor(x, orb, w, self._nao_ao, self._ld)]  # (one launch: csrc/fock.hip)
+        l_ao = x @ (orb * torch.sqrt(w).unsqueeze(-2))
+        r = l_ao.shape[-1]
+        if lib.padded_norb(r) > 0:
+            return [lib.pad_factor(l_ao, self._ld)]
+        # wider than the kernel's widest instantiation: D = sum_p L_p L_p^T over column panels of L
+        npan = (r + 127) // 128
+        wid = (r + npan - 1) // npan
+        return [lib.pad_factor(l_ao[:, i:i + wid].contiguous(), self._ld) for i in range(0, r, wid)]
 
     def aodm2dens(self, dm, xyz):
         """density at arbitrary points (hcgto.py:283-299): dm (*BD, nao, nao), xyz (*BR, ndim) -> (*BRD), the batch dimensions
@@ -692,13 +723,13 @@ class HamiltonMI355(_Base):
         return self._trdot(self.kinnucl_mat, dm)
 
     def get_e_elrep(self, dm):
-        e = self._memo_energy(dm, 2)
+        e = self._memo_energy(dm, "j")
         if e is not None:
             return e
         return 0.5 * self._trdot(self.get_elrep(dm).fullmatrix(), dm)
 
     def get_e_exchange(self, dm):
-        e = self._memo_energy(dm, 4)
+        e = self._memo_energy(dm, "k")
         if e is not None:
             return e
         exc = self.get_exchange(dm)
@@ -711,7 +742,7 @@ class HamiltonMI355(_Base):
             densinfo = self._dm2densinfo_pol(dm)
             return self._allsum(torch.sum(self.dvolume * self.xc.get_edensityxc(densinfo), dim=-1))
 
-        e = self._memo_energy(dm, 3)
+        e = self._memo_energy(dm, "xc")
         if e is not None:
             return e
 
@@ -736,9 +767,6 @@ class HamiltonMI355(_Base):
         if gga and not self.is_grad_ao_set:
             raise RuntimeError("Please call `setup_grid(grid, gradlevel>=1)` to calculate the density gradient")
         fac = self._factor_of(dm)
-        # meta-GGA: the laplacian of the density is only formed for functionals that may use it (none of the kernel set does:
-        # LibXC objects; a user-supplied BaseXC gets it, as in the reference, through the full-matrix path below)
-        from .xc import LibXC
         # meta-GGA: LibXC objects of the kernel set never read the laplacian of the density (lapl=None); any other BaseXC gets it,
         # as in the reference, from the factor too (cross term by the polarisation identity, see below)
         use_factor = fac is not None and (self.xcfamily != 4 or self.is_lapl_ao_set)
@@ -787,7 +815,7 @@ class HamiltonMI355(_Base):
     def _dm2densinfo_pol(self, dm: SpinParam) -> SpinParam:
         """both spin channels' densities (SpinParam.apply_fcn over _dm2densinfo in the reference, hcgto.py:260-269).  GGA with both
         factors known: ONE pass over the AO matrix for the two spins (dqc_grid_density_lr_pol) instead of one per spin"""
-        if self.xcfamily == 2 and self.is_ao_set and self.is_grad_ao_set and os.environ.get("DQC_AMD_POL_DENSITY", "fused") != "split":
+        if self.xcfamily == 2 and self.is_ao_set and self.is_grad_ao_set:
             fu, fd = self._factor_of(dm.u), self._factor_of(dm.d)
             if fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1:
                 out = lib.grid_density_lr_pol(self._ao, self._nao_ao, fu[0], fd[0])
@@ -799,9 +827,7 @@ class HamiltonMI355(_Base):
         return SpinParam(u=self._dm2densinfo(dm.u), d=self._dm2densinfo(dm.d))
 
     def _get_vxc_from_potinfo(self, potinfo: ValGrad):
-        vm = self._vxc_ao_from_potinfo(potinfo)
-        mat = self._convert2(vm[:self._nao_ao, :self._nao_ao])
-        return (mat + mat.transpose(-2, -1)) * 0.5
+        return self._sym_orth(self._vxc_ao_from_potinfo(potinfo)[:self._nao_ao, :self._nao_ao])
 
     def _vxc_ao_from_potinfo(self, potinfo: ValGrad):
         """(ld, ld) AO-basis Vxc matrix (hcgto.py:445-489 before the conversion to the orthogonal basis)"""
@@ -819,88 +845,132 @@ class HamiltonMI355(_Base):
             vm = vm + lib.grid_vxc_pair(g3, g3, self._nao_ao, self.dvolume.repeat(3), lk.repeat(3), what="dqc_grid_vxc_pair[three gradient components]")
         return self._allsum(vm)
 
+    def _coulomb_side(self, dev, own=False):
+        """the stream a build's Coulomb pass over the tile store runs on beside its grid pass, or None (in line, on this stream): the
+        one registered for this (device, current stream) by register_coulomb_side_stream, else, with `own`, a second stream of this
+        Hamiltonian's.  In line inside a graph capture and when the store is not resident whole"""
+        if not (own or _COULOMB_SIDE) or not self.tiles_resident or dev.type != "cuda" or torch.cuda.is_current_stream_capturing():
+            return None
+        side = _COULOMB_SIDE.get((dev.index, torch.cuda.current_stream(dev).cuda_stream))
+        if side is None and own:
+            if self._j_stream is None:
+                self._j_stream = torch.cuda.Stream(device=dev)
+            side = self._j_stream
+        return side
+
+    @staticmethod
+    def _beside(side, fn, *reads):
+        """fn() enqueued on `side` behind what this stream has queued so far (`reads`: tensors of this stream that it reads); on this
+        stream when `side` is None"""
+        if side is None:
+            return fn()
+        side.wait_stream(torch.cuda.current_stream(side.device))
+        for t in reads:
+            t.record_stream(side)
+        with torch.cuda.stream(side):
+            return fn()
+
+    @staticmethod
+    def _rejoin(side, out=None):
+        """this stream waits for what _beside enqueued on `side`; `out` was allocated there and is read and later freed here"""
+        if side is not None:
+            main = torch.cuda.current_stream(side.device)
+            main.wait_stream(side)
+            if out is not None:
+                out.record_stream(main)
+
+    def _prep(self, work, dm, fac, with_k):
+        """dqc_fock_prep: the symmetric AO density into `work`, its accumulators zeroed -- L L^T when the orbital factor `fac` is one
+        panel, else X D X^T"""
+        if fac is not None and len(fac) == 1 and fac[0][0].is_contiguous():
+            lib.fock_prep(work, self._orthozer, self._nao_ao, with_k, orb=fac[0][0])
+        else:
+            lib.fock_prep(work, self._orthozer, self._nao_ao, with_k, dm=dm.contiguous())
+
+    def _vxc_exc(self, densinfo):
+        """(potentials, E_xc as a (1,) tensor or None): both from one pass over the grid where the functional has that pass"""
+        if not hasattr(self.xc, "get_vxc_and_exc"):
+            return self.xc.get_vxc(densinfo), None
+        potinfo, exc = self.xc.get_vxc_and_exc(densinfo, self.dvolume)
+        # (exc[:1]: the result, the rest of the buffer is the kernel's per-block scratch; sharded: the quadrature of this rank's slab)
+        return potinfo, None if exc is None else self._allsum(exc[:1])
+
     def get_elrep_plus_vxc(self, dm, core=None):
         """J[D] + Vxc[D] of ONE restricted density matrix as a plain tensor in the orthogonalised basis -- the sum
         `_KSEngine.__dm2fock` forms (ks.py:176-187) -- with a single AO -> orthogonal conversion X^T (J_ao + V_ao) X instead
         of one per operator.  Same numbers as get_elrep(dm) + get_vxc(dm) up to round-off."""
+        return self._elrep_plus_vxc(dm, core, lambda: None)
+
+    def _elrep_plus_vxc(self, dm, core, mark):
+        """get_elrep_plus_vxc with mark() called between its six stages (timed_fock_kernels).  The small-matrix ends go through the
+        fused kernels of csrc/fock.hip unless the Coulomb pass has a side stream to run on"""
         assert self.xc is not None and dm.dim() == 2
         fac = self._factor_of(dm)
-        if self._fused_fock_ok(dm) and not (_COULOMB_SIDE and not torch.cuda.is_current_stream_capturing()):
-            return self._elrep_plus_vxc_fused(dm, fac, core)
+        side = self._coulomb_side(dm.device)
+        if side is None and self._fused_build_ok(dm):
+            return self._elrep_plus_vxc_fused(dm, fac, core, mark)
+        n = self._nao_ao
+        mark()
         if fac is not None and len(fac) == 1:  # D_ao = L_ao L_ao^T: one thin GEMM instead of X D X^T
-            n = self._nao_ao
             dao = (fac[0][0] @ fac[0][1])[:n, :n].contiguous()
         else:
             dao = self._unconvert_dm(dm)
+        mark()
         if self._tile_slice is not None:  # tile store spread over the ranks: J, Vxc and E_xc parts travel in one all_reduce
             self._deferred = []
-        side = main = None
-        if _COULOMB_SIDE and dm.is_cuda and self._df is None and not self._direct and self._tile_slice is None \
-                and not torch.cuda.is_current_stream_capturing():
-            main = torch.cuda.current_stream(dm.device)
-            side = _COULOMB_SIDE.get((dm.device.index, main.cuda_stream))
         try:
-            if side is not None:  # the tile stream on its own compute units, beside this molecule's grid pass
-                side.wait_stream(main)
-                dao.record_stream(side)
-                with torch.cuda.stream(side):
-                    jao, _ = self._jk_ao(dao, False)
-            elif self._df is not None:
+            if self._df is not None:
                 jao = self._df.coulomb_ao(dao)
-            else:
-                jao, _ = self._jk_ao(dao, False)
+            else:  # (on a side stream: the tile stream on its own compute units, beside this molecule's grid pass)
+                jao = self._beside(side, lambda: self._jk_ao(dao, False)[0], dao)
+            mark()
             densinfo = self._dm2densinfo(dm)
-            if hasattr(self.xc, "get_vxc_and_exc"):  # potentials and the E_xc quadrature from one pass over the grid
-                potinfo, exc = self.xc.get_vxc_and_exc(densinfo, self.dvolume)
-                if exc is not None:
-                    exc = exc[:1]  # (the result; the rest of the buffer is the kernel's per-block scratch)
-                    self._allsum(exc)  # (sharded: the quadrature of this rank's slab)
-            else:
-                potinfo, exc = self.xc.get_vxc(densinfo), None
+            mark()
+            potinfo, exc = self._vxc_exc(densinfo)
+            mark()
             vm = self._vxc_ao_from_potinfo(potinfo)
-            if side is not None:
-                main.wait_stream(side)
-                jao.record_stream(main)  # (allocated on the side stream, read and later freed on this one)
+            self._rejoin(side, jao)
             if self._deferred is not None:
                 self._allsum_flush()
         finally:
             self._deferred = None  # (an exception in between must not leave later _allsum calls queued for ever)
+        mark()
         # the two-electron energies of THIS density fall out of the build (tr D J = tr D_ao J_ao): remembered under the
         # identity + version of `dm`, so that dm2energy(dm) right after dm2scp(dm) streams neither the tiles nor the grid again
-        e_j = 0.5 * (dao * jao).sum()
-        self._energy_memo = (dm, dm._version, e_j, None if exc is None else exc[0])
-        mat = self._convert2(jao + vm[:self._nao_ao, :self._nao_ao])
-        mat = (mat + mat.transpose(-2, -1)) * 0.5
-        return mat if core is None else core + mat
+        self._energy_memo.put(_Energies(j=0.5 * (dao * jao).sum(), xc=None if exc is None else exc[0]), dm)
+        mat = self._sym_orth(jao + vm[:n, :n])
+        mat = mat if core is None else core + mat
+        mark()
+        return mat
 
-    def _elrep_plus_vxc_fused(self, dm, fac, core=None):
+    def _elrep_plus_vxc_fused(self, dm, fac, core, mark):
         """get_elrep_plus_vxc with the small-matrix ends fused (csrc/fock.hip): AO density (from the orbital factor when it is known,
         else X D X^T) + zeroed accumulators in ONE launch, the tile pass, the grid pass, then J's symmetrisation, tr D J / 2,
         X^T (J + V_ao) X and its symmetrisation in ONE launch"""
         n, x, work = self._nao_ao, self._orthozer, self._jkwork
         tiles = self._tiles
-        if fac is not None and len(fac) == 1 and fac[0][0].is_contiguous():
-            lib.fock_prep(work, x, n, False, orb=fac[0][0])
-        else:
-            lib.fock_prep(work, x, n, False, dm=dm.contiguous())
+        mark()
+        self._prep(work, dm, fac, False)
+        mark()
         lib.jk_stream_prepared(tiles, n, work, False)
+        mark()
         densinfo = self._dm2densinfo(dm)
-        if hasattr(self.xc, "get_vxc_and_exc"):
-            potinfo, exc = self.xc.get_vxc_and_exc(densinfo, self.dvolume)
-            if exc is not None:
-                exc = exc[:1]
-        else:
-            potinfo, exc = self.xc.get_vxc(densinfo), None
-        if self.xcfamily != 4 and self._pworld == 1:
+        mark()
+        potinfo, exc = self._vxc_exc(densinfo)
+        mark()
+        if self.xcfamily != 4:
             # LDA / GGA: the Vxc kernel's raw cross-block sums go straight into the finish (their symmetrisation is part of its
             # combine kernel: one launch less)
             vg = potinfo.grad if self.xcfamily == 2 else None
             vraw, vsc = lib.grid_vxc_raw(self._ao, n, self.dvolume, potinfo.value.contiguous(), None if vg is None else vg.contiguous())
+            mark()
             mat, en = lib.fock_finish_vraw(work, x, n, vraw, vsc, core=core)
         else:
             vm = self._vxc_ao_from_potinfo(potinfo)
+            mark()
             mat, en, _ = lib.fock_finish(work, x, n, False, vxc_ao=vm, core=core)  # (core: the one-electron part, added in the same launch)
-        self._energy_memo = (dm, dm._version, en[0], None if exc is None else exc[0])
+        mark()
+        self._energy_memo.put(_Energies(j=en[0], xc=None if exc is None else exc[0]), dm)
         return mat
 
     def get_elrep_plus_vxc_pol(self, dm: SpinParam, core=None):
@@ -908,79 +978,43 @@ class HamiltonMI355(_Base):
         orthogonalised basis -- the sums the polarised `_KSEngine.__dm2fock` forms (ks.py:176-187, hf.py:93-103) -- with ONE batched
         AO -> orthogonal conversion X^T (J_ao + V_s,ao) X of the two sums instead of one per operator (three), the AO-basis total
         density from the two orbital factors when they are known, and the Coulomb stream over the tile store (HBM-bound) enqueued on
-        a second stream BESIDE the two-spin grid pass (its Vxc products are bound by the matrix cores; DQC_AMD_J_OVERLAP=0 or a
-        graph capture: one stream).  Same numbers as get_elrep(dm.u + dm.d) + get_vxc(dm) up to round-off."""
-        assert self.xc is not None and dm.u.dim() == 2 and self._df is None and not self._direct and self._tile_slice is None
-        n = self._nao_ao
+        a second stream BESIDE the two-spin grid pass (its Vxc products are bound by the matrix cores; a graph capture: one stream).
+        With both factors known the ends are fused (csrc/fock.hip): L L^T of the stacked factor [L_u | L_d] in one launch, then per
+        spin M_s = J + V_s, X^T M_s X, the symmetrisation and the core Hamiltonian in one launch each.  Needs `tiles_resident`.
+        Same numbers as get_elrep(dm.u + dm.d) + get_vxc(dm) up to round-off."""
+        assert self.xc is not None and dm.u.dim() == 2 and self.tiles_resident
+        n, x = self._nao_ao, self._orthozer
         fu, fd = self._factor_of(dm.u), self._factor_of(dm.d)
-        if (self._fused_fock_ok(dm.u) and fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1
-                and not (_COULOMB_SIDE and not torch.cuda.is_current_stream_capturing())):
-            return self._elrep_plus_vxc_pol_fused(dm, fu[0], fd[0], core)
-
-        def coulomb():  # (the AO-basis total density and its Coulomb matrix: nothing the grid pass waits for)
-            if fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1:
-                dao = (fu[0][0] @ fu[0][1] + fd[0][0] @ fd[0][1])[:n, :n].contiguous()
-            else:
-                dao = self._unconvert_dm(dm.u + dm.d)
-            return self._jk_ao(dao, False)[0]
-
-        side = None
-        if dm.u.is_cuda and os.environ.get("DQC_AMD_J_OVERLAP", "1") != "0" and not torch.cuda.is_current_stream_capturing():
-            side = getattr(self, "_j_stream", None)
-            if side is None:
-                side = self._j_stream = torch.cuda.Stream(device=dm.u.device)
-        if side is not None:
-            main = torch.cuda.current_stream(dm.u.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                jao = coulomb()
+        one = fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1
+        side = self._coulomb_side(dm.u.device, own=True)
+        # (a side stream registered for this stream takes the torch form, as in the restricted build)
+        fused = one and (side is None or side is self._j_stream) and self._fused_build_ok(dm.u)
+        if fused:
+            work, tiles = self._jkwork, self._tiles
+            self._prep(work, None, [(torch.cat([fu[0][0], fd[0][0]], dim=1),)], False)
+            self._beside(side, lambda: lib.jk_stream_prepared(tiles, n, work, False))
         else:
-            jao = coulomb()
-        potinfo = self.xc.get_vxc(self._dm2densinfo_pol(dm))
-        vu = self._vxc_ao_from_potinfo(potinfo.u)[:n, :n]
-        vd = self._vxc_ao_from_potinfo(potinfo.d)[:n, :n]
-        if side is not None:
-            main.wait_stream(side)
-            jao.record_stream(main)  # (allocated on the side stream, read and later freed on this one)
-        x = self._orthozer
-        mat = x.transpose(-2, -1) @ torch.stack([jao + vu, jao + vd]) @ x
-        mat = (mat + mat.transpose(-2, -1)) * 0.5
-        return mat if core is None else core + mat
+            def coulomb():  # (the AO-basis total density and its Coulomb matrix: nothing the grid pass waits for)
+                if one:
+                    return self._jk_ao((fu[0][0] @ fu[0][1] + fd[0][0] @ fd[0][1])[:n, :n].contiguous(), False)[0]
+                return self._jk_ao(self._unconvert_dm(dm.u + dm.d), False)[0]
 
-    def _elrep_plus_vxc_pol_fused(self, dm, fu, fd, core=None):
-        """get_elrep_plus_vxc_pol through the fused build ends (csrc/fock.hip): the total AO density L L^T of the stacked factor
-        [L_u | L_d] in one launch, the Coulomb stream beside the two-spin grid pass (second stream, as in the torch form), then per
-        spin M_s = J + V_s, X^T M_s X, the symmetrisation and the core Hamiltonian in three launches"""
-        n, x, work = self._nao_ao, self._orthozer, self._jkwork
-        tiles = self._tiles
-        lib.fock_prep(work, x, n, False, orb=torch.cat([fu[0], fd[0]], dim=1))
-        side = None
-        if dm.u.is_cuda and os.environ.get("DQC_AMD_J_OVERLAP", "1") != "0" and not torch.cuda.is_current_stream_capturing():
-            side = getattr(self, "_j_stream", None)
-            if side is None:
-                side = self._j_stream = torch.cuda.Stream(device=dm.u.device)
-        if side is not None:
-            main = torch.cuda.current_stream(dm.u.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                lib.jk_stream_prepared(tiles, n, work, False)
-        else:
-            lib.jk_stream_prepared(tiles, n, work, False)
+            jao = self._beside(side, coulomb)
         potinfo = self.xc.get_vxc(self._dm2densinfo_pol(dm))
         vu = self._vxc_ao_from_potinfo(potinfo.u)
         vd = self._vxc_ao_from_potinfo(potinfo.d)
-        if side is not None:
-            main.wait_stream(side)
-        # (the two finishes share the scratch regions of the work buffer: stream order keeps them apart)
-        f_u, _, _ = lib.fock_finish(work, x, n, False, vxc_ao=vu, core=core)
-        f_d, _, _ = lib.fock_finish(work, x, n, False, vxc_ao=vd, core=core)
-        return torch.stack([f_u, f_d])
+        self._rejoin(side, None if fused else jao)
+        if fused:  # (the two finishes share the scratch regions of the work buffer: stream order keeps them apart)
+            return torch.stack([lib.fock_finish(work, x, n, False, vxc_ao=v, core=core)[0] for v in (vu, vd)])
+        mat = x.transpose(-2, -1) @ torch.stack([jao + vu[:n, :n], jao + vd[:n, :n]]) @ x
+        mat = (mat + mat.transpose(-2, -1)) * 0.5
+        return mat if core is None else core + mat
 
-    def _memo_energy(self, dm, k):
-        c = getattr(self, "_energy_memo", None)
-        if c is not None and isinstance(dm, torch.Tensor) and c[0] is dm and c[1] == dm._version and k < len(c):
-            return c[k]
-        return None
+    def _memo_energy(self, dm, field):
+        """E_J, E_xc or E_K (`field` "j", "xc", "k", or 2, 3, 4 as callers of the positional memo name them) of `dm` when the last
+        build formed it, else None"""
+        e = self._energy_memo.get(dm)
+        return None if e is None else getattr(e, {2: "j", 3: "xc", 4: "k"}.get(field, field))
 
     def get_elrep_plus_exchange(self, dm, core=None):
         """J[D] - K[D] / 2 of ONE restricted density matrix as a plain tensor in the orthogonalised basis -- the sum a restricted
@@ -990,91 +1024,33 @@ class HamiltonMI355(_Base):
         if self._df is not None:  # hcgto.py:229-230
             raise RuntimeError("Exact exchange cannot be computed with density fitting")
         assert dm.dim() == 2
-        if self._fused_fock_ok(dm):
-            # D_ao = X D X^T + zeroed accumulators, the tile pass, then symmetrised J / K, the two traces and X^T (J - K / 2) X: three
+        if self._fused_build_ok(dm):
+            # D_ao + zeroed accumulators, the tile pass, then symmetrised J / K, the two traces and X^T (J - K / 2) X: three
             # launches (csrc/fock.hip) instead of sixteen
-            n, x, work = self._nao_ao, self._orthozer, self._jkwork
-            tiles = self._tiles
-            fac = self._factor_of(dm)
-            if fac is not None and len(fac) == 1 and fac[0][0].is_contiguous():  # D_ao = L L^T from the orbital factor (dqc_fock_factor)
-                lib.fock_prep(work, x, n, True, orb=fac[0][0])
-            else:
-                lib.fock_prep(work, x, n, True, dm=dm.contiguous())
+            n, work, tiles = self._nao_ao, self._jkwork, self._tiles
+            self._prep(work, dm, self._factor_of(dm), True)
             lib.jk_stream_prepared(tiles, n, work, True)
-            mat, en, _ = lib.fock_finish(work, x, n, True, core=core)
-            self._energy_memo = (dm, dm._version, en[0], None, en[1])
+            mat, en, _ = lib.fock_finish(work, self._orthozer, n, True, core=core)
+            self._energy_memo.put(_Energies(j=en[0], k=en[1]), dm)
             return mat
         dao = self._unconvert_dm(dm)
         J, K = self._jk_ao(dao, True)
         # the two-electron energies of THIS density fall out of the build: remembered like get_elrep_plus_vxc's
-        self._energy_memo = (dm, dm._version, 0.5 * (dao * J).sum(), None, -0.25 * (dao * K).sum())
-        mat = self._convert2(J - 0.5 * K)
-        mat = (mat + mat.transpose(-2, -1)) * 0.5
+        self._energy_memo.put(_Energies(j=0.5 * (dao * J).sum(), k=-0.25 * (dao * K).sum()), dm)
+        mat = self._sym_orth(J - 0.5 * K)
         return mat if core is None else core + mat
 
     def timed_fock_kernels(self, dm, core):
-        """measurement aid (bench.py): the restricted KS Fock build `core + get_elrep_plus_vxc(dm)` unrolled -- the same
-        library calls in the same order -- with a HIP event on the launch stream between its kernels.
-        Returns (names, events) with len(events) == len(names) + 1."""
-        assert self.xc is not None and dm.dim() == 2 and self.xcfamily == 2
-        n = self._nao_ao
-        fac = self._factor_of(dm)
+        """measurement aid (bench.py): the restricted KS Fock build `core + get_elrep_plus_vxc(dm)` -- its own body, on this stream --
+        with a HIP event on the launch stream between its stages.  Returns (names, events) with len(events) == len(names) + 1."""
         ev = []
 
         def mark():
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(torch.cuda.current_stream(self.device))
-            ev.append(e)
+            ev.append(torch.cuda.Event(enable_timing=True))
+            ev[-1].record(torch.cuda.current_stream(self.device))
 
-        if self._fused_fock_ok(dm):  # the calls of _elrep_plus_vxc_fused, in its order
-            x, work, tiles = self._orthozer, self._jkwork, self._tiles
-            mark()
-            if fac is not None and len(fac) == 1 and fac[0][0].is_contiguous():
-                lib.fock_prep(work, x, n, False, orb=fac[0][0])
-            else:
-                lib.fock_prep(work, x, n, False, dm=dm.contiguous())
-            mark()
-            lib.jk_stream_prepared(tiles, n, work, False)
-            mark()
-            if fac is not None and len(fac) == 1:
-                rho, grho = lib.grid_density_lr(self._ao, n, fac[0], True)
-            else:
-                dmdmt = (dm + dm.transpose(-2, -1)) * 0.5
-                rho, grho = lib.grid_density(self._ao, n, lib.pad_matrix(self._unconvert_dm(dmdmt), self._ld), True)
-            mark()
-            _, v, vg = lib.xc_eval(self.xc.terms, rho, grho, want_e=False, want_v=True)
-            mark()
-            vraw, vsc = lib.grid_vxc_raw(self._ao, n, self.dvolume, v, vg)
-            mark()
-            fock, _ = lib.fock_finish_vraw(work, x, n, vraw, vsc, core=core.contiguous())  # noqa: F841
-            mark()
-            return ["orth_transforms", "jk_tiles", "grid_density", "xc_eval", "grid_vxc", "fock_assemble"], ev
-        dao_n = self._unconvert_dm((dm + dm.transpose(-2, -1)) * 0.5).contiguous()
-
-        mark()
-        if self._df is None:
-            jao, _ = self._jk_ao(dao_n, False)
-        else:
-            jao = lib.df_coulomb(self._df.j3c, self._df._inv_j2c, dao_n, self._df._work)
-        mark()
-        dao = lib.pad_matrix(dao_n, self._ld)
-        mark()
-        names = ["jk_tiles", "orth_transforms"]
-        if fac is not None and len(fac) == 1:
-            rho, grho = lib.grid_density_lr(self._ao, n, fac[0], True)
-        else:
-            rho, grho = lib.grid_density(self._ao, n, dao, True)
-        mark()
-        _, v, vg = lib.xc_eval(self.xc.terms, rho, grho, want_e=False, want_v=True)
-        mark()
-        vm = lib.grid_vxc(self._ao, n, self.dvolume, v, vg)
-        mark()
-        names += ["grid_density", "xc_eval", "grid_vxc"]
-        mat = self._convert2(jao + vm[:n, :n])
-        fock = core + (mat + mat.transpose(-2, -1)) * 0.5  # noqa: F841
-        mark()
-        names.append("fock_assemble")
-        return names, ev
+        self._elrep_plus_vxc(dm, core.contiguous(), mark)
+        return ["orth_transforms", "jk_tiles", "grid_density", "xc_eval", "grid_vxc", "fock_assemble"], ev
 
     def getparamnames(self, methodname: str, prefix: str = "") -> List[str]:
         table = {

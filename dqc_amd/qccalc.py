@@ -91,8 +91,7 @@ class _Engine:
                 J, kx = h.get_elrep_exchange_pol(dm)
                 core = self.knvext.fullmatrix() + J
                 return torch.stack([core + kx.u, core + kx.d])
-            if (self.is_ks and dm.u.dim() == 2 and h.df is None and hasattr(h, "get_elrep_plus_vxc_pol") and not getattr(h, "_direct", False)
-                    and not getattr(h, "sharded", False) and getattr(h, "_tile_slice", None) is None):
+            if self.is_ks and dm.u.dim() == 2 and hasattr(h, "get_elrep_plus_vxc_pol") and h.tiles_resident:
                 # J + Vxc_s with one batched AO -> orthogonal conversion, the Coulomb stream beside the grid pass (hamilton.py)
                 return h.get_elrep_plus_vxc_pol(dm, core=self._core_matrix())
             core = self.knvext + h.get_elrep(dm.u + dm.d)
