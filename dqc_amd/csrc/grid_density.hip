@@ -100,11 +100,12 @@ DQC_DEV void rowdot_epilogue(const v4d (&acc)[NCT], double (&p)[4][GGA ? 4 : 1],
 // 0.564 ms (tools/gpu_den_time.py; the staged panel gets an odd row stride so that the permuted ds_read_b64 pattern stays
 // conflict-free).  Tried instead: trading accumulators between neighbouring lanes with DPP swaps so that the LDS layout stays
 // plain -- 0.572 ms.
-template <int NCT, bool GGA, int Q0 = 0>
+template <int NCT, bool GGA, int Q0 = 0, int DP = 2>
 DQC_DEV void rowdot_epilogue_paired(const v4d (&acc)[NCT], double (&p)[4][GGA ? 4 : 1], const double *__restrict__ blk0,
                                     const double *__restrict__ blkg, size_t cs, const int (&roff)[4], int lr, int col0) {
-    // roff[r] = row * ld + 2 lr (the lane's first column of a tile pair).  A batch = the NP double2 loads (+ the odd tile) of one (row, component); two batches in flight
-    constexpr int NQ = (GGA ? 4 : 1) - Q0, NB = 4 * NQ, NP = NCT / 2, ODD = NCT & 1, DP = 2;
+    // roff[r] = row * ld + 2 lr (the lane's first column of a tile pair).  A batch = the NP double2 loads (+ the odd tile) of one
+    // (row, component); DP batches in flight (two in the one-role kernels; the role-B waves of density_roles_kernel hold more)
+    constexpr int NQ = (GGA ? 4 : 1) - Q0, NB = 4 * NQ, NP = NCT / 2, ODD = NCT & 1;
     if (NB == 0) return;
     double2 t2[DP][NP > 0 ? NP : 1];
     double t1[DP];
@@ -115,10 +116,11 @@ DQC_DEV void rowdot_epilogue_paired(const v4d (&acc)[NCT], double (&p)[4][GGA ? 
         for (int m = 0; m < NP; m++) d2[m] = *reinterpret_cast<const double2 *>(base + roff[r] + m * 32);
         if (ODD) d1 = base[(roff[r] - lr) + (NCT - 1) * 16];
     };
-    issue(0, t2[0], t1[0]);
+#pragma unroll
+    for (int b0 = 0; b0 < DP - 1 && b0 < NB; b0++) issue(b0, t2[b0], t1[b0]);
 #pragma unroll
     for (int bt = 0; bt < NB; bt++) {
-        if (bt + 1 < NB) issue(bt + 1, t2[(bt + 1) % DP], t1[(bt + 1) % DP]);
+        if (bt + DP - 1 < NB) issue(bt + DP - 1, t2[(bt + DP - 1) % DP], t1[(bt + DP - 1) % DP]);
         const int r = bt / NQ, q = bt % NQ + Q0;
 #pragma unroll
         for (int m = 0; m < NP; m++) p[r][q] += acc[2 * m][r] * t2[bt % DP][m].x + acc[2 * m + 1][r] * t2[bt % DP][m].y;
@@ -663,6 +665,270 @@ static int launch_density_lr_n(int nct, dim3 grid, hipStream_t st, double *rho, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The factor-form GGA density with the waves of a block split into two ROLES (round 7; DESIGN.md 3, docs/LOG_r07.md).
+// density_lr_kernel's blocks march through phase 1 / phase 2 / epilogue in chip-wide lock step: HBM idles while they are in phase
+// 2 and the matrix pipe idles while they are in the epilogue.  Here ONE persistent block of 8 waves per CU walks the 64-point
+// tiles; waves 0..3 (role A) run the matrix phases of a tile, waves 4..7 (role B) the row-dot epilogue of the tile before it, so
+// every SIMD always carries one MFMA-issuing and one streaming wave.  A-wave w and B-wave w own the same 16 points of a tile and
+// hand over through a mailbox in LDS; no block-wide barrier after the set-up.
+//   * L^T (RP x 16 NT) stays RESIDENT in LDS for the life of the block (odd row stride: the permuted phase-2 fragment reads are
+//     conflict-free) and is the operand of BOTH GEMMs -- phase 1's A fragment L[ao][r] is element [r][ao] of it --, so the A
+//     waves need no shared staging and no barrier among themselves.  The Phi operand goes through a wave-private LDS chunk.
+//   * same MFMA order per accumulator and the same fragments as density_lr_kernel<NRT, NT>: a1 and acc hold the same bits.
+//   * the B = (Phi L) L^T accumulators cross in two passes of <= P0 column tiles, written as the register image (lane-contiguous
+//     16-byte stores; the B wave reads the same image back, so lane (lr, lk) again holds B[pt = lk + 4 reg][col of tile ct]).
+//     The B wave copies a pass into registers at once and frees the mailbox, then runs rowdot_epilogue_paired over all NT tiles
+//     in density_lr_kernel's order: the gradient comes out bit-identical.
+//   * hand-off: two monotone counters per wave pair (filled / drained), release / acquire at workgroup scope.  The waits are
+//     bounded (ROLE_SPIN_CAP polls, counted while the wave runs, so a context switch does not eat them); a wave that gives up
+//     marks the block broken, every later wait falls through and the B waves store NaN: a protocol slip is a loud parity failure
+//     and never a hang.
+// LDS: 8 (RP (16 NT + 1) + 4 P0 256 + 4 2 16 DEN_SA) + 64 bytes = 156 096 for NRT 3, NT 13; one block per CU, 2 waves per SIMD.
+// ---------------------------------------------------------------------------------------------
+constexpr int ROLE_NT = 512;                 // threads: 4 role-A + 4 role-B waves
+constexpr unsigned ROLE_SPIN_CAP = 1u << 22; // polls of one hand-off wait (a wait lasts a few hundred at most)
+constexpr int ROLE_DP = 3;                   // epilogue batches a B wave keeps in flight
+
+template <int NRT, int NT>
+struct RoleGeom {
+    static constexpr int RP = NRT * 16;
+    static constexpr int S = NT * 16 + 1;    // row stride of the resident L^T
+    static constexpr int P0 = (NT + 1) / 2;  // column tiles of the first hand-off pass
+    static constexpr int P1 = NT - P0;
+    static constexpr int LT_SZ = (RP * S + 1) & ~1;  // doubles; keeps the mailbox 16-byte aligned
+    static constexpr int MB_W = P0 * 256;            // mailbox doubles per wave pair
+    static constexpr int SA_W = 2 * 16 * DEN_SA;     // Phi chunk doubles per A wave (two buffers)
+    static constexpr size_t lds_bytes() { return sizeof(double) * (LT_SZ + 4 * MB_W + 4 * SA_W) + 64; }
+};
+
+// the lane's column within the resident L^T row for accumulator tile ct (the permutation of rowdot_epilogue_paired)
+template <int NT>
+DQC_DEV int role_col(int ct, int lr) {
+    return ct < 2 * (NT / 2) ? 32 * (ct >> 1) + 2 * lr + (ct & 1) : ct * 16 + lr;
+}
+
+DQC_DEV void role_wait(unsigned *flag, unsigned want, unsigned *broken) {
+    unsigned n = 0;
+    while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
+        if (__hip_atomic_load(broken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) break;
+        if (++n > ROLE_SPIN_CAP) {
+            __hip_atomic_store(broken, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(2);
+    }
+}
+
+DQC_DEV void role_signal(unsigned *flag, unsigned v) {
+    __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);  // (every lane stores the same value)
+}
+
+template <int NRT, int NT>
+__global__ __launch_bounds__(ROLE_NT, 1) void density_roles_kernel(double *__restrict__ rho, double *__restrict__ grho,
+                                                                   const double *__restrict__ ao, int ngrid,
+                                                                   const double *__restrict__ orbt, int lda) {
+    using G = RoleGeom<NRT, NT>;
+    constexpr int RP = G::RP, S = G::S, P0 = G::P0, P1 = G::P1, LD = NT * 16;
+    constexpr int NPF = 4;  // Phi chunks an A wave requests ahead (4 VGPRs each)
+    static_assert(NT >= 2 && NT <= 14 && P1 >= 1, "one epilogue panel of 2..14 tiles");
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *sLT = lds, *sMB = lds + G::LT_SZ, *sAall = sMB + 4 * G::MB_W;
+    unsigned *flags = reinterpret_cast<unsigned *>(sAall + 4 * G::SA_W);  // [0..3] filled, [4..7] drained, [8] broken
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 15, lk = lane >> 4;
+    const int ntiles = (ngrid + DEN_BM - 1) / DEN_BM;
+    const size_t cs = (size_t)ngrid * lda;
+
+    for (int e = tid; e < RP * LD; e += ROLE_NT) {  // orbt is (RP x LD) row-major, zero padded
+        const int r = e / LD, c = e - r * LD;
+        sLT[r * S + c] = orbt[e];
+    }
+    if (tid < 16) flags[tid] = 0u;
+    __syncthreads();  // the only block-wide barrier
+    const int w = wave & 3;
+    unsigned *filled = flags + w, *drained = flags + 4 + w, *broken = flags + 8;
+    double *mb = sMB + w * G::MB_W + lane * 2;
+    unsigned seq = 0;  // hand-off passes of this wave pair so far (two per tile)
+
+    if (wave < 4) {
+        // ================= role A: phase 1, rho, phase 2 in two column passes =================
+        double *sA = sAall + w * G::SA_W;
+        const int arow = lane >> 2, aseg = (lane & 3) * 4;
+        // scalars and macros, not arrays and lambdas: register sets that live across the tile loop's back-edge end up in scratch
+        double2 pa0a, pa0b, pa1a, pa1b, pa2a, pa2b, pa3a, pa3b;
+        static_assert(NPF == 4, "four named prefetch sets");
+#define DQC_ROLE_REQUEST(T, KC, SET)                                                                       \
+    {   /* chunk KC of tile T: 16 rows x 128 bytes */                                                      \
+        const int rmax_ = ngrid - 1 - (T) * DEN_BM;                                                        \
+        const double *s_ = ao + (size_t)(T) * DEN_BM * lda + (min(w * 16 + arow, rmax_) * lda + aseg) + (KC) * DEN_KC; \
+        pa##SET##a = *reinterpret_cast<const double2 *>(s_);                                               \
+        pa##SET##b = *reinterpret_cast<const double2 *>(s_ + 2);                                           \
+    }
+#define DQC_ROLE_STEP(KC, SET)                                                                             \
+    if ((KC) < NT) {                                                                                       \
+        double *a_ = sA + ((KC) & 1) * 16 * DEN_SA;                                                        \
+        *reinterpret_cast<double2 *>(a_ + arow * DEN_SA + aseg) = pa##SET##a;                              \
+        *reinterpret_cast<double2 *>(a_ + arow * DEN_SA + aseg + 2) = pa##SET##b;                          \
+        if ((KC) + NPF < NT) DQC_ROLE_REQUEST(t, (KC) + NPF, SET)                                          \
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                             \
+        __builtin_amdgcn_wave_barrier(); /* the chunk is wave-private: LDS executes a wave's accesses in order */ \
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                             \
+        const double *b_ = a_ + lr * DEN_SA + lk;              /* Phi[pt][ao]  (B operand) */              \
+        const double *l_ = sLT + lr * S + (KC) * DEN_KC + lk;  /* L[ao][r]     (A operand) */              \
+        _Pragma("unroll") for (int kk = 0; kk < DEN_KC / 4; kk++) {                                        \
+            const double bv = b_[kk * 4];                                                                  \
+            _Pragma("unroll") for (int ct = 0; ct < NRT; ct++)                                             \
+                a1[ct] = mfma_f64(l_[ct * 16 * S + kk * 4], bv, a1[ct]);                                   \
+        }                                                                                                  \
+    }
+#define DQC_ROLE_REQUEST4(T)  \
+    DQC_ROLE_REQUEST(T, 0, 0) DQC_ROLE_REQUEST(T, 1, 1) DQC_ROLE_REQUEST(T, 2, 2) DQC_ROLE_REQUEST(T, 3, 3)
+        int t = blockIdx.x;
+        pa0a = pa0b = pa1a = pa1b = pa2a = pa2b = pa3a = pa3b = make_double2(0.0, 0.0);
+        if (t < ntiles) { DQC_ROLE_REQUEST4(t) }
+        for (; t < ntiles; t += gridDim.x) {
+            const int g0 = t * DEN_BM;
+            v4d a1[NRT];
+#pragma unroll
+            for (int ct = 0; ct < NRT; ct++) a1[ct] = v4d{0, 0, 0, 0};
+            DQC_ROLE_STEP(0, 0) DQC_ROLE_STEP(1, 1) DQC_ROLE_STEP(2, 2) DQC_ROLE_STEP(3, 3) DQC_ROLE_STEP(4, 0)
+            DQC_ROLE_STEP(5, 1) DQC_ROLE_STEP(6, 2) DQC_ROLE_STEP(7, 3) DQC_ROLE_STEP(8, 0) DQC_ROLE_STEP(9, 1)
+            DQC_ROLE_STEP(10, 2) DQC_ROLE_STEP(11, 3) DQC_ROLE_STEP(12, 0) DQC_ROLE_STEP(13, 1)
+            {   // rho_g = sum_r A'[g][r]^2, as in density_lr_kernel
+                double rs = 0.0;
+#pragma unroll
+                for (int ct = 0; ct < NRT; ct++)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) rs += a1[ct][q] * a1[ct][q];
+                rs += __shfl_xor(rs, 16);
+                rs += __shfl_xor(rs, 32);
+                const int row = g0 + w * 16 + lr;
+                if (lk == 0 && row < ngrid) rho[row] = rs;
+            }
+            // the next tile's first chunks are requested now: they arrive while phase 2 runs on the matrix pipe
+            if (t + (int)gridDim.x < ntiles) { DQC_ROLE_REQUEST4(t + (int)gridDim.x) }
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                constexpr int PMAX = P0;
+                const int c0 = h * P0;
+                v4d acc[PMAX];
+#pragma unroll
+                for (int ct = 0; ct < PMAX; ct++) acc[ct] = v4d{0, 0, 0, 0};
+#pragma unroll
+                for (int kc = 0; kc < NRT; kc++)
+#pragma unroll
+                    for (int kk = 0; kk < 4; kk++) {
+                        const double av = a1[kc][kk];
+                        const double *b = sLT + (kc * 16 + kk * 4 + lk) * S;
+#pragma unroll
+                        for (int ct = 0; ct < PMAX; ct++)
+                            if (ct < (h ? P1 : P0)) acc[ct] = mfma_f64(av, b[role_col<NT>(c0 + ct, lr)], acc[ct]);
+                    }
+                role_wait(drained, seq, broken);  // mailbox free: the B wave has copied pass seq - 1
+#pragma unroll
+                for (int ct = 0; ct < PMAX; ct++)
+                    if (ct < (h ? P1 : P0)) {
+                        *reinterpret_cast<double2 *>(mb + (2 * ct) * 128) = make_double2(acc[ct][0], acc[ct][1]);
+                        *reinterpret_cast<double2 *>(mb + (2 * ct + 1) * 128) = make_double2(acc[ct][2], acc[ct][3]);
+                    }
+                seq++;
+                role_signal(filled, seq);
+            }
+        }
+#undef DQC_ROLE_REQUEST4
+#undef DQC_ROLE_STEP
+#undef DQC_ROLE_REQUEST
+    } else {
+        // ================= role B: the row-dot epilogue over the three gradient arrays =================
+        for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+            const int g0 = t * DEN_BM;
+            const int rmax = ngrid - 1 - g0;
+            const double *aoblk = ao + (size_t)g0 * lda;
+            int roff[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) roff[r] = min(w * 16 + lk + 4 * r, rmax) * lda + 2 * lr;
+            v4d acc[NT];
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                role_wait(filled, seq + 1, broken);
+#pragma unroll
+                for (int ct = 0; ct < (h ? P1 : P0); ct++) {
+                    const double2 lo = *reinterpret_cast<const double2 *>(mb + (2 * ct) * 128);
+                    const double2 hi = *reinterpret_cast<const double2 *>(mb + (2 * ct + 1) * 128);
+                    acc[h * P0 + ct] = v4d{lo.x, lo.y, hi.x, hi.y};
+                }
+                seq++;
+                role_signal(drained, seq);
+            }
+            double p[4][4];
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) p[r][q] = 0.0;
+            rowdot_epilogue_paired<NT, true, 1, ROLE_DP>(acc, p, aoblk, aoblk, cs, roff, lr, 0);
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int q = 1; q < 4; q++) {
+                    double v = p[r][q];
+                    v += __shfl_xor(v, 1);
+                    v += __shfl_xor(v, 2);
+                    v += __shfl_xor(v, 4);
+                    v += __shfl_xor(v, 8);
+                    p[r][q] = v;
+                }
+            const bool bad = __hip_atomic_load(broken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u;
+            if (lr == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int row = g0 + w * 16 + lk + 4 * r;
+                    if (row < ngrid) {
+                        const double nan = __builtin_nan("");
+                        grho[row] = bad ? nan : 2.0 * p[r][1];
+                        grho[(size_t)ngrid + row] = bad ? nan : 2.0 * p[r][2];
+                        grho[2 * (size_t)ngrid + row] = bad ? nan : 2.0 * p[r][3];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// shapes density_roles_kernel serves (GGA, one spin channel): the instantiations that measured faster than density_lr_kernel
+static bool density_roles_shape(int nrt, int ntile) { return nrt == 3 && ntile == 13; }
+
+// DQC_DENSITY_ROLES=0 forces density_lr_kernel (A/B runs); read at every call
+static bool density_roles_enabled() {
+    const char *e = getenv("DQC_DENSITY_ROLES");
+    return !(e && e[0] == '0');
+}
+
+static int launch_density_roles(int nrt, int ntile, hipStream_t st, double *rho, double *grho, const double *ao, int ngrid,
+                                const double *orbt, int lda) {
+    static int ncu = 0;
+    if (ncu == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+            set_error("density_roles: cannot read the device's CU count");
+            return DQC_EINVAL;
+        }
+        ncu = n;
+    }
+    const int ntiles = (ngrid + DEN_BM - 1) / DEN_BM;
+    if (nrt == 3 && ntile == 13) {
+        constexpr size_t shm = RoleGeom<3, 13>::lds_bytes();
+        static_assert(shm <= 160 * 1024, "one block has to fit the CU's LDS");
+        auto kern = density_roles_kernel<3, 13>;
+        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        hipLaunchKernelGGL(kern, dim3(std::min(ntiles, ncu)), dim3(ROLE_NT), shm, st, rho, grho, ao, ngrid, orbt, lda);
+        return 0;
+    }
+    set_error("density_roles: internal shape dispatch error");
+    return DQC_EINVAL;
+}
+
+// ---------------------------------------------------------------------------------------------
 // meta-GGA densities from the orbital factor in ONE pass (round 4): psi = Phi L and d_d psi = (d_d Phi) L for the three gradient
 // components -- four phase-1 GEMMs of density_lr_kernel, no phase 2 and no row-dot epilogue --
 //     rho = sum_r psi_r^2,   grad_d rho = 2 sum_r psi_r d_d psi_r,   tau = 1/2 sum_d sum_r (d_d psi_r)^2        (hcgto.py:398-438)
@@ -901,11 +1167,22 @@ int dqc_grid_density_lr(double *d_rho, double *d_grho, const double *d_ao, int n
     const int nchunk = (ntile + lim - 1) / lim;
     const int nct = (ntile + nchunk - 1) / nchunk;
     dim3 grid((ngrid + DEN_BM - 1) / DEN_BM);
-    int rc = gga ? launch_density_lr<true>(norb_pad / 16, nct, grid, st, d_rho, d_grho, d_ao, ngrid, ld, d_orb, d_orbt, ntile, lda)
+    int rc;
+    if (gga && density_roles_shape(norb_pad / 16, ntile) && density_roles_enabled())
+        rc = launch_density_roles(norb_pad / 16, ntile, st, d_rho, d_grho, d_ao, ngrid, d_orbt, lda);
+    else
+        rc = gga ? launch_density_lr<true>(norb_pad / 16, nct, grid, st, d_rho, d_grho, d_ao, ngrid, ld, d_orb, d_orbt, ntile, lda)
                  : launch_density_lr<false>(norb_pad / 16, nct, grid, st, d_rho, d_grho, d_ao, ngrid, ld, d_orb, d_orbt, ntile, lda);
     if (rc) return rc;
     DQC_CHECK_LAUNCH();
     return DQC_OK;
+}
+
+int dqc_grid_density_lr_roles(int nao, int norb_pad, int gga) {
+    // 1 when dqc_grid_density_lr runs this shape on density_roles_kernel (DQC_DENSITY_ROLES=0 in the environment: never), else 0
+    using namespace dqc;
+    if (!gga || norb_pad <= 0 || dqc_padded_norb(norb_pad) != norb_pad) return 0;
+    return density_roles_shape(norb_pad / 16, dqc_padded_nao(nao) / 16) && density_roles_enabled() ? 1 : 0;
 }
 
 int dqc_grid_density_lr_pol(double *d_rho, double *d_grho, const double *d_ao, int ncomp, int ngrid, int nao,

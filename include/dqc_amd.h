@@ -340,6 +340,10 @@ int dqc_grid_vxc(double *d_vmat, const double *d_ao, int ncomp, int ngrid, int n
 int dqc_padded_norb(int norb);
 int dqc_grid_density_lr(double *d_rho, double *d_grho, const double *d_ao, int ncomp, int ngrid, int nao,
                         const double *d_orb, const double *d_orbt, int norb_pad, void *stream);
+/* 1 when dqc_grid_density_lr runs this shape on the role-split kernel (density_roles_kernel: GGA, norb_pad 48, 13 AO tiles --
+ * the C5 shape), 0 when on density_lr_kernel.  DQC_DENSITY_ROLES=0 in the environment forces the latter (A/B runs; read at
+ * every call).  Same results bit for bit either way. */
+int dqc_grid_density_lr_roles(int nao, int norb_pad, int gga);
 /* Both spin densities of an unrestricted Kohn-Sham build from ONE pass over the AO matrix (reference: SpinParam.apply_fcn over
  * HamiltonCGTO._dm2densinfo, dqc/hamilton/hcgto.py:260-269, 371-418 -- one pass per spin there).  d_orb (ld, 2 norb_pad_spin) =
  * [L_u | L_d] row-major with every channel zero padded to norb_pad_spin columns (16, 32, 48 or 64), d_orbt its transpose;
