@@ -25,36 +25,22 @@ purification; the step from the core guess goes through eigh when its purificati
 later step that fails hands the run to `_run_gen` (vanishing gap: eigh needed), which also takes
 everything it does not cover (a user dm0, non-uniform occupations, a raw AO basis, direct / sharded Hamiltonians).
 """
-import os
-import warnings
-
 import torch
 
-from . import lib
+from . import lib, scfloop
 from .utils.datastruct import SpinParam
 
 
 def eligible(engine, dm0, opts) -> bool:
-    """can `DeviceLoop` run this calculation?  (otherwise the host-driven generator of qccalc.py does)"""
+    """can `DeviceLoop` run this calculation?  (otherwise the host-driven generator of qccalc.py does); `opts`: scfloop.options"""
     if not isinstance(dm0, str) or dm0 != "1e":
         return False
-    if not opts.get("graph", os.environ.get("DQC_AMD_GRAPH", "1") != "0"):
-        return False
-    if opts.get("driver", os.environ.get("DQC_AMD_SCF_DRIVER", "device")) != "device":
-        return False
-    if opts.get("diag", os.environ.get("DQC_AMD_DIAG", "purify")) != "purify":
+    if not opts["graph"] or opts["driver"] != "device" or opts["diag"] != "purify":
         return False
     h = engine.hamilton
     if getattr(h, "_direct", False) or getattr(h, "sharded", False) or getattr(engine, "ovlp", None) is not None:
         return False
-    if not (1 <= int(opts.get("history", 12)) <= 16):
-        return False
-    ws = [engine.orb_weight.u, engine.orb_weight.d] if engine.polarized else [engine.orb_weight]
-    if not all((not w.numel()) or bool((w == w[0]).all()) for w in ws):
-        return False
-    if torch.cuda.is_current_stream_capturing():
-        return False
-    return True
+    return 1 <= int(opts["history"]) <= 16 and scfloop.uniform_occupations(engine) and not torch.cuda.is_current_stream_capturing()
 
 
 class DeviceLoop:
@@ -85,22 +71,23 @@ class DeviceLoop:
         self.graph = None
 
     # ------------------------------------------------------------------ pieces
+    def _load(self, fock, dm):
+        """(fock, dm, etot) <- a pair as the engine returns it"""
+        if self.pol:  # an unrestricted engine evaluates dm2energy of the final densities once, after the loop
+            self.fock.copy_(fock)
+            self.dm[0].copy_(dm.u)
+            self.dm[1].copy_(dm.d)
+        else:  # the two-electron parts are by-products of the build just made (the Hamiltonian's memo)
+            self.fock[0].copy_(fock)
+            self.dm[0].copy_(dm)
+            self.etot.copy_(self.eng.dm2energy(dm))
+
     def _build_from(self, fmix):
         """(fock, dm, etot, perr) <- one step from the mixed Fock matrix (purification + Fock build)"""
         st = self.step
         st.f_in.copy_(fmix if self.pol else fmix[0])
         f_out, d_out, perr = st._body()
-        if self.pol:
-            self.fock.copy_(f_out)
-            self.dm[0].copy_(d_out.u)
-            self.dm[1].copy_(d_out.d)
-            dmx = d_out
-        else:
-            self.fock[0].copy_(f_out)
-            self.dm[0].copy_(d_out)
-            dmx = d_out
-        if not self.pol:  # the two-electron parts are by-products of the build just made (the Hamiltonian's memo); an unrestricted
-            self.etot.copy_(self.eng.dm2energy(dmx))  # engine evaluates dm2energy of the final densities once, after the loop
+        self._load(f_out, d_out)
         self.perr.copy_(perr)
 
     def _iteration(self):
@@ -129,88 +116,78 @@ class DeviceLoop:
     def _capture(self):
         dev = self.eng.device
         # warm-up on a side stream (allocator, lazy kernel attributes), from a scratch copy of the state; then capture
-        keep = [t.clone() for t in (self.fock, self.dm, self.etot, self.perr, self.fh, self.eh, self.gram, self.count)]
+        state = (self.fock, self.dm, self.etot, self.perr, self.fh, self.eh, self.gram, self.count)
+        keep = [t.clone() for t in state]
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
             self._iteration()
         torch.cuda.current_stream(dev).wait_stream(s)
         torch.cuda.synchronize(dev)
-        for t, k in zip((self.fock, self.dm, self.etot, self.perr, self.fh, self.eh, self.gram, self.count), keep):
+        for t, k in zip(state, keep):
             t.copy_(k)
         getattr(self.eng.hamilton, "_tiles", None) if self.eng.hamilton.df is None else None  # (retires the tile-fill event)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self._iteration()
-        for t, k in zip((self.fock, self.dm, self.etot, self.perr, self.fh, self.eh, self.gram, self.count), keep):
+        for t, k in zip(state, keep):
             t.copy_(k)  # (a capture does not execute: belt and braces)
         self.eng.hamilton.clear_memos()
 
     # ------------------------------------------------------------------ the loop
+    def _scalars(self, j):
+        """(max|[F, D]|, projector error) of the entering pair of iteration j, from pinned memory (valid once the event recorded
+        behind iteration j has completed)"""
+        return float(self.host[j % 2, 0]), float(self.host[j % 2, 1])
+
     def run(self, qc, opts):
-        """drive `qc` (an SCF_QCCalc) to convergence; returns True, or False when the caller has to take over with the
-        host-driven loop (a purification that did not converge: the step needs eigh)"""
+        """drive `qc` (an SCF_QCCalc) to convergence with `opts` (scfloop.options); returns None, or the scfloop.Handover with
+        which the host-driven loop has to take over (a purification that did not converge: the step needs eigh)"""
         eng, n, S, dev = self.eng, self.n, self.S, self.eng.device
         f_tol, maxiter = float(opts["f_tol"]), int(opts["maxiter"])
         if maxiter < 1:
             raise RuntimeError("maxiter must be >= 1")
-        trace = bool(os.environ.get("DQC_AMD_SCF_TRACE"))
-        qc._resume_dm = None
         # core guess (scf_qccalc.py:88-91): F0 = dm2scp(0), occupy its lowest orbitals -- the first step, eagerly
-        z = torch.zeros((n, n), dtype=eng.dtype, device=dev)
-        f0 = eng.dm2scp(SpinParam(u=z, d=z) if self.pol else z)
+        f0 = scfloop.core_guess_fock(eng)
         self._build_from(f0.reshape(S, n, n))
         for t in (self.fh, self.eh, self.gram, self.count):
             t.zero_()
-        if not float(self.perr) < 1e-9:   # (the one synchronisation before the loop)
+        if scfloop.projector_failed(float(self.perr)):   # (the one synchronisation before the loop)
             # the bare-nucleus Hamiltonian often has a degenerate or vanishing gap at the Fermi level (open pi shells, ...): this one
             # step through eigh, as the reference's (hf.py:137-150) -- later steps that fail hand the run to the host-driven loop
-            qc.eigh_fallbacks = getattr(qc, "eigh_fallbacks", 0) + 1
+            qc.eigh_fallbacks += 1
             dm = eng.scp2dm(f0)
-            fock = eng.dm2scp(dm)
-            if self.pol:
-                self.fock.copy_(fock)
-                self.dm[0].copy_(dm.u)
-                self.dm[1].copy_(dm.d)
-            else:
-                self.fock[0].copy_(fock)
-                self.dm[0].copy_(dm)
-                self.etot.copy_(eng.dm2energy(dm))
+            self._load(eng.dm2scp(dm), dm)
             self.perr.zero_()
         if self.graph is None:
             self._capture()
         evs = [torch.cuda.Event(), torch.cuda.Event()]
-        best_err, best_it = float("inf"), 0
+        progress = scfloop.Progress(f_tol)
         qc.converged = qc.stalled = False
-        done_at = None
         stream = torch.cuda.current_stream(dev)
 
         def look(j):
-            """host-side bookkeeping of iteration j (its scalars are in pinned memory once evs[j % 2] has completed)"""
-            nonlocal best_err, best_it
+            """host-side bookkeeping of iteration j: None to go on, or how the loop ends"""
             evs[j % 2].synchronize()
-            emax, pe = float(self.host[j % 2, 0]), float(self.host[j % 2, 1])
+            emax, pe = self._scalars(j)
             qc.niter, qc.scf_error = j + 1, emax
-            if trace:
+            if opts["trace"]:
                 print("scf it %2d  max|[F,D]| %.2e  (device loop)" % (j, emax), flush=True)
-            if not emax == emax or emax == float("inf"):  # a non-finite error: the host-driven loop starts over with eigh steps
+            if not scfloop.finite(emax):  # the host-driven loop starts over with eigh steps
                 return "restart"
-            if getattr(self, "_test_fail_at", None) == j:  # (test hook: a projector failure at iteration j)
+            if scfloop.projector_failed(pe):  # (vanishing gap): the host-driven loop resumes from the last good density
                 return "fallback"
-            if not pe < 1e-9:  # the projector of this step failed (vanishing gap): the host-driven loop resumes from the last good density
-                return "fallback"
-            if emax < best_err * 0.9:
-                best_err, best_it = emax, j
-            if j - best_it >= 40 and emax > 1e-6:
+            progress.note(emax, j)  # (BEFORE the wander check; the host-driven loop notes after its own -- kept as found)
+            if progress.wandering(emax, j):
                 # the wander guard of the host-driven loop (qccalc.py): inside a degenerate Fermi level the purification step has no
                 # preferred basis and the iteration never settles (UKS SCAN, oxygen triplet) -- hand over, eigh steps from the core guess
                 return "restart"
-            if emax < f_tol:
+            if progress.converged(emax):
                 qc.converged = True
                 return "done"
-            if emax < 100 * f_tol and j - best_it >= 8:
+            if progress.stalled(emax, j):
                 qc.stalled = True
-                warnings.warn("SCF stopped at the round-off floor of the Fock build: max|[F,D]| = %.2e (f_tol %.1e)" % (emax, f_tol))
+                scfloop.warn_stalled(emax, f_tol)
                 return "done"
             return None
 
@@ -226,35 +203,23 @@ class DeviceLoop:
         if verdict is None:
             verdict = look(maxiter - 1)
             done_at = maxiter - 1
-            if verdict is None and qc.scf_error > 1e-6:
+            if verdict is None and scfloop.far_off(qc.scf_error):
                 # out of iterations far from a fixed point: the reference's diagonalise-and-occupy step (hf.py:105-113) gets its turn
                 # before the run is reported as not converged (the degenerate-level wander needs 40 steps to be told from slow progress)
                 verdict = "restart"
         torch.cuda.synchronize(dev)
+        # the entering pair of iteration `done_at` (the iteration launched after it wrote the other ring slot)
+        p = done_at % 2
         if verdict == "restart":
             # wandering or non-finite: nothing of this run is worth resuming from (a non-finite commutator means the entering pair of
             # iteration `done_at` is already non-finite) -- the host-driven loop starts at the core guess WITHOUT the purification step
-            qc._resume_dm = None
-            qc._skip_purification = True
-            return False
+            return scfloop.Handover(purification=False)
         if verdict == "fallback":
             # a projector failure with a finite error: the entering density of the failing iteration is the last good iterate (every
             # earlier step passed its projector check) -- the host-driven loop resumes from it instead of the core guess
-            p = done_at % 2
-            if done_at >= 1:
-                qc._resume_dm = SpinParam(u=self.ring_d[p, 0].clone(), d=self.ring_d[p, 1].clone()) if self.pol else self.ring_d[p, 0].clone()
-            return False
-        # the entering pair of iteration `done_at` (the iteration launched after it wrote the other ring slot)
-        p = done_at % 2
-        if self.pol:
-            qc._dm = SpinParam(u=self.ring_d[p, 0].clone(), d=self.ring_d[p, 1].clone())
-            qc._fock = self.ring_f[p].clone()
-        else:
-            qc._dm = self.ring_d[p, 0].clone()
-            qc._fock = self.ring_f[p, 0].clone()
-        qc._energy = None if self.pol else self.ring_e[p].clone()
-        qc._has_run = True
-        if not qc.accepted:
-            warnings.warn("SCF did not converge in %d iterations: max|[F,D]| = %.2e (f_tol %.1e); energy() and "
-                          "nuclear_gradient() of this object refer to a non-stationary density" % (qc.niter, qc.scf_error, f_tol))
-        return True
+            if done_at < 1:
+                return scfloop.Handover()
+            d = self.ring_d[p]
+            return scfloop.Handover(dm=SpinParam(u=d[0].clone(), d=d[1].clone()) if self.pol else d[0].clone(), projector_failures=1)
+        scfloop.store_result(qc, self.ring_f[p], self.ring_d[p], self.ring_e[p], f_tol, stacked=True)
+        return None

@@ -21,29 +21,18 @@ length, same least-squares Pulay solve, same purification.
 Restricted closed-shell and unrestricted (stacked F_u, F_d; hf.py:93-103) engines with uniform occupations per spin channel in
 an orthogonalised basis; `signature(qc)` says whether a calculation qualifies -- everything else (restricted open-shell,
 fractional occupations, raw AO bases) keeps the one-molecule driver (`batch.run_lockstep` sorts that out)."""
-import os
-import warnings
-
 import torch
 
 from . import lib
 from .purify import _TC2_ITERS
+from .scfloop import PROJECTOR_TOL, Progress, core_guess_fock, drive, options, projector_failed, spin_channels, store_result
 from .utils.datastruct import SpinParam
 
 
-def _spin_channels(eng):
-    """[(n_occ, occupation)] per spin channel (one entry for a restricted engine), or None when a channel's occupations are
-    not uniform; an empty channel (the reference keeps one orbital of weight 0 there, mol.py:437-441) counts as n_occ = 0"""
-    ws = [eng.orb_weight.u, eng.orb_weight.d] if eng.polarized else [eng.orb_weight]
-    out = []
-    for w in ws:
-        if not w.numel() or bool((w == 0).all()):
-            out.append((0, 0.0))
-        elif bool((w == w[0]).all()):
-            out.append((int(w.numel()), float(w[0])))
-        else:
-            return None
-    return out
+# a molecule close to the tolerance (scfloop.STALL_BAND) whose error has not improved for this many steps gets its Pulay subspace
+# restarted, at most this many times, before the stall rule shared with the other drivers ends its run
+_SUBSPACE_RESTART_STEPS = 5
+_SUBSPACE_RESTARTS = 2
 
 
 def signature(qc):
@@ -55,7 +44,7 @@ def signature(qc):
     # branches, which only SCF_QCCalc.run guarantees (it broadcasts rank 0's per-iteration scalars, hamilton.sync_scalars)
     if getattr(getattr(eng, "hamilton", None), "sharded", False):
         return None
-    ch = _spin_channels(eng)
+    ch = spin_channels(eng)
     if ch is None:
         return None
     n = int(eng.shape[-1])
@@ -111,7 +100,7 @@ class LockstepSCF:
         self.device, self.dtype = e0.device, e0.dtype
         self._engine = e0  # (batch.run_concurrent reads the device from here)
         self.pol = bool(e0.polarized)
-        self.channels = _spin_channels(e0)            # [(n_occ, occupation)] per spin
+        self.channels = spin_channels(e0)            # [(n_occ, occupation)] per spin
         self.S = len(self.channels)
         self.n = int(e0.shape[-1])
         self.r = self.channels[0][0]
@@ -163,7 +152,7 @@ class LockstepSCF:
         through eigh.  Synchronises."""
         f4 = focks if focks.dim() == 4 else focks.unsqueeze(1)
         qs, err = self._occupied(f4)
-        for m in (~(err < 1e-9)).nonzero().reshape(-1).tolist():
+        for m in (~(err < PROJECTOR_TOL)).nonzero().reshape(-1).tolist():
             self._eigh_orbitals(m, f4[m], qs)
             self.eigh_fallbacks += 1
         return qs[0] if focks.dim() == 3 else qs
@@ -205,13 +194,7 @@ class LockstepSCF:
 
     # ------------------------------------------------------------------ the loop
     def run(self, **kw):
-        gen = self._run_gen(**kw)
-        try:
-            req = next(gen)
-            while True:
-                req = gen.send(req.cpu().numpy())
-        except StopIteration:
-            pass
+        drive(self._run_gen(**kw))
         return self
 
     def _run_gen(self, dm0="1e", fwd_options=None):
@@ -219,8 +202,7 @@ class LockstepSCF:
         iteration for the whole batch), is resumed with its numpy copy"""
         if dm0 != "1e":
             raise RuntimeError("LockstepSCF starts from the core guess dm0='1e' (scf_qccalc.py:88-91)")
-        opts = {"maxiter": 50, "f_tol": 1e-9, "history": 12}
-        opts.update(fwd_options or {})
+        opts = options(fwd_options)
         H = int(opts["history"])
         M, n, S, dev, dt = len(self.qcs), self.n, self.S, self.device, self.dtype
         main = torch.cuda.current_stream(dev)
@@ -232,7 +214,6 @@ class LockstepSCF:
         gram = torch.zeros((M, H, H), dtype=dt, device=dev)
         coef = torch.zeros((M, H), dtype=dt, device=dev)
         etot = torch.zeros(M, dtype=dt, device=dev)
-        trace = bool(os.environ.get("DQC_AMD_SCF_TRACE"))
         for q in self.qcs:
             q.converged = q.stalled = False
             q.niter, q.scf_error = 0, float("inf")
@@ -241,21 +222,20 @@ class LockstepSCF:
         def fix_failed(qmat, fmix, perr_host, which):
             # purification did not converge (vanishing gap): that molecule's orbitals come from eigh (hf.py:227-247)
             for m in which:
-                if not perr_host[m] < 1e-9:
+                if projector_failed(perr_host[m]):
                     self._eigh_orbitals(m, fmix[m], qmat)
                     self.qcs[m].eigh_fallbacks += 1
                     self.eigh_fallbacks += 1
 
         # core guess (scf_qccalc.py:88-91): F0 = dm2scp(0), occupy its lowest orbitals
-        z = torch.zeros((n, n), dtype=dt, device=dev)
-        f0 = torch.stack([e.dm2scp(SpinParam(u=z, d=z) if self.pol else z) for e in self.engines]).reshape(M, S, n, n)
+        f0 = torch.stack([core_guess_fock(e) for e in self.engines]).reshape(M, S, n, n)
         qmat, perr = self._occupied(f0)
         host = yield perr
         active = list(range(M))
         fix_failed(qmat, f0, host, active)
         self._build(qmat, active, fock, dm, etot, streams)
 
-        best = [[float("inf"), 0] for _ in range(M)]
+        progress = [Progress(opts["f_tol"]) for _ in range(M)]
         restarts = [0] * M
         fmix = f0
         for it in range(int(opts["maxiter"])):
@@ -279,48 +259,32 @@ class LockstepSCF:
             qmat, perr = self._occupied(fmix)
             host = yield torch.cat([emax_t, perr])
             emax, pe = host[:M], host[M:]
-            if trace:
+            if opts["trace"]:
                 print("lockstep it %2d  max|[F,D]|: %s" % (it, " ".join("%.1e" % emax[m] for m in range(M))), flush=True)
             for m in list(active):
-                qc = self.qcs[m]
-                qc.niter, qc.scf_error = it + 1, float(emax[m])
-                if emax[m] < best[m][0] * 0.9:
-                    best[m] = [float(emax[m]), it]
-                done = emax[m] < opts["f_tol"]
-                stagnant = (not done) and emax[m] < 100 * opts["f_tol"]
-                if stagnant and it - best[m][1] >= 5 and restarts[m] < 2:
+                qc, p, e = self.qcs[m], progress[m], float(emax[m])
+                qc.niter, qc.scf_error = it + 1, e
+                p.note(e, it)
+                done = p.converged(e)
+                if not done and p.stalled(e, it, _SUBSPACE_RESTART_STEPS) and restarts[m] < _SUBSPACE_RESTARTS:
                     # five steps without progress close to the tolerance (seen once in ~200 molecule runs of the C5 batch:
                     # 3e-9 at step 42): restart this molecule's Pulay subspace from the current iterate -- every slot holds
                     # the present (F, [F, D]) pair, a rank-one Gram block whose minimum-norm solution is F itself -- before
                     # calling it stalled
                     restarts[m] += 1
-                    best[m][1] = it
+                    p.best_it = it
                     eh[m, :] = eh[m, slot].clone()
                     fh[m, :] = fh[m, slot].clone()
                     gram[m, :, :] = gram[m, slot, slot].clone()
-                stalled = stagnant and it - best[m][1] >= 8
+                stalled = not done and p.stalled(e, it)  # (silently; and no wander guard in this driver)
                 if done or stalled:
-                    qc.converged, qc.stalled = bool(done), bool(stalled)
-                    self._finish(qc, m, fock, dm, etot)
+                    qc.converged, qc.stalled = done, stalled
+                    store_result(qc, fock[m], dm[m], etot[m], opts["f_tol"], stacked=True)
                     active.remove(m)
             if not active:
                 break
             fix_failed(qmat, fmix, pe, active)
             if it + 1 < int(opts["maxiter"]):
                 self._build(qmat, active, fock, dm, etot, streams)
-        for m in active:  # maxiter exhausted
-            qc = self.qcs[m]
-            self._finish(qc, m, fock, dm, etot)
-            warnings.warn("SCF did not converge in %d iterations: max|[F,D]| = %.2e (f_tol %.1e)"
-                          % (qc.niter, qc.scf_error, opts["f_tol"]))
-
-    def _finish(self, qc, m, fock, dm, etot):
-        if self.pol:
-            qc._dm = SpinParam(u=dm[m, 0].clone(), d=dm[m, 1].clone())
-            qc._fock = fock[m].clone()
-            qc._energy = None  # (energy() evaluates dm2energy of the stored densities)
-        else:
-            qc._dm = dm[m, 0].clone()
-            qc._fock = fock[m, 0].clone()
-            qc._energy = etot[m].clone()  # engine.dm2energy(dm) as evaluated with the Fock build of this very dm
-        qc._has_run = True
+        for m in active:  # maxiter exhausted: stored with the "did not converge" warning
+            store_result(self.qcs[m], fock[m], dm[m], etot[m], opts["f_tol"], stacked=True)

@@ -17,6 +17,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import scfloop
 from .utils.datastruct import SpinParam
 from .xc import get_xc
 
@@ -146,6 +147,109 @@ class _Engine:
         return p
 
 
+def _commutator(fock, dm, ovlp):
+    """[F, D] (S = 1) or F D S - S D F, S the overlap of a non-orthogonalised basis (None: identity); stacked over the spin
+    channels of an unrestricted pair"""
+    d = torch.stack([dm.u, dm.d]) if isinstance(dm, SpinParam) else dm
+    return fock @ d - d @ fock if ovlp is None else fock @ d @ ovlp - ovlp @ d @ fock
+
+
+class _HostDIIS:
+    """Pulay mixing of the host-driven loop: Fock matrices and error vectors stay on the device, the Gram matrix lives on the
+    host and grows by the row the loop reads each iteration"""
+
+    def __init__(self, history):
+        self.history = int(history)
+        self.reset()
+
+    def reset(self):
+        self.fs, self.es, self.gram = [], [], np.zeros((0, 0))
+
+    def gram_row(self, ev):
+        """(device) the error vector `ev` against the stored ones that survive its insertion, and itself"""
+        hist = self.es[-(self.history - 1):] if self.history > 1 else []
+        return (torch.stack(hist + [ev]) * ev).sum(-1)
+
+    def mix(self, fock, ev, grow):
+        """store (fock, ev) with the host copy `grow` of gram_row(ev); returns the Pulay mix of the stored Fock matrices"""
+        self.fs.append(fock)
+        self.es.append(ev)
+        if len(self.fs) > self.history:
+            self.fs.pop(0)
+            self.es.pop(0)
+        m = len(self.fs)
+        # the Gram matrix lives on the host and grows by the row just read (broadcast-multiply-reduce on the device:
+        # the GEMM form E @ E.T hits a pathological rocBLAS path for the tall-skinny fp64 shape, 7 ms for 8 x 43264)
+        keep = m - 1  # the stored vectors that survive
+        gram = np.zeros((m, m))
+        if keep:
+            gram[:keep, :keep] = self.gram[-keep:, -keep:]
+        gram[keep, :] = grow
+        gram[:, keep] = grow
+        self.gram = gram
+        if m == 1:
+            return fock
+        B = np.zeros((m + 1, m + 1))
+        # the Pulay coefficients do not change when the Gram block is scaled (only the multiplier does): normalised to
+        # a unit largest diagonal, otherwise lstsq's rank cut (eps x largest singular value, set by the +-1 border)
+        # discards the whole Gram block once the errors fall below ~1e-8 and the mix degrades to a plain average
+        B[:m, :m] = gram / max(float(np.max(np.diag(gram))), 1e-300) if _DIIS_SCALE else gram
+        B[m, :m] = -1
+        B[:m, m] = -1
+        rhs = np.zeros(m + 1)
+        rhs[m] = -1
+        # (m+1) x (m+1) Pulay system on the host with numpy: torch's CPU lstsq costs ~7 ms per call on a
+        # 256-thread box (thread-pool wake-up), several times the whole Fock build
+        try:
+            c = np.linalg.lstsq(B, rhs, rcond=None)[0][:m] if np.isfinite(B).all() else None
+        except np.linalg.LinAlgError:  # (LAPACK's SVD gives up on an ill-scaled or non-finite Gram block)
+            c = None
+        if c is None or not np.isfinite(c).all():
+            # a Pulay system that cannot be solved: forget the history and take the plain step from this Fock matrix (the next
+            # iterations rebuild the history; a non-finite commutator is caught at the top of the loop)
+            self.fs, self.es, self.gram = [fock], [ev], np.array([[float(grow[-1])]])
+            c = np.ones(1)
+        c = torch.as_tensor(c, dtype=fock.dtype).to(fock.device)
+        return (c.reshape((-1,) + (1,) * fock.dim()) * torch.stack(self.fs)).sum(0)
+
+
+def _choose_step(eng, opts, purification):
+    """(GraphedSCFStep or None, GraphedFock or None): how the host-driven loop gets from a mixed Fock matrix to the next pair.
+    Restricted engines replay the Fock build as one hipGraph (dqc_amd/graph.py); "graph": False runs it eagerly.
+    "diag": "purify" (default for uniform occupations) replaces eigh by GEMM-only purification inside the same graph
+    (dqc_amd/purify.py); "eigh" keeps the reference's diagonalise-and-occupy step (hf.py:105-113)"""
+    # (direct SCF builds allocate stream-ordered scratch and upload pair tables per call: not captured)
+    # (nor the builds of a Hamiltonian sharded over several GPUs: they hold collectives)
+    # A direct-SCF engine still takes the purification step, launched eagerly: the 412 x 412 eigh of naphthalene / cc-pVTZ is
+    # 6 ms of rocSOLVER launches per iteration against ~1 ms of GEMMs
+    ham = getattr(eng, "hamilton", None)
+    direct = bool(getattr(ham, "_direct", False))
+    if not opts["graph"] or getattr(ham, "sharded", False):
+        return None, None
+    from .graph import GraphedFock, GraphedSCFStep
+    if opts["diag"] == "purify" and scfloop.uniform_occupations(eng) and getattr(eng, "ovlp", None) is None and purification:
+        return GraphedSCFStep(eng, capture=not direct), None
+    if not eng.polarized and not direct:
+        return None, GraphedFock(eng)
+    return None, None
+
+
+def _take_step(eng, fmix, purified, graphed):
+    """(fock, dm, projector error or None) of the step from the mixed Fock matrix `fmix`"""
+    if purified is not None:
+        f_out, d_out, perr = purified(fmix)
+        if purified.graph is None:  # eager step (direct SCF): fresh tensors, and the Hamiltonian's caches stay keyed on them
+            return f_out, d_out, perr
+        # static buffers of the graph: copy out
+        dm = SpinParam(u=d_out.u.clone(), d=d_out.d.clone()) if eng.polarized else d_out.clone()
+        return f_out.clone(), dm, perr.clone()
+    if graphed is not None:
+        fock = graphed(eng.scp2orb(fmix)).clone()
+        return fock, graphed.density_matrix().clone(), None
+    dm = eng.scp2dm(fmix)
+    return eng.dm2scp(dm), dm, None
+
+
 class SCF_QCCalc:
     def __init__(self, engine):
         self._engine = engine
@@ -154,6 +258,12 @@ class SCF_QCCalc:
         self.converged = False   # max|[F, D]| < f_tol
         self.stalled = False     # stopped at the round-off floor of the Fock build, above f_tol (see run())
         self.scf_error = float("inf")  # max|[F, D]| of the returned iterate -- the achieved error, whatever the exit
+        self.fock_residual = None      # the reference's own fixed-point residual max|F_out - F_in| (host-driven loop)
+        self.driver_used = None        # "device" / "host": which loop produced the result (diagnostics / tests)
+        self.eigh_fallbacks = 0        # purification steps redone through eigh (accumulates over run() calls; lockstep resets it)
+        self.purification_dropped = False  # a run gave up the purification step for eigh steps from the core guess (sticky)
+        self._devloop = None           # the DeviceLoop of this object, kept for the next run()
+        self._dm = self._fock = self._energy = None
 
     @property
     def accepted(self):
@@ -168,229 +278,129 @@ class SCF_QCCalc:
         """the SCF loop, driven synchronously: every host read of the generator below is a blocking device -> host copy.
         dqc_amd.batch.run_concurrent drives many of these generators at once, one stream per molecule."""
         # one molecule, core guess, purification step: the whole iteration replays as ONE hipGraph and the host only looks at two
-        # doubles per iteration, one iteration late (dqc_amd/devscf.py); everything else takes the host-driven generator below
+        # doubles per iteration, one iteration late (dqc_amd/devscf.py); everything else takes the host-driven generator below,
+        # and so does what the device loop hands over (a projector failure mid-run, a wandering purification)
         from . import devscf
-        opts = {"maxiter": 50, "f_tol": 1e-9, "history": 12}
-        opts.update(fwd_options or {})
+        opts = scfloop.options(fwd_options)
+        handover = None
         if self._engine.device.type == "cuda" and devscf.eligible(self._engine, dm0, opts):
-            loop = getattr(self, "_devloop", None)
-            if loop is None or loop.H != int(opts["history"]):
-                loop = self._devloop = devscf.DeviceLoop(self._engine, int(opts["history"]))
-            if loop.run(self, opts):
-                self.driver_used = "device"  # (which loop produced the result: diagnostics / tests)
+            if self._devloop is None or self._devloop.H != int(opts["history"]):
+                self._devloop = devscf.DeviceLoop(self._engine, int(opts["history"]))
+            handover = self._devloop.run(self, opts)
+            if handover is None:
+                self.driver_used = "device"
                 return self
         self.driver_used = "host"
-        resume = getattr(self, "_resume_dm", None)  # the device loop's last good density (a projector failure mid-run)
-        if resume is not None:
-            dm0, self._resume_dm = resume, None
-            self._resumed_after_failure = True
-        gen = self._run_gen(dm0, fwd_options)
         # a Hamiltonian sharded over several GPUs (HamiltonMI355.shard_over) runs this loop on every rank: the scalars the
         # driver decides on are rank 0's, so that every rank takes the same branch and issues the same collectives
         sync = getattr(getattr(self._engine, "hamilton", None), "sync_scalars", lambda t: t)
-        try:
-            req = next(gen)
-            while True:
-                req = gen.send(sync(req).cpu().numpy())
-        except StopIteration:
-            pass
+        scfloop.drive(self._run_gen(dm0, fwd_options, handover), sync)
         return self
 
-    def _run_gen(self, dm0="1e", fwd_options=None):
-        """generator form of run(): yields the (small) device tensor it needs on the host -- ONE per SCF iteration -- and is
-        resumed with that tensor's numpy copy; everything else is enqueued on the current stream without synchronising"""
-        opts = {"maxiter": 50, "f_tol": 1e-9, "history": 12}
-        opts.update(fwd_options or {})
+    def _initial_density(self, dm0):
         eng = self._engine
         if isinstance(dm0, str):
             if dm0 != "1e":
                 raise RuntimeError("Unknown dm0: %s" % dm0)
-            n = eng.shape[-1]
-            z = torch.zeros((n, n), dtype=eng.dtype, device=eng.device)
-            scp0 = eng.dm2scp(SpinParam(u=z, d=z) if eng.polarized else z)
-            dm = eng.scp2dm(scp0)
+            dm = eng.scp2dm(scfloop.core_guess_fock(eng))
         elif dm0 is None:
             raise RuntimeError("dm0 must be '1e' or a density matrix")
         else:
             dm = SpinParam.apply_fcn(lambda d: d.to(eng.device), dm0)
         if eng.polarized and not isinstance(dm, SpinParam):  # scf_qccalc.py:97-100
             dm = SpinParam(u=dm * 0.5, d=dm * 0.5)
-        pol = eng.polarized
-        fs, es = [], []
+        return dm
+
+    def _run_gen(self, dm0="1e", fwd_options=None, handover=None):
+        """generator form of run(): yields the (small) device tensor it needs on the host -- ONE per SCF iteration -- and is
+        resumed with that tensor's numpy copy; everything else is enqueued on the current stream without synchronising.
+        `handover`: what the device loop left (scfloop.Handover) when it could not finish this run"""
+        opts = scfloop.options(fwd_options)
+        eng = self._engine
+        handover = handover or scfloop.Handover()
+        dm = self._initial_density(dm0 if handover.dm is None else handover.dm)
         fock = eng.dm2scp(dm)
-        # restricted engines replay the Fock build as one hipGraph (dqc_amd/graph.py); "graph": False runs it eagerly
-        # "diag": "purify" (default for closed shells) replaces eigh by GEMM-only purification inside the same graph
-        # (dqc_amd/purify.py); "eigh" keeps the reference's diagonalise-and-occupy step (hf.py:105-113)
-        graphed, purified = None, None
-        # (direct SCF builds allocate stream-ordered scratch and upload pair tables per call: not captured)
-        # (nor the builds of a Hamiltonian sharded over several GPUs: they hold collectives)
-        # A direct-SCF engine still takes the purification step, launched eagerly: the 412 x 412 eigh of naphthalene / cc-pVTZ is
-        # 6 ms of rocSOLVER launches per iteration against ~1 ms of GEMMs
-        ham = getattr(eng, "hamilton", None)
-        direct = bool(getattr(ham, "_direct", False))
-        resumed_after_failure = bool(getattr(self, "_resumed_after_failure", False))
-        self._resumed_after_failure = False
-        skip_purify = bool(getattr(self, "_skip_purification", False))  # (the device loop wandered: eigh steps from the start)
-        self._skip_purification = False
-        if skip_purify:
+        if not handover.purification:  # (the device loop wandered: eigh steps from the start)
             self.purification_dropped = True
-        if opts.get("graph", os.environ.get("DQC_AMD_GRAPH", "1") != "0") and not getattr(ham, "sharded", False):
-            from .graph import GraphedFock, GraphedSCFStep
-            ws = [eng.orb_weight.u, eng.orb_weight.d] if pol else [eng.orb_weight]
-            uniform = all((not w.numel()) or bool((w == w[0]).all()) for w in ws)
-            if opts.get("diag", os.environ.get("DQC_AMD_DIAG", "purify")) == "purify" and uniform and getattr(eng, "ovlp", None) is None and not skip_purify:
-                purified = GraphedSCFStep(eng, capture=not direct)
-            elif not pol and not direct:
-                graphed = GraphedFock(eng)
-        perr = None
-        fprev = None
-        gram = np.zeros((0, 0))
-        best_err, best_it = float("inf"), 0
+        purified, graphed = _choose_step(eng, opts, handover.purification)
+        ovlp = getattr(eng, "ovlp", None)
+        diis = _HostDIIS(opts["history"])
+        progress = scfloop.Progress(opts["f_tol"])
+        perr = fprev = None
         self.converged = self.stalled = False
         # iteration budget: `maxiter` steps -- and `maxiter` more from the restart, once, when the purification step is dropped (the
         # reference's diagonalise-and-occupy iteration gets the cap the caller set; the steps the purification wandered do not count)
         it, it_end = -1, int(opts["maxiter"])
-        nfail = 1 if resumed_after_failure else 0   # projector failures so far (the device loop's hand-over counts)
+        nfail = handover.projector_failures
         while it + 1 < it_end:
             it += 1
             self.niter = it + 1
-            S = getattr(eng, "ovlp", None)  # overlap of a non-orthogonalised basis (None: identity)
-            if pol:
-                dms = torch.stack([dm.u, dm.d])
-                err = fock @ dms - dms @ fock if S is None else fock @ dms @ S - S @ dms @ fock
-            else:
-                err = fock @ dm - dm @ fock if S is None else fock @ dm @ S - S @ dm @ fock  # [F, D] (S = 1) or F D S - S D F
+            err = _commutator(fock, dm, ovlp)
             # ONE host read per iteration: max |[F, D]|, the projector error of the step just taken, and the new row of the
             # DIIS Gram matrix (this error vector against the stored ones) travel together
             ev = err.reshape(-1)
-            hist = es[-(int(opts["history"]) - 1):] if int(opts["history"]) > 1 else []
-            row = (torch.stack(hist + [ev]) * ev).sum(-1)
             zero = torch.zeros((), dtype=fock.dtype, device=fock.device)
             # the reference's own fixed-point residual max|F_out - F_in| (scp2scp(y) - y, scf_qccalc.py:109-113) rides along
             fres_t = (fock - fprev).abs().max() if fprev is not None else zero + float("inf")
             head = torch.stack([err.abs().max(), perr if perr is not None else zero, fres_t])
-            host = yield torch.cat([head, row])
+            host = yield torch.cat([head, diis.gram_row(ev)])
             emax, pe, fres, grow = float(host[0]), float(host[1]), float(host[2]), host[3:]
             self.fock_residual = fres
-            if os.environ.get("DQC_AMD_SCF_TRACE"):
+            if opts["trace"]:
                 print("scf it %2d  max|[F,D]| %.2e  max|F_out-F_in| %.2e" % (it, emax, fres), flush=True)
-            if perr is not None and not pe < 1e-9:  # purification did not converge (vanishing gap): redo this step through eigh
-                self.eigh_fallbacks = getattr(self, "eigh_fallbacks", 0) + 1
+            if perr is not None and scfloop.projector_failed(pe):
+                # purification did not converge (vanishing gap): redo this step through eigh
+                self.eigh_fallbacks += 1
                 nfail += 1
                 dm = eng.scp2dm(fprev)
                 fock = eng.dm2scp(dm)
                 perr = None
-                dmm = torch.stack([dm.u, dm.d]) if pol else dm
-                err = fock @ dmm - dmm @ fock if S is None else fock @ dmm @ S - S @ dmm @ fock
+                err = _commutator(fock, dm, ovlp)
                 ev = err.reshape(-1)
-                h2 = yield torch.cat([err.abs().max().reshape(1), (torch.stack(hist + [ev]) * ev).sum(-1)])
+                h2 = yield torch.cat([err.abs().max().reshape(1), diis.gram_row(ev)])
                 emax, grow = float(h2[0]), h2[1:]
-            if purified is not None and (not np.isfinite(emax) or (it - best_it >= 40 and emax > 1e-6) or nfail >= 3
-                                         or (it + 1 >= it_end and emax > 1e-6)):
+            if purified is not None and (not scfloop.finite(emax) or progress.wandering(emax, it)
+                                         or nfail >= scfloop.MAX_PROJECTOR_FAILURES
+                                         or (it + 1 >= it_end and scfloop.far_off(emax))):
                 # The purification step has no preferred basis inside a degenerate Fermi level (open p shells, ...): every step then
                 # lands on another rotation of the degenerate orbitals, the iteration wanders for ever and the DIIS system eventually
                 # blows up (UKS SCAN on the oxygen triplet: NaN after 88 steps, or -26 Ha).  The reference diagonalises (hf.py:105-113),
                 # which fixes the orbitals: after 40 steps without progress -- or at the first non-finite error -- the loop drops the
                 # purification and starts again from the core guess with eigh steps and a fresh history
                 self.purification_dropped = True
-                purified, graphed, perr, fprev = None, None, None, None
-                fs, es, gram = [], [], np.zeros((0, 0))
+                purified = graphed = perr = fprev = None
+                diis.reset()
                 # (from the core guess again: continued from the best wandering iterate the eigh steps did not settle in 160 more
                 # iterations on that system, from the core guess they converge in 23)
-                n_ = eng.shape[-1]
-                z_ = torch.zeros((n_, n_), dtype=eng.dtype, device=eng.device)
-                dm = eng.scp2dm(eng.dm2scp(SpinParam(u=z_, d=z_) if pol else z_))
+                dm = eng.scp2dm(scfloop.core_guess_fock(eng))
                 fock = eng.dm2scp(dm)
-                best_err, best_it = float("inf"), it
+                progress = scfloop.Progress(opts["f_tol"], start=it)
                 it_end = it + 1 + int(opts["maxiter"])
                 continue
             self.scf_error = emax  # max |[F, D]| of the last iterate
-            # the commutator bottoms out at the round-off floor of the Fock build (fp64 atomics; ~1e-9 for ~200 AOs,
-            # growing with the matrix size): an iterate that is within 100 f_tol and has not improved for 8 steps ends the
-            # loop as `stalled` -- `converged` keeps meaning f_tol, `scf_error` reports what was achieved
-            if emax < best_err * 0.9:
-                best_err, best_it = emax, it
+            progress.note(emax, it)  # (AFTER the wander check above; the device loop notes before its own -- kept as found)
             # (the reference's fixed-point residual max|F_out - F_in|, kept in self.fock_residual, runs ~3x the commutator;
             # stopping on it as well -- 3e-9 or SURVEY.md 8d's 1e-8 -- saves 1-7 % of the iterations but costs a digit in the
             # non-variational energy components that the goldens pin to 1e-7: not done)
-            if emax < opts["f_tol"]:
+            if progress.converged(emax):
                 self.converged = True
                 break
-            if emax < 100 * opts["f_tol"] and it - best_it >= 8:
+            # an iterate that is within 100 f_tol and has not improved for 8 steps ends the loop as `stalled` -- `converged`
+            # keeps meaning f_tol, `scf_error` reports what was achieved
+            if progress.stalled(emax, it):
                 self.stalled = True
-                warnings.warn("SCF stopped at the round-off floor of the Fock build: max|[F,D]| = %.2e (f_tol %.1e)"
-                              % (emax, opts["f_tol"]))
+                scfloop.warn_stalled(emax, opts["f_tol"])
                 break
-            fs.append(fock)
-            es.append(ev)
-            if len(fs) > opts["history"]:
-                fs.pop(0)
-                es.pop(0)
-            m = len(fs)
-            # the Gram matrix lives on the host and grows by the row just read (broadcast-multiply-reduce on the device:
-            # the GEMM form E @ E.T hits a pathological rocBLAS path for the tall-skinny fp64 shape, 7 ms for 8 x 43264)
-            keep = m - 1  # == len(hist): the stored vectors that survive
-            gnew = np.zeros((m, m))
-            if keep:
-                gnew[:keep, :keep] = gram[-keep:, -keep:]
-            gnew[keep, :] = grow
-            gnew[:, keep] = grow
-            gram = gnew
-            if m > 1:
-                B = np.zeros((m + 1, m + 1))
-                # the Pulay coefficients do not change when the Gram block is scaled (only the multiplier does): normalised to
-                # a unit largest diagonal, otherwise lstsq's rank cut (eps x largest singular value, set by the +-1 border)
-                # discards the whole Gram block once the errors fall below ~1e-8 and the mix degrades to a plain average
-                B[:m, :m] = gram / max(float(np.max(np.diag(gram))), 1e-300) if _DIIS_SCALE else gram
-                B[m, :m] = -1
-                B[:m, m] = -1
-                rhs = np.zeros(m + 1)
-                rhs[m] = -1
-                # (m+1) x (m+1) Pulay system on the host with numpy: torch's CPU lstsq costs ~7 ms per call on a
-                # 256-thread box (thread-pool wake-up), several times the whole Fock build
-                try:
-                    c = np.linalg.lstsq(B, rhs, rcond=None)[0][:m] if np.isfinite(B).all() else None
-                except np.linalg.LinAlgError:  # (LAPACK's SVD gives up on an ill-scaled or non-finite Gram block)
-                    c = None
-                if c is None or not np.isfinite(c).all():
-                    # a Pulay system that cannot be solved: forget the history and take the plain step from this Fock matrix (the next
-                    # iterations rebuild the history; a non-finite commutator is caught at the top of the loop)
-                    fs, es, gram = [fock], [ev], np.array([[float(grow[-1])]])
-                    c = np.ones(1)
-                    m = 1
-                c = torch.as_tensor(c, dtype=fock.dtype).to(fock.device)
-                fmix = (c.reshape((-1,) + (1,) * fock.dim()) * torch.stack(fs)).sum(0)
-            else:
-                fmix = fock
-            fprev = fmix
-            if purified is not None:
-                f_out, d_out, perr = purified(fmix)
-                if purified.graph is None:  # eager step (direct SCF): fresh tensors, and the Hamiltonian's caches stay keyed on them
-                    fock, dm = f_out, d_out
-                else:  # static buffers of the graph: copy out
-                    fock, perr = f_out.clone(), perr.clone()
-                    dm = SpinParam(u=d_out.u.clone(), d=d_out.d.clone()) if pol else d_out.clone()
-            elif graphed is not None:
-                fock = graphed(eng.scp2orb(fmix)).clone()
-                dm = graphed.density_matrix().clone()
-            else:
-                dm = eng.scp2dm(fmix)
-                fock = eng.dm2scp(dm)
-        self._dm = dm
-        self._fock = fock
-        self._energy = None
-        self._has_run = True
-        if not self.accepted:  # the reference's xitorch solver emits a ConvergenceWarning here
-            warnings.warn("SCF did not converge in %d iterations: max|[F,D]| = %.2e (f_tol %.1e); energy() and "
-                          "nuclear_gradient() of this object refer to a non-stationary density"
-                          % (self.niter, self.scf_error, opts["f_tol"]))
+            fprev = diis.mix(fock, ev, grow)
+            fock, dm, perr = _take_step(eng, fprev, purified, graphed)
+        scfloop.store_result(self, fock, dm, None, opts["f_tol"])
 
     def energy(self):
         """the converged energy; differentiable (torch.autograd) with respect to the caller's positions, floating-point charges,
         efield, vext, orb_weights and the parameters of a torch.nn.Module functional (dqc_amd/autograd.py) -- when none of them
         requires grad, or grad mode is off, the plain detached tensor"""
         assert self._has_run
-        e = getattr(self, "_energy", None)  # the lockstep driver keeps dm2energy(dm) of the final Fock build (same call, same dm)
+        e = self._energy  # the lockstep and device-loop drivers keep dm2energy(dm) of the final Fock build (same call, same dm)
         if e is None:
             e = self._engine.dm2energy(self._dm)
         from . import autograd

@@ -339,6 +339,7 @@ def test_scf_driver_diis_on_a_model_problem_cpu():
     vectors must give the same answer as a damped fixed-point iteration run to convergence, in far fewer steps, for the
     restricted and the unrestricted code path (history shorter than the run, so that rows are dropped)"""
     from dqc_amd.qccalc import SCF_QCCalc
+    from dqc_amd.scfloop import Handover, drive
     from dqc_amd.utils.datastruct import SpinParam
 
     n, g = 8, 0.6
@@ -381,7 +382,8 @@ def test_scf_driver_diis_on_a_model_problem_cpu():
 
     for pol in (False, True):
         eng = Engine(pol)
-        qc = SCF_QCCalc(eng).run(fwd_options={"graph": False, "history": 4, "f_tol": 1e-11, "maxiter": 60})
+        opts = {"graph": False, "history": 4, "f_tol": 1e-11, "maxiter": 60}
+        qc = SCF_QCCalc(eng).run(fwd_options=opts)
         assert qc.accepted and qc.niter < 40
         # reference: damped fixed point to convergence
         z = torch.zeros((n, n), dtype=torch.float64)
@@ -394,6 +396,47 @@ def test_scf_driver_diis_on_a_model_problem_cpu():
             assert float((got.u - dm.u).abs().max()) < 1e-8 and float((got.d - dm.d).abs().max()) < 1e-8
         else:
             assert float((got - dm).abs().max()) < 1e-8
+        # the hand-over entry of the host loop (what the device loop leaves when it cannot finish a run, scfloop.Handover):
+        # (a) resumed from the density three iterations into an undisturbed run, (b) told to do without the purification step
+        # -- the same fixed point (1e-8 as above: both ends meet f_tol 1e-11 in the commutator), (a) in fewer iterations
+        assert not qc.purification_dropped
+        with pytest.warns(UserWarning, match="did not converge in 3 iterations"):
+            early = SCF_QCCalc(eng).run(fwd_options=dict(opts, maxiter=3)).aodm()
+        for handover, dropped in ((Handover(dm=early, projector_failures=1), False), (Handover(purification=False), True)):
+            q = SCF_QCCalc(eng)
+            drive(q._run_gen("1e", opts, handover))
+            assert q.accepted and q.purification_dropped == dropped
+            assert q.niter < qc.niter if handover.dm is not None else q.niter == qc.niter
+            new = q.aodm()
+            assert max(float((x - y).abs().max()) for x, y in (((new.u, got.u), (new.d, got.d)) if pol else ((new, got),))) < 1e-8
+
+
+def test_scf_progress_record_on_hand_made_error_sequences():
+    """scfloop.Progress, the convergence policy the three SCF drivers share: converged below f_tol; stalled within 100 f_tol
+    after 8 steps without progress (an error counts as progress below 0.9 x the best); wandering after 40 such steps above 1e-6"""
+    from dqc_amd import scfloop
+
+    def first(question, errs, f_tol=1e-9):
+        p = scfloop.Progress(f_tol)
+        for it, e in enumerate(errs):
+            p.note(e, it)
+            if getattr(p, question)(*((e,) if question == "converged" else (e, it))):
+                return it
+        return None
+
+    falling = [10.0 ** -k for k in range(12)]
+    assert first("converged", falling) == 10 and first("stalled", falling) is None and first("wandering", falling) is None
+    assert first("converged", [1e-9] * 3) is None  # (strictly below f_tol)
+    # flat at 5e-8 (within 100 f_tol) from step 8 on: the best is noted at step 8, stalled 8 steps later; 0.95 x is no progress
+    flat = falling[:8] + [5e-8] + [5e-8 * 0.95] * 20
+    assert first("stalled", flat) == 16 and first("converged", flat) is None
+    assert first("stalled", falling[:7] + [2e-7] * 60) is None   # flat, but outside 100 f_tol: never stalled
+    assert first("stalled", flat, f_tol=1e-10) is None
+    # flat at 1e-3 from step 3 on: wandering 40 steps after the last progress; at 1e-6 exactly it is not
+    assert first("wandering", falling[:3] + [1e-3] * 60) == 43 and first("stalled", falling[:3] + [1e-3] * 60) is None
+    assert first("wandering", falling[:6] + [1e-6] * 60) is None
+    assert scfloop.projector_failed(1e-9) and scfloop.projector_failed(float("nan")) and not scfloop.projector_failed(9e-10)
+    assert scfloop.finite(1.0) and not scfloop.finite(float("nan")) and not scfloop.finite(float("inf"))
 
 
 def test_xc_combinators_keep_every_valgrad_field_and_spin():
