@@ -222,7 +222,7 @@ __global__ __launch_bounds__(FT_NT) void fock_xd_kernel(double *__restrict__ t_o
 }
 
 // ---------------------------------------------------------------------------------------------
-// combine.  M = (Wj + Wj^T) - (Wk + Wk^T) / 2 + V  (AO basis) -> scratch m (npad-strided); the two energy traces
+// combine.  M = (Wj + Wj^T) - a (Wk + Wk^T) / 2 + V  (AO basis; a = 1 for Hartree-Fock, a hybrid functional's fraction otherwise) -> scratch m (npad-strided); the two energy traces
 // en[0] = 1/2 sum D_ao J, en[1] = -1/4 sum D_ao K: per-block partial sums in a fixed order, the LAST block to arrive (atomic ticket)
 // adds the partials up in block order -- bit-reproducible.  jout (nao x nao, optional) <- J.
 // D_ao is bitwise symmetric (fock_dao_kernel), so sum_ij D_ij (W_ij + W_ji) = 2 sum_ij D_ij W_ij: no transposed read for the traces.
@@ -231,11 +231,14 @@ constexpr int FC_NB = 64;  // blocks
 
 // HAS_V: 0 no V, 1 a symmetric AO matrix, 2 the RAW cross-block sums of dqc_grid_vxc_raw (V = (M + M^T) / 2; fixed-point integers of
 // scale vscale in deterministic mode)
-template <bool DET, bool WITH_K, int HAS_V>
+// WITH_K: 0 no K, 1 Hartree-Fock (M = J - K / 2 + V), 2 a hybrid functional's exact-exchange fraction `kfrac` from the kernel
+// argument (M = J - kfrac K / 2 + V, en[1] = -kfrac / 4 sum D_ao K, en[2] = *excp, the E_xc quadrature handed through)
+template <bool DET, int WITH_K, int HAS_V>
 __global__ __launch_bounds__(FT_NT) void fock_combine_kernel(double *__restrict__ m, double *__restrict__ en, double *__restrict__ jout,
                                                              const double *__restrict__ work, const double *__restrict__ v, int ldv, int nao,
                                                              int npad, const double *__restrict__ dscp, double *__restrict__ part,
-                                                             unsigned *__restrict__ ticket, double vscale) {
+                                                             unsigned *__restrict__ ticket, double vscale, double kfrac,
+                                                             const double *__restrict__ excp) {
     __shared__ double red[2][FT_WAVES];
     __shared__ bool last;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -272,7 +275,7 @@ __global__ __launch_bounds__(FT_NT) void fock_combine_kernel(double *__restrict_
                 sj += d[u] * j1;
                 if (WITH_K) {
                     const double k1 = dval(ka[u]);
-                    mv -= 0.5 * (k1 + dval(kb[u]));
+                    mv -= (WITH_K == 2 ? 0.5 * kfrac : 0.5) * (k1 + dval(kb[u]));
                     sk += d[u] * k1;
                 }
                 if (HAS_V == 1) mv += vv[u];
@@ -308,6 +311,10 @@ __global__ __launch_bounds__(FT_NT) void fock_combine_kernel(double *__restrict_
         }
         en[0] = a;          // = 1/2 . 2 sum D W
         en[1] = -0.5 * b;   // = -1/4 . 2 sum D W
+        if (WITH_K == 2) {
+            en[1] = -0.5 * kfrac * b;
+            en[2] = excp ? *excp : 0.0;
+        }
         *ticket = 0u;       // (ready for the next launch on this work buffer)
     }
 }
@@ -434,7 +441,8 @@ int dqc_fock_prep(double *d_work, const double *d_dm, const double *d_x, const d
 }
 
 static int fock_finish_impl(double *d_fock, double *d_energies, double *d_j_ao, double *d_work, const double *d_vxc_ao, int ldv,
-                            const double *d_core, const double *d_x, int nao, int north, int with_k, int vraw, double vscale, void *stream);
+                            const double *d_core, const double *d_x, int nao, int north, int with_k, int vraw, double vscale, void *stream, double kfrac = 1.0,
+                            const double *d_exc = nullptr);
 
 int dqc_fock_finish(double *d_fock, double *d_energies, double *d_j_ao, double *d_work, const double *d_vxc_ao, int ldv,
                     const double *d_core, const double *d_x, int nao, int north, int with_k, void *stream) {
@@ -448,8 +456,18 @@ int dqc_fock_finish_vraw(double *d_fock, double *d_energies, double *d_work, con
     return fock_finish_impl(d_fock, d_energies, nullptr, d_work, d_vxc_raw, ldv, d_core, d_x, nao, north, 0, 1, vscale, stream);
 }
 
+int dqc_fock_finish_hybrid(double *d_fock, double *d_energies, double *d_work, const double *d_vxc, int ldv, int vraw, double vscale,
+                           double kfrac, const double *d_exc, const double *d_core, const double *d_x, int nao, int north, void *stream) {
+    // the hybrid Kohn-Sham finish: J and K accumulators of a with_k tile pass, V either symmetric (vraw = 0) or the raw sums of
+    // dqc_grid_vxc_raw (vraw = 1, vscale what that call returned); kfrac = the functional's exact-exchange fraction (a run-time value)
+    if (!d_vxc) { dqc::set_error("dqc_fock_finish_hybrid: null Vxc matrix"); return DQC_EINVAL; }
+    if (!(kfrac == kfrac)) { dqc::set_error("dqc_fock_finish_hybrid: the exchange fraction is not a number"); return DQC_EINVAL; }
+    return fock_finish_impl(d_fock, d_energies, nullptr, d_work, d_vxc, ldv, d_core, d_x, nao, north, 2, vraw ? 1 : 0, vscale, stream, kfrac, d_exc);
+}
+
 static int fock_finish_impl(double *d_fock, double *d_energies, double *d_j_ao, double *d_work, const double *d_vxc_ao, int ldv,
-                            const double *d_core, const double *d_x, int nao, int north, int with_k, int vraw, double vscale, void *stream) {
+                            const double *d_core, const double *d_x, int nao, int north, int with_k, int vraw, double vscale, void *stream,
+                            double kfrac, const double *d_exc) {
     using namespace dqc;
     if (nao <= 0) return DQC_OK;
     if (nao > dqc_fock_max_nao() || north > nao || north <= 0) { set_error("dqc_fock_finish: needs 0 < north <= nao <= 1024"); return DQC_EINVAL; }
@@ -463,17 +481,20 @@ static int fock_finish_impl(double *d_fock, double *d_energies, double *d_j_ao, 
     double *d_m = d_work + 3 * n2 + 8, *d_t = d_work + 4 * n2 + 8, *d_part = d_work + 5 * n2 + 8;
     // (the ticket is zero when the kernel starts: dqc_fock_prep, which every build runs first on this buffer, resets it)
 #define DQC_FK_COMBINE(D, K, V) \
-    hipLaunchKernelGGL((fock_combine_kernel<D, K, V>), dim3(FC_NB), dim3(FT_NT), 0, st, d_m, d_energies, d_j_ao, d_work, d_vxc_ao, ldv, nao, npad, dscp, d_part, ticket, vscale);
+    hipLaunchKernelGGL((fock_combine_kernel<D, K, V>), dim3(FC_NB), dim3(FT_NT), 0, st, d_m, d_energies, d_j_ao, d_work, d_vxc_ao, ldv, nao, npad, dscp, d_part, ticket, vscale, kfrac, d_exc);
     const bool det = dscp != nullptr, wk_ = with_k != 0, hv = d_vxc_ao != nullptr;
     if (vraw && (vscale != 0.0) != det) { set_error("dqc_fock_finish_vraw: the scale does not match the deterministic mode"); return DQC_EINVAL; }
-    if (vraw) {
-        if (det) DQC_FK_COMBINE(true, false, 2) else DQC_FK_COMBINE(false, false, 2)
+    if (with_k == 2) {  // hybrid: K scaled by the run-time fraction, V always there (checked by dqc_fock_finish_hybrid)
+        if (vraw) { if (det) DQC_FK_COMBINE(true, 2, 2) else DQC_FK_COMBINE(false, 2, 2) }
+        else { if (det) DQC_FK_COMBINE(true, 2, 1) else DQC_FK_COMBINE(false, 2, 1) }
+    } else if (vraw) {
+        if (det) DQC_FK_COMBINE(true, 0, 2) else DQC_FK_COMBINE(false, 0, 2)
     } else if (det) {
-        if (wk_) { if (hv) DQC_FK_COMBINE(true, true, 1) else DQC_FK_COMBINE(true, true, 0) }
-        else { if (hv) DQC_FK_COMBINE(true, false, 1) else DQC_FK_COMBINE(true, false, 0) }
+        if (wk_) { if (hv) DQC_FK_COMBINE(true, 1, 1) else DQC_FK_COMBINE(true, 1, 0) }
+        else { if (hv) DQC_FK_COMBINE(true, 0, 1) else DQC_FK_COMBINE(true, 0, 0) }
     } else {
-        if (wk_) { if (hv) DQC_FK_COMBINE(false, true, 1) else DQC_FK_COMBINE(false, true, 0) }
-        else { if (hv) DQC_FK_COMBINE(false, false, 1) else DQC_FK_COMBINE(false, false, 0) }
+        if (wk_) { if (hv) DQC_FK_COMBINE(false, 1, 1) else DQC_FK_COMBINE(false, 1, 0) }
+        else { if (hv) DQC_FK_COMBINE(false, 0, 1) else DQC_FK_COMBINE(false, 0, 0) }
     }
 #undef DQC_FK_COMBINE
     DQC_CHECK_LAUNCH();

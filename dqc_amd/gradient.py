@@ -10,7 +10,8 @@ same derivative is the Hellmann-Feynman + Pulay expression -- no response equati
             + dE_xc/dR_A                                           LDA and GGA, INCLUDING the grid response
             + dE_nn/dR_A
 
-Restricted and unrestricted (UHF / UKS: J from the total density, exchange and XC spin by spin).  The XC part
+Restricted and unrestricted (UHF / UKS: J from the total density, exchange and XC spin by spin); hybrid functionals scale the
+exchange part of the two-electron term by their exact-exchange fraction (k = a).  The XC part
 differentiates the discretised functional E_xc = sum_g w_g(R) e(rho_s(r_g(R))) exactly, as the reference's autograd does:
 (i) Becke-weight derivative (torch autograd through dqc_amd.grid's own weight code, e_g held fixed), and for every spin,
 with b = Phi D_s, c_i = d_i Phi D_s, u = the gradient part of the potential (`vgrad` of dqc_xc_eval*), S_j = sum_i u_i d_i d_j Phi:
@@ -79,6 +80,15 @@ def nuclear_gradient(qc) -> torch.Tensor:
     lib.int1e_grad(grad, tocart(d_tot), tocart(w_ao), h._tab, h._zs)
     if h.df is not None:
         _df_coulomb_gradient(h, d_tot, grad)
+    elif eng.is_ks and getattr(eng, "exx", 0.0) != 0.0:
+        # hybrid functional, exact-exchange fraction a: the Hartree-Fock two-electron term with the exchange scaled by a
+        a = float(eng.exx)
+        if not pol:
+            lib.eri_grad(grad, tocart(d_tot), a, h._tab)
+        else:  # J from the total density, -a K[D_s] spin by spin
+            lib.eri_grad(grad, tocart(d_tot), 0.0, h._tab)
+            for d in d_aos:
+                lib.eri_grad(grad, tocart(d), 2.0 * a, h._tab, jscale=0.0)
     elif eng.is_ks:
         lib.eri_grad(grad, tocart(d_tot), 0.0, h._tab)
     elif not pol:

@@ -25,7 +25,7 @@ from . import lib
 from .basis import make_tables
 from .linop import LinearOperator
 from .utils.datastruct import AtomCGTOBasis, SpinParam, ValGrad
-from .xc import LibXC
+from .xc import LibXC, exx_fraction_of
 
 # Coulomb side streams (round 6, dqc_amd.batch.CuPartition): a Fock build that runs on a registered "grid" stream sends its
 # Coulomb pass over the ERI tiles to the stream registered beside it -- a HIP stream confined to OTHER compute units
@@ -76,8 +76,8 @@ class _Factor:
         self.orb, self.w, self.pairs = orb, w, pairs
 
 
-# the two-electron energies that fall out of a Fock build (None: not formed by it)
-_Energies = namedtuple("_Energies", "j xc k", defaults=(None, None, None))
+# the two-electron energies that fall out of a Fock build (None: not formed by it); ka: a E_K of a hybrid build, a its fraction
+_Energies = namedtuple("_Energies", "j xc k ka", defaults=(None, None, None, None))
 
 
 try:  # inside a DQC installation the class IS a BaseHamilton (isinstance checks of dqc.qccalc / dqc.system pass)
@@ -158,6 +158,7 @@ class HamiltonMI355(_Base):
         # two-electron energies of the last build, and the orbital factors of the last two ao_orb2dm results (the spin-up and
         # spin-down matrices of an unrestricted iteration); per weight tensor: the last two occupation checks
         self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors = _Memo(), _Memo(), _Memo(), _Memo(2)
+        self._hybpol_memo = _Memo()  # a E_K of the last unrestricted hybrid build
         self._w_checked = _Memo(2)
         # which density kernel the grid passes took: "factor" (rank-n_occ kernel, D = ao_orb2dm(...) recognised), "dense" (anonymous
         # full matrix: 0.84 instead of 0.50 ms on a 20-atom molecule).  A caller that forms more than two density matrices before
@@ -166,7 +167,7 @@ class HamiltonMI355(_Base):
 
     def clear_memos(self):
         """forget what was remembered per density matrix (a graph capture's tensors belong to its private pool)"""
-        for m in (self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors):
+        for m in (self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors, self._hybpol_memo):
             m.clear()
 
     # ------------------------------------------------------------------ properties
@@ -252,6 +253,8 @@ class HamiltonMI355(_Base):
                               "free: direct SCF (integrals re-evaluated in every Fock build, no hipGraph / lockstep step); "
                               "DQC_AMD_ERI=tiles insists on the store" % (tab.nao, need / 1e9, free / 1e9))
             self.eri_mode_used = mode
+            if self._direct and self.xc is not None:
+                self._check_hybrid(exx_fraction_of(self.xc))
         if self._df is None and self._direct:
             # direct SCF: no tile store; every J / K call re-evaluates the shell quartets -- those the
             # Schwarz bounds do not rule out (dqc_direct_*: tables and bounds stay on the device)
@@ -296,6 +299,7 @@ class HamiltonMI355(_Base):
         family = 1 if xc is None else xc.family
         if family not in (1, 2, 4):
             raise RuntimeError("unknown xc family %s" % family)
+        self._check_hybrid(exx_fraction_of(xc))
         if self.is_grid_set and getattr(self, "grid", None) is grid and family == self.xcfamily:
             if xc is not self.xc:  # another functional on the resident AO values: what was remembered of the old one goes
                 self._energy_memo.clear()
@@ -340,6 +344,25 @@ class HamiltonMI355(_Base):
         self.is_grad_ao_set = deriv >= 1
         self.is_lapl_ao_set = deriv == 2
         self._ao_lapl_pm = None
+
+    def _check_hybrid(self, a):
+        """what a functional with the exact-exchange fraction `a` cannot be combined with (raises)"""
+        if a == 0.0:
+            return
+        if self._df is not None:
+            raise NotImplementedError("hybrid functionals (exact-exchange fraction %g) cannot be used with density fitting: "
+                                      "Mol.densityfit() fits the Coulomb operator J only, there is no fitted exchange" % a)
+        if self._pworld > 1:
+            raise NotImplementedError("hybrid functionals (exact-exchange fraction %g) on a Hamiltonian sharded over several GPUs "
+                                      "(shard_over) are not implemented" % a)
+        if self._eri_mode == "direct" or (self.is_built and self._direct):
+            raise NotImplementedError("hybrid functionals (exact-exchange fraction %g) with direct SCF (DQC_AMD_ERI=direct) are not "
+                                      "implemented: the incremental J / K builds are not wired to the hybrid Fock build" % a)
+
+    @property
+    def exx_fraction(self):
+        """the exact-exchange fraction of the functional given to setup_grid (0.0: a pure functional, or none)"""
+        return exx_fraction_of(self.xc)
 
     def grid_select(self, x):
         """a per-point array on the caller's grid (last axis ngrid_full) -> the same on the resident (live) points"""
@@ -1039,6 +1062,88 @@ class HamiltonMI355(_Base):
         self._energy_memo.put(_Energies(j=0.5 * (dao * J).sum(), k=-0.25 * (dao * K).sum()), dm)
         mat = self._sym_orth(J - 0.5 * K)
         return mat if core is None else core + mat
+
+    def get_elrep_plus_exchange_plus_vxc(self, dm, core=None):
+        """J[D] - a K[D] / 2 + Vxc[D] of ONE restricted density matrix as a plain tensor in the orthogonalised basis: the
+        two-electron part of a HYBRID Kohn-Sham Fock matrix, a = the exact-exchange fraction of the functional given to setup_grid
+        (get_elrep(dm) + a get_exchange(dm) + get_vxc(dm) up to round-off).  The J + K pass over the ERI tiles runs on a second
+        stream beside the density / XC / Vxc grid passes (in line inside a graph capture); the ends are the fused kernels of
+        csrc/fock.hip, the last of them dqc_fock_finish_hybrid: X^T (J - a K / 2 + V) X + core and the traces E_J, a E_K."""
+        a = self.exx_fraction
+        assert self.xc is not None and dm.dim() == 2
+        self._check_hybrid(a)
+        n = self._nao_ao
+        fac = self._factor_of(dm)
+        if self._fused_build_ok(dm):
+            x, work, tiles = self._orthozer, self._jkwork, self._tiles
+            side = self._coulomb_side(dm.device, own=True)
+            self._prep(work, dm, fac, True)
+            self._beside(side, lambda: lib.jk_stream_prepared(tiles, n, work, True))
+            potinfo, exc = self._vxc_exc(self._dm2densinfo(dm))
+            if self.xcfamily != 4:
+                vg = potinfo.grad if self.xcfamily == 2 else None
+                vm, vsc = lib.grid_vxc_raw(self._ao, n, self.dvolume, potinfo.value.contiguous(), None if vg is None else vg.contiguous())
+            else:
+                vm, vsc = self._vxc_ao_from_potinfo(potinfo), None
+            self._rejoin(side)
+            mat, en = lib.fock_finish_hybrid(work, x, n, a, vm, vscale=vsc, exc=exc, core=core)
+            self._energy_memo.put(_Energies(j=en[0], xc=None if exc is None else en[2], ka=en[1]), dm)
+            return mat
+        # the torch form of the same sum (DQC_AMD_FUSED_FOCK=0, an anonymous or strided input): what the fused kernels are tested against
+        dao = self._unconvert_dm(dm)
+        side = self._coulomb_side(dm.device, own=True)
+        jk = self._beside(side, lambda: self._jk_ao(dao, True), dao)
+        potinfo, exc = self._vxc_exc(self._dm2densinfo(dm))
+        vm = self._vxc_ao_from_potinfo(potinfo)
+        self._rejoin(side, jk[0])
+        self._rejoin(side, jk[1])
+        self._energy_memo.put(_Energies(j=0.5 * (dao * jk[0]).sum(), xc=None if exc is None else exc[0],
+                                        ka=-0.25 * a * (dao * jk[1]).sum()), dm)
+        mat = self._sym_orth(jk[0] - (0.5 * a) * jk[1] + vm[:n, :n])
+        return mat if core is None else core + mat
+
+    def get_elrep_plus_exchange_plus_vxc_pol(self, dm: SpinParam, core=None):
+        """the unrestricted form: stacked (2, nao, nao)  J[D_u + D_d] - a K[D_s] + Vxc_s[D_u, D_d]  (a get_exchange(dm) is -a K[2 D_s] / 2
+        = -a K[D_s] per spin, hcgto.py:238-241).  J and the two K from ONE pass over the tiles (dqc_jk_from_tiles_multi) on a second
+        stream beside the two-spin grid pass, one batched AO -> orthogonal conversion of the two sums"""
+        a = self.exx_fraction
+        assert self.xc is not None and dm.u.dim() == 2 and self.tiles_resident
+        self._check_hybrid(a)
+        n, x = self._nao_ao, self._orthozer
+        fu, fd = self._factor_of(dm.u), self._factor_of(dm.d)
+        one = fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1
+        side = self._coulomb_side(dm.u.device, own=True)
+        tiles = self._tiles
+
+        def jk():
+            if one:
+                ds = torch.stack([(fu[0][0] @ fu[0][1])[:n, :n], (fd[0][0] @ fd[0][1])[:n, :n]])
+            else:
+                ds = self._unconvert_dm(torch.stack([dm.u, dm.d]))
+                ds = (ds + ds.transpose(-2, -1)) * 0.5
+            return (ds,) + lib.jk_multi(tiles, (ds[0] + ds[1]).unsqueeze(0), ds, self._multi_work(1, 2))
+
+        ds, jao, kao = self._beside(side, jk)
+        potinfo = self.xc.get_vxc(self._dm2densinfo_pol(dm))
+        vu = self._vxc_ao_from_potinfo(potinfo.u)
+        vd = self._vxc_ao_from_potinfo(potinfo.d)
+        for t in (ds, jao, kao):
+            self._rejoin(side, t)
+        # the exchange energy of this pair falls out of the build: E_K = -a / 2 sum_s tr D_s K[D_s]  (remembered per pair)
+        self._hybpol_memo.put(-0.5 * a * (ds * kao).sum(), dm.u, dm.d)
+        mat = x.transpose(-2, -1) @ torch.stack([jao[0] - a * kao[0] + vu[:n, :n], jao[0] - a * kao[1] + vd[:n, :n]]) @ x
+        mat = (mat + mat.transpose(-2, -1)) * 0.5
+        return mat if core is None else core + mat
+
+    def get_e_exchange_hybrid(self, dm):
+        """a E_K: the exact-exchange energy of a hybrid functional, get_e_exchange(dm) scaled by the functional's fraction (a by-product
+        of the last hybrid build of `dm` when there was one)"""
+        a = self.exx_fraction
+        if isinstance(dm, SpinParam):
+            e = self._hybpol_memo.get(dm.u, dm.d)
+            return e if e is not None else a * self.get_e_exchange(dm)
+        e = self._memo_energy(dm, "ka")
+        return e if e is not None else a * self.get_e_exchange(dm)
 
     def timed_fock_kernels(self, dm, core):
         """measurement aid (bench.py): the restricted KS Fock build `core + get_elrep_plus_vxc(dm)` -- its own body, on this stream --

@@ -119,6 +119,8 @@ def load():
     lib.dqc_fock_prep.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_int, c_int, c_vp]
     lib.dqc_jk_stream_prepared.argtypes = [c_dp, c_int, c_dp, c_int, c_vp]
     lib.dqc_fock_finish.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_dp, c_int, c_int, c_int, c_vp]
+    lib.dqc_fock_finish_hybrid.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.c_double, ctypes.c_double, c_dp, c_dp, c_dp, c_int,
+                                           c_int, c_vp]
     lib.dqc_padded_norb.argtypes = [c_int]
     lib.dqc_padded_norb.restype = c_int
     lib.dqc_grid_density_lr.argtypes = [c_dp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp, c_int, c_vp]
@@ -1025,6 +1027,20 @@ def fock_finish_vraw(work, x, nao, vxc_raw, vscale, core=None):
     with _on(work.device) as st_:
         _check(load().dqc_fock_finish_vraw(_ptr(fock), _ptr(en), _ptr(work), _ptr(vxc_raw), int(vxc_raw.shape[-1]), float(vscale), _ptr(core),
                                            _ptr(x), int(nao), int(north), st_), "dqc_fock_finish")
+    return fock, en
+
+
+def fock_finish_hybrid(work, x, nao, kfrac, vxc, vscale=None, exc=None, core=None):
+    """the finish of a hybrid Kohn-Sham build -> fock (north, north) = sym(X^T (J - kfrac K / 2 + V) X) + core, energies (3,) =
+    [tr D J / 2, -kfrac tr D K / 4, E_xc handed through from the (1,) tensor `exc`].  `vxc`: the raw sums of grid_vxc_raw with their
+    `vscale`, or (vscale None) a symmetric AO-basis matrix"""
+    north = x.shape[1]
+    fock = torch.empty((north, north), dtype=torch.float64, device=work.device)
+    en = torch.empty(3, dtype=torch.float64, device=work.device)
+    with _on(work.device) as st_:
+        _check(load().dqc_fock_finish_hybrid(_ptr(fock), _ptr(en), _ptr(work), _ptr(vxc), int(vxc.shape[-1]), 0 if vscale is None else 1,
+                                             0.0 if vscale is None else float(vscale), float(kfrac), _ptr(exc), _ptr(core), _ptr(x),
+                                             int(nao), int(north), st_), "dqc_fock_finish_hybrid")
     return fock, en
 
 

@@ -19,7 +19,7 @@ import torch
 
 from . import scfloop
 from .utils.datastruct import SpinParam
-from .xc import get_xc
+from .xc import exx_fraction_of, get_xc
 
 
 _DIIS_SCALE = os.environ.get("DQC_AMD_DIIS_SCALE", "1") != "0"
@@ -31,6 +31,9 @@ class _Engine:
         self.hamilton = system.get_hamiltonian()
         self.is_ks = is_ks
         self.xc = get_xc(xc) if is_ks else None
+        # exact-exchange fraction of a hybrid functional, read ONCE as a float (not a trainable parameter); 0.0: every path below is
+        # the pure Kohn-Sham / Hartree-Fock one
+        self.exx = exx_fraction_of(self.xc) if is_ks else 0.0
         # hf.py:49-53: polarised iff spin != 0 unless `restricted` says otherwise
         self.polarized = bool(system.spin != 0) if restricted is None else (not restricted)
         # spin != 0 with restricted=True: one set of orbitals with occupations [2, ..., 2, 1, ..., 1] (mol.py:421-443) -- the
@@ -83,6 +86,8 @@ class _Engine:
 
     # Fock build -- THE hot path (hf.py:182-201, ks.py:176-187)
     def dm2scp(self, dm):
+        if self.exx != 0.0:
+            return self._dm2scp_hybrid(dm)
         if self.polarized:  # scp = stacked (F_u, F_d)  (hf.py:93-103)
             if not isinstance(dm, SpinParam):
                 dm = SpinParam(u=dm[0], d=dm[1])
@@ -111,6 +116,22 @@ class _Engine:
             fock = self.knvext + elrep + self.hamilton.get_exchange(dm)
         return fock.fullmatrix()
 
+    def _dm2scp_hybrid(self, dm):
+        """F = h + J + a get_exchange(D) + Vxc[D], a = self.exx: one fused build (hamilton.py: get_elrep_plus_exchange_plus_vxc and its
+        unrestricted form); batched densities through the operators' own sum"""
+        h, a = self.hamilton, self.exx
+        if self.polarized:
+            if not isinstance(dm, SpinParam):
+                dm = SpinParam(u=dm[0], d=dm[1])
+            if dm.u.dim() == 2:
+                return h.get_elrep_plus_exchange_plus_vxc_pol(dm, core=self._core_matrix())
+            core = self.knvext + h.get_elrep(dm.u + dm.d)
+            v, k = h.get_vxc(dm), h.get_exchange(dm)
+            return torch.stack([(core + v.u).fullmatrix() + a * k.u.fullmatrix(), (core + v.d).fullmatrix() + a * k.d.fullmatrix()])
+        if dm.dim() == 2:
+            return h.get_elrep_plus_exchange_plus_vxc(dm, core=self._core_matrix())
+        return (self.knvext + h.get_elrep(dm) + h.get_vxc(dm)).fullmatrix() + a * h.get_exchange(dm).fullmatrix()
+
     def scp2dm(self, scp):
         if self.polarized:
             out = []
@@ -132,9 +153,13 @@ class _Engine:
         if self.polarized:  # hf.py:166-172 / ks.py:157-166 with dmtot = dm.u + dm.d
             tot = dm.u + dm.d
             e = h.get_e_hcore(tot) + h.get_e_elrep(tot) + (h.get_e_xc(dm) if self.is_ks else h.get_e_exchange(dm))
+            if self.exx != 0.0:
+                e = e + h.get_e_exchange_hybrid(dm)
             return e + self._enuc
         e = h.get_e_hcore(dm) + h.get_e_elrep(dm)
         e = e + (h.get_e_xc(dm) if self.is_ks else h.get_e_exchange(dm))
+        if self.exx != 0.0:  # a E_K of the hybrid functional (a by-product of the build of this density)
+            e = e + h.get_e_exchange_hybrid(dm)
         return e + self._enuc
 
     def energy_parts(self, dm):
@@ -143,6 +168,8 @@ class _Engine:
         p = {"e_core": float(h.get_e_hcore(tot)), "e_elrep": float(h.get_e_elrep(tot)),
              "e_nuc": float(self._system.get_nuclei_energy())}
         p["e_xc" if self.is_ks else "e_exch"] = float(h.get_e_xc(dm) if self.is_ks else h.get_e_exchange(dm))
+        if self.exx != 0.0:
+            p["e_exch"] = float(h.get_e_exchange_hybrid(dm))
         p["e_tot"] = sum(p.values())
         return p
 

@@ -3,7 +3,12 @@
 `get_xc("lda_x + gga_c_pbe")` (dqc/api/getxc.py:38-59).  Functional evaluation runs in the HIP kernel
 dqc_xc_eval (csrc/xc.hip) for trees made of the supported libxc names; any other object exposing the
 BaseXC methods (e.g. a user CustomXC, dqc/xc/custom_xc.py:7-25) is called as-is on device tensors by the
-Hamiltonian."""
+Hamiltonian.
+
+Hybrid functionals: an object may carry `exx_fraction`, the fraction a of exact (Hartree-Fock) exchange that the SCF adds to the
+grid part, F = h + J - a K / 2 + Vxc.  `get_xc` knows "hyb_gga_xc_pbeh" (alias "pbe0"), "hyb_gga_xc_b3lyp5" and the general
+spelling "0.25 * hf + 0.75 * gga_x_pbe + gga_c_pbe", in which the pseudo-term `hf` has no grid part and adds its coefficient to
+the fraction.  The fraction is read ONCE, as a float, when the calculation is set up: it is not a trainable parameter."""
 import re
 
 import torch
@@ -17,7 +22,25 @@ _FAMILY = {"lda_x": 1, "lda_c_pw": 1, "lda_c_pw_mod": 1, "lda_c_vwn": 1, "gga_x_
            "gga_x_pw91": 2, "gga_x_b86": 2, "gga_x_g96": 2, "gga_x_pw86": 2, "gga_x_optx": 2, "gga_x_wc": 2, "lda_c_pz": 1, "gga_c_p86": 2}
 
 
+# hybrids by name: (terms of the grid part, fraction of exact exchange)
+_HYBRIDS = {
+    "hyb_gga_xc_pbeh": ([(0.75, "gga_x_pbe"), (1.0, "gga_c_pbe")], 0.25),
+    # lda_c_vwn of the kernel set is VWN5: this is libxc's hyb_gga_xc_b3lyp5 (hyb_gga_xc_b3lyp proper uses lda_c_vwn_rpa)
+    "hyb_gga_xc_b3lyp5": ([(0.08, "lda_x"), (0.72, "gga_x_b88"), (0.19, "lda_c_vwn"), (0.81, "gga_c_lyp")], 0.20),
+}
+_HYBRIDS["pbe0"] = _HYBRIDS["hyb_gga_xc_pbeh"]
+
+
+def exx_fraction_of(xc):
+    """the exact-exchange fraction of a functional object as a float (0.0 for None and for objects without the attribute)"""
+    return float(getattr(xc, "exx_fraction", 0.0) or 0.0)
+
+
 class BaseXC:
+    # fraction of exact exchange the SCF adds to this functional's grid part; a subclass (torch.nn.Module ones included) may set it.
+    # Read as a float when the calculation is set up: not a trainable parameter
+    exx_fraction = 0.0
+
     @property
     def family(self):
         raise NotImplementedError
@@ -29,12 +52,13 @@ class BaseXC:
         raise NotImplementedError
 
     def __add__(self, other):
-        return LibXC(self.terms + other.terms) if isinstance(self, LibXC) and isinstance(other, LibXC) \
-            else _SumXC(self, other)
+        if isinstance(self, LibXC) and isinstance(other, LibXC):
+            return LibXC(self.terms + other.terms, exx_fraction_of(self) + exx_fraction_of(other))
+        return _SumXC(self, other)
 
     def __mul__(self, f):
         if isinstance(self, LibXC):
-            return LibXC([(c * float(f), n) for c, n in self.terms])
+            return LibXC([(c * float(f), n) for c, n in self.terms], exx_fraction_of(self) * float(f))
         return _MulXC(self, f)
 
     __rmul__ = __mul__
@@ -46,8 +70,10 @@ class BaseXC:
 class LibXC(BaseXC):
     """weighted sum of libxc functionals evaluated by the fused HIP kernel (unpolarised)"""
 
-    def __init__(self, terms):
+    def __init__(self, terms, exx_fraction=0.0):
         self.terms = list(terms)
+        if exx_fraction:  # (pure functionals keep the class attribute 0.0)
+            self.exx_fraction = float(exx_fraction)
         for _, n in self.terms:
             if n not in _FAMILY:
                 raise ValueError("libxc functional %s is not available in dqc_amd (supported: %s)"
@@ -165,6 +191,7 @@ class LibXC(BaseXC):
 class _SumXC(BaseXC):
     def __init__(self, a, b):
         self.a, self.b = a, b
+        self.exx_fraction = exx_fraction_of(a) + exx_fraction_of(b)
 
     @property
     def family(self):
@@ -182,6 +209,7 @@ class _SumXC(BaseXC):
 class _MulXC(BaseXC):
     def __init__(self, a, f):
         self.a, self.f = a, f
+        self.exx_fraction = exx_fraction_of(a) * float(f)
 
     @property
     def family(self):
@@ -200,15 +228,28 @@ def get_libxc(name):
 
 
 def get_xc(xcstr):
-    """"lda_x + gga_c_pbe", "0.7*lda_x" ... ; None -> zero functional (reference ks.py:59-60 accepts None)"""
+    """"lda_x + gga_c_pbe", "0.7*lda_x" ... ; None -> zero functional (reference ks.py:59-60 accepts None).
+    Hybrids: "hyb_gga_xc_pbeh" / "pbe0" (0.75 gga_x_pbe + gga_c_pbe, a = 0.25), "hyb_gga_xc_b3lyp5" (0.08 lda_x + 0.72 gga_x_b88
+    + 0.19 lda_c_vwn + 0.81 gga_c_lyp, a = 0.20 -- the VWN5 variant of B3LYP, libxc's b3lyp5: lda_c_vwn here is VWN5), and the
+    pseudo-term `hf` ("0.25 * hf + 0.75 * gga_x_pbe + gga_c_pbe"), whose coefficient is added to the result's `exx_fraction`"""
     if xcstr is None:
         return LibXC([])
     if isinstance(xcstr, BaseXC) or hasattr(xcstr, "get_vxc"):
         return xcstr
-    terms = []
+    terms, exx = [], 0.0
     for tok in xcstr.replace(" ", "").split("+"):
         m = re.fullmatch(r"(?:([0-9.eE+-]+)\*)?([a-zA-Z0-9_]+)", tok)
         if m is None:
             raise ValueError("cannot parse xc term: %s" % tok)
-        terms.append((float(m.group(1)) if m.group(1) else 1.0, m.group(2).lower()))
-    return LibXC(terms)
+        c, name = (float(m.group(1)) if m.group(1) else 1.0), m.group(2).lower()
+        if name == "hf":
+            exx += c
+        elif name in _HYBRIDS:
+            terms += [(c * ct, n) for ct, n in _HYBRIDS[name][0]]
+            exx += c * _HYBRIDS[name][1]
+        elif name in ("hyb_gga_xc_b3lyp", "b3lyp"):
+            raise ValueError("%s needs lda_c_vwn_rpa, which dqc_amd does not have; the VWN5 variant is available as "
+                             "hyb_gga_xc_b3lyp5" % name)
+        else:
+            terms.append((c, name))
+    return LibXC(terms, exx)

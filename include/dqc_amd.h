@@ -122,6 +122,14 @@ int dqc_fock_finish_vraw(double *d_fock, double *d_energies, double *d_work, con
                          const double *d_core, const double *d_x, int nao, int north, void *stream);
 int dqc_fock_finish(double *d_fock, double *d_energies, double *d_j_ao, double *d_work, const double *d_vxc_ao, int ldv,
                     const double *d_core, const double *d_x, int nao, int north, int with_k, void *stream);
+/* the finish of a HYBRID Kohn-Sham build (exact-exchange fraction kfrac, a run-time value: PBE0 0.25, B3LYP 0.20, ...), after
+ * dqc_fock_prep(with_k = 1) and dqc_jk_stream_prepared(with_k = 1) on d_work:
+ *   d_fock <- sym(X^T (J - kfrac K / 2 + V) X) + core;  d_energies (3 doubles): [0] = 1/2 tr D_ao J, [1] = -kfrac / 4 tr D_ao K,
+ *   [2] = *d_exc (the E_xc quadrature of the grid pass handed through; 0 when d_exc is NULL).
+ * d_vxc: the symmetric AO-basis Vxc matrix (vraw = 0) or the raw cross-block sums of dqc_grid_vxc_raw (vraw = 1, vscale as for
+ * dqc_fock_finish_vraw), row stride ldv.  Same launches, reduction order and deterministic-mode behaviour as dqc_fock_finish. */
+int dqc_fock_finish_hybrid(double *d_fock, double *d_energies, double *d_work, const double *d_vxc, int ldv, int vraw, double vscale,
+                           double kfrac, const double *d_exc, const double *d_core, const double *d_x, int nao, int north, void *stream);
 
 /* Several density matrices in ONE pass over the tiles (unrestricted HF: J[D_u + D_d], K[2 D_u], K[2 D_d],
  * hcgto.py:238-241, hf.py:93-103; batched dm, base_hamilton.py:92-93).
