@@ -377,6 +377,70 @@ __global__ __launch_bounds__(FT_NT) void fock_out_kernel(double *__restrict__ fo
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The small ends of an orbital-Hessian product (dqc_amd/response.py), batched over the nvec trial rotations (blockIdx.z):
+//   resp_gemm_kernel   C[v] = alpha (op(A[v]) B[v])  [+ alpha (ea[m] - eb[n]) X[v][m][n]]       (batch stride 0: shared operand)
+//       T = C_v kappa (half-transformed rotation), U = G C_o, and the projection C_v^T U with the diagonal term
+//       (eps_a - eps_i) kappa_ai of canonical orbitals in its epilogue
+//   resp_dm_kernel     dD[v] = scale (T[v] C_o^T + C_o T[v]^T): ONE product over K = 2 n_occ, [T | C_o] [C_o | T]^T
+// One 4-wave block per 16 x 16 output tile (ft_tile): loads from clamped addresses, stores guarded.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FT_NT) void resp_gemm_kernel(double *__restrict__ c, const double *__restrict__ a, const double *__restrict__ b, int M,
+                                                          int N, int K, int lda, int ldb, int ldc, long long sa, long long sb, long long sc,
+                                                          int transa, double alpha, const double *__restrict__ ea,
+                                                          const double *__restrict__ eb, const double *__restrict__ x, long long sx) {
+    __shared__ double sred[4 * 256];
+    const int lane = threadIdx.x & 63, lr = lane & 15, kq = lane >> 4;
+    const int i0 = 16 * blockIdx.x, j0 = 16 * blockIdx.y, v = blockIdx.z;
+    a += (size_t)v * sa;
+    b += (size_t)v * sb;
+    const v4d t = ft_tile((K + 3) & ~3,
+        [&](int m, int k) {
+            const int mm = min(i0 + m, M - 1), kk = min(k, K - 1);
+            const double val = transa ? a[(size_t)kk * lda + mm] : a[(size_t)mm * lda + kk];
+            return (i0 + m < M && k < K) ? val : 0.0;
+        },
+        [&](int k, int n) { const double val = b[(size_t)min(k, K - 1) * ldb + min(j0 + n, N - 1)]; return (k < K && j0 + n < N) ? val : 0.0; }, sred);
+    if (threadIdx.x < 64) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int i = i0 + kq + 4 * q, j = j0 + lr;
+            if (i < M && j < N) {
+                double r = t[q];
+                if (x) r += (ea[i] - eb[j]) * x[(size_t)v * sx + (size_t)i * N + j];
+                c[(size_t)v * sc + (size_t)i * ldc + j] = alpha * r;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(FT_NT) void resp_dm_kernel(double *__restrict__ dm, const double *__restrict__ t_, const double *__restrict__ co,
+                                                        int nao, int no, double scale) {
+    __shared__ double sred[4 * 256];
+    const int lane = threadIdx.x & 63, lr = lane & 15, kq = lane >> 4;
+    const int i0 = 16 * blockIdx.x, j0 = 16 * blockIdx.y, v = blockIdx.z;
+    const double *t = t_ + (size_t)v * nao * no;
+    const int K = 2 * no;
+    const v4d r = ft_tile((K + 3) & ~3,
+        [&](int m, int k) {
+            const int mm = min(i0 + m, nao - 1), kk = min(k, K - 1);
+            const double val = kk < no ? t[(size_t)mm * no + kk] : co[(size_t)mm * no + (kk - no)];
+            return (i0 + m < nao && k < K) ? val : 0.0;
+        },
+        [&](int k, int n) {
+            const int nn = min(j0 + n, nao - 1), kk = min(k, K - 1);
+            const double val = kk < no ? co[(size_t)nn * no + kk] : t[(size_t)nn * no + (kk - no)];
+            return (j0 + n < nao && k < K) ? val : 0.0;
+        }, sred);
+    if (threadIdx.x < 64) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int i = i0 + kq + 4 * q, j = j0 + lr;
+            if (i < nao && j < nao) dm[((size_t)v * nao + i) * nao + j] = scale * r[q];
+        }
+    }
+}
+
 }  // namespace dqc
 
 extern "C" {
@@ -502,6 +566,44 @@ static int fock_finish_impl(double *d_fock, double *d_energies, double *d_j_ao, 
     DQC_CHECK_LAUNCH();
     const int T = (north + 15) / 16;
     hipLaunchKernelGGL(fock_out_kernel, dim3(T * (T + 1) / 2), dim3(FT_NT), 0, st, d_fock, d_t, d_x, d_core, nao, north);
+    DQC_CHECK_LAUNCH();
+    return DQC_OK;
+}
+
+
+int dqc_resp_gemm(double *d_c, const double *d_a, const double *d_b, int M, int N, int K, int lda, int ldb, int ldc, long long sa,
+                  long long sb, long long sc, int transa, int nbatch, double alpha, const double *d_ea, const double *d_eb, const double *d_x,
+                  void *stream) {
+    // C[v] (M x N, row stride ldc, batch stride sc) = alpha op(A[v]) B[v] (+ alpha (ea[m] - eb[n]) X[v][m][n], X dense (nbatch, M, N), when
+    // d_x is given); op(A) = A (M x K, row stride lda) or A^T (A stored K x M) with transa; batch strides sa / sb may be 0
+    using namespace dqc;
+    if (M <= 0 || N <= 0 || nbatch <= 0) return DQC_OK;
+    if (K <= 0 || !d_c || !d_a || !d_b || nbatch > 65535 || lda < (transa ? M : K) || ldb < N || ldc < N || sa < 0 || sb < 0 ||
+        sc < (long long)M * ldc || (d_x && (!d_ea || !d_eb))) {
+        set_error("dqc_resp_gemm: bad shape, stride or null argument");
+        return DQC_EINVAL;
+    }
+    hipLaunchKernelGGL(resp_gemm_kernel, dim3((M + 15) / 16, (N + 15) / 16, nbatch), dim3(FT_NT), 0, (hipStream_t)stream, d_c, d_a, d_b, M, N, K,
+                       lda, ldb, ldc, sa, sb, sc, transa, alpha, d_ea, d_eb, d_x, (long long)M * N);
+    DQC_CHECK_LAUNCH();
+    return DQC_OK;
+}
+
+int dqc_resp_kappa2dm(double *d_dm, double *d_t, const double *d_kappa, const double *d_cv, const double *d_co, int nao, int nv, int no,
+                      int nvec, double scale, void *stream) {
+    // dD[v] = scale (C_v kappa[v] C_o^T + transpose) (nvec, nao, nao) from kappa (nvec, nv, no), C_v (nao, nv), C_o (nao, no), all
+    // row-major; d_t: scratch of nvec nao no doubles (the half-transformed rotations C_v kappa[v])
+    using namespace dqc;
+    if (nvec <= 0 || nao <= 0) return DQC_OK;
+    if (nv <= 0 || no <= 0 || nvec > 65535 || !d_dm || !d_t || !d_kappa || !d_cv || !d_co) {
+        set_error("dqc_resp_kappa2dm: needs n_virt > 0, n_occ > 0 and no null argument");
+        return DQC_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(resp_gemm_kernel, dim3((nao + 15) / 16, (no + 15) / 16, nvec), dim3(FT_NT), 0, st, d_t, d_cv, d_kappa, nao, no, nv, nv, no, no,
+                       0LL, (long long)nv * no, (long long)nao * no, 0, 1.0, nullptr, nullptr, nullptr, 0LL);
+    DQC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(resp_dm_kernel, dim3((nao + 15) / 16, (nao + 15) / 16, nvec), dim3(FT_NT), 0, st, d_dm, d_t, d_co, nao, no, scale);
     DQC_CHECK_LAUNCH();
     return DQC_OK;
 }

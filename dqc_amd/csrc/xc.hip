@@ -58,49 +58,53 @@ __global__ __launch_bounds__(64) void xc_quad_sum_kernel(double *__restrict__ ex
 // lda_x / gga_x_pbe by exact spin scaling; PW92 with the zeta interpolation (constants of
 // dqc/test/test_xc.py:399-414); PBE correlation with phi(zeta) and the modified-PW92 LDA part.
 // ---------------------------------------------------------------------------------------------
-struct D5 {
-    double v, d[5];
+template <class S>
+struct D5T {
+    S v, d[5];
 };
-DQC_DEV D5 c5(double v) { D5 r; r.v = v; for (int i = 0; i < 5; i++) r.d[i] = 0.0; return r; }
-DQC_DEV D5 var5(double v, int k) { D5 r = c5(v); r.d[k] = 1.0; return r; }
-DQC_DEV D5 operator+(D5 a, D5 b) { D5 r; r.v = a.v + b.v; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] + b.d[i]; return r; }
-DQC_DEV D5 operator-(D5 a, D5 b) { D5 r; r.v = a.v - b.v; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] - b.d[i]; return r; }
-DQC_DEV D5 operator*(D5 a, D5 b) { D5 r; r.v = a.v * b.v; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
-DQC_DEV D5 operator/(D5 a, D5 b) {
-    D5 r; const double ib = 1.0 / b.v; r.v = a.v * ib;
+using D5 = D5T<double>;
+template <class S = double> DQC_DEV D5T<S> c5(double v) { D5T<S> r; r.v = s_const<S>(v); for (int i = 0; i < 5; i++) r.d[i] = s_const<S>(0.0); return r; }
+template <class S = double> DQC_DEV D5T<S> var5(double v, int k) { D5T<S> r = c5<S>(v); r.d[k] = s_const<S>(1.0); return r; }
+template <class S> DQC_DEV D5T<S> operator+(D5T<S> a, D5T<S> b) { D5T<S> r; r.v = a.v + b.v; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] + b.d[i]; return r; }
+template <class S> DQC_DEV D5T<S> operator-(D5T<S> a, D5T<S> b) { D5T<S> r; r.v = a.v - b.v; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] - b.d[i]; return r; }
+template <class S> DQC_DEV D5T<S> operator*(D5T<S> a, D5T<S> b) { D5T<S> r; r.v = a.v * b.v; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
+template <class S> DQC_DEV D5T<S> operator/(D5T<S> a, D5T<S> b) {
+    D5T<S> r; const S ib = 1.0 / b.v; r.v = a.v * ib;
     for (int i = 0; i < 5; i++) r.d[i] = (a.d[i] - r.v * b.d[i]) * ib;
     return r;
 }
-DQC_DEV D5 operator*(double a, D5 b) { D5 r; r.v = a * b.v; for (int i = 0; i < 5; i++) r.d[i] = a * b.d[i]; return r; }
-DQC_DEV D5 operator+(double a, D5 b) { b.v += a; return b; }
-DQC_DEV D5 operator-(double a, D5 b) { D5 r; r.v = a - b.v; for (int i = 0; i < 5; i++) r.d[i] = -b.d[i]; return r; }
-DQC_DEV D5 operator/(double a, D5 b) { return c5(a) / b; }
-DQC_DEV D5 chain(D5 a, double f, double df) { D5 r; r.v = f; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] * df; return r; }
-DQC_DEV D5 p5(D5 a, double e) { const double f = pow(a.v, e); return chain(a, f, e * f / a.v); }
-DQC_DEV D5 cbrt5(D5 a) { const double f = cbrt(a.v); return chain(a, f, f / (3.0 * a.v)); }
-DQC_DEV D5 sqrt5(D5 a) { const double f = sqrt(a.v); return chain(a, f, 0.5 / f); }
-DQC_DEV D5 log1p5(D5 a) { return chain(a, log1p(a.v), 1.0 / (1.0 + a.v)); }
-DQC_DEV D5 expm15(D5 a) { return chain(a, expm1(a.v), exp(a.v)); }
+template <class S> DQC_DEV D5T<S> operator*(double a, D5T<S> b) { D5T<S> r; r.v = a * b.v; for (int i = 0; i < 5; i++) r.d[i] = a * b.d[i]; return r; }
+template <class S> DQC_DEV D5T<S> operator+(double a, D5T<S> b) { b.v = b.v + a; return b; }
+template <class S> DQC_DEV D5T<S> operator-(double a, D5T<S> b) { D5T<S> r; r.v = a - b.v; for (int i = 0; i < 5; i++) r.d[i] = -b.d[i]; return r; }
+template <class S> DQC_DEV D5T<S> operator/(double a, D5T<S> b) { return c5<S>(a) / b; }
+template <class S> DQC_DEV D5T<S> chain(D5T<S> a, S f, S df) { D5T<S> r; r.v = f; for (int i = 0; i < 5; i++) r.d[i] = a.d[i] * df; return r; }
+template <class S> DQC_DEV D5T<S> p5(D5T<S> a, double e) { const S f = s_pow(a.v, e); return chain(a, f, e * f / a.v); }
+template <class S> DQC_DEV D5T<S> cbrt5(D5T<S> a) { const S f = s_cbrt(a.v); return chain(a, f, f / (3.0 * a.v)); }
+template <class S> DQC_DEV D5T<S> sqrt5(D5T<S> a) { const S f = s_sqrt(a.v); return chain(a, f, 0.5 / f); }
+template <class S> DQC_DEV D5T<S> log1p5(D5T<S> a) { return chain(a, s_log1p(a.v), 1.0 / (1.0 + a.v)); }
+template <class S> DQC_DEV D5T<S> expm15(D5T<S> a) { return chain(a, s_expm1(a.v), s_exp(a.v)); }
 
-DQC_DEV D5 log5(D5 a) { return chain(a, log(a.v), 1.0 / a.v); }
-DQC_DEV D5 atan5(D5 a) { return chain(a, atan(a.v), 1.0 / (1.0 + a.v * a.v)); }
-DQC_DEV D5 exp5(D5 a) { const double e = exp(a.v); return chain(a, e, e); }
-DQC_DEV D5 xasinhx5(D5 y) { double dg; const double v = xasinhx_val(y.v, dg); return chain(y, v, dg); }
-DQC_DEV D5 n_exp(D5 a) { return exp5(a); }
-DQC_DEV D5 n_log(D5 a) { return log5(a); }
-DQC_DEV D5 n_log1p(D5 a) { return log1p5(a); }
-DQC_DEV D5 n_sqrt(D5 a) { return sqrt5(a); }
-DQC_DEV D5 n_cbrt(D5 a) { return cbrt5(a); }
-DQC_DEV D5 n_pow(D5 a, double e) { return p5(a, e); }
-DQC_DEV D5 n_xasinhx(D5 a) { return xasinhx5(a); }
-DQC_DEV D5 n_floor(D5 a, double lo) { return a.v < lo ? c5(lo) : a; }
-DQC_DEV D5 operator*(D5 a, double b) { return b * a; }
-DQC_DEV D5 operator+(D5 a, double b) { return b + a; }
-DQC_DEV D5 operator-(D5 a, double b) { a.v -= b; return a; }
-DQC_DEV D5 operator/(D5 a, double b) { return (1.0 / b) * a; }
+template <class S> DQC_DEV D5T<S> log5(D5T<S> a) { return chain(a, s_log(a.v), 1.0 / a.v); }
+template <class S> DQC_DEV D5T<S> atan5(D5T<S> a) { return chain(a, s_atan(a.v), 1.0 / (1.0 + a.v * a.v)); }
+template <class S> DQC_DEV D5T<S> exp5(D5T<S> a) { const S e = s_exp(a.v); return chain(a, e, e); }
+template <class S> DQC_DEV D5T<S> xasinhx5(D5T<S> y) { S dg; const S v = xasinhx_val(y.v, dg); return chain(y, v, dg); }
+template <class S> DQC_DEV D5T<S> n_exp(D5T<S> a) { return exp5(a); }
+template <class S> DQC_DEV D5T<S> n_log(D5T<S> a) { return log5(a); }
+template <class S> DQC_DEV D5T<S> n_log1p(D5T<S> a) { return log1p5(a); }
+template <class S> DQC_DEV D5T<S> n_sqrt(D5T<S> a) { return sqrt5(a); }
+template <class S> DQC_DEV D5T<S> n_cbrt(D5T<S> a) { return cbrt5(a); }
+template <class S> DQC_DEV D5T<S> n_pow(D5T<S> a, double e) { return p5(a, e); }
+template <class S> DQC_DEV D5T<S> n_xasinhx(D5T<S> a) { return xasinhx5(a); }
+template <class S> DQC_DEV D5T<S> n_floor(D5T<S> a, double lo) { return s_val(a.v) < lo ? c5<S>(lo) : a; }
+template <class S> DQC_DEV D5T<S> operator*(D5T<S> a, double b) { return b * a; }
+template <class S> DQC_DEV D5T<S> operator+(D5T<S> a, double b) { return b + a; }
+template <class S> DQC_DEV D5T<S> operator-(D5T<S> a, double b) { a.v = a.v - b; return a; }
+template <class S> DQC_DEV D5T<S> operator/(D5T<S> a, double b) { return (1.0 / b) * a; }
 
 // lda_c_vwn (VWN5), spin-polarised: eps = eps_P + alpha_c f(zeta) (1 - zeta^4) / f''(0) + (eps_F - eps_P) f(zeta) zeta^4
-DQC_DEV D5 vwn_pol_eps(D5 rho, D5 zeta) {
+template <class S>
+DQC_DEV D5T<S> vwn_pol_eps(D5T<S> rho, D5T<S> zeta) {
+    using D5 = D5T<S>;
     const double fz20 = 1.709920934161365617563962776245, Aalpha = -1.0 / (6.0 * kPi * kPi);
     D5 x = sqrt5(cbrt5((3.0 / (4.0 * kPi)) / rho));
     auto lg = [](D5 a) { return log5(a); };
@@ -108,21 +112,25 @@ DQC_DEV D5 vwn_pol_eps(D5 rho, D5 zeta) {
     D5 eP = vwn_fit(x, 0.0310907, 3.72744, 12.9352, -0.10498, lg, at);
     D5 eF = vwn_fit(x, 0.01554535, 7.06042, 18.0578, -0.32500, lg, at);
     D5 aC = vwn_fit(x, Aalpha, 1.13107, 13.0045, -0.0047584, lg, at);
-    D5 fz = (p5(1.0 + zeta, 4.0 / 3.0) + p5(1.0 - zeta, 4.0 / 3.0) - c5(2.0)) / c5(0.51984209978974632953);
+    D5 fz = (p5(1.0 + zeta, 4.0 / 3.0) + p5(1.0 - zeta, 4.0 / 3.0) - c5<S>(2.0)) / c5<S>(0.51984209978974632953);
     D5 z2 = zeta * zeta, z4 = z2 * z2;
-    return eP + aC * fz * (c5(1.0) - z4) / c5(fz20) + (eF - eP) * fz * z4;
+    return eP + aC * fz * (c5<S>(1.0) - z4) / c5<S>(fz20) + (eF - eP) * fz * z4;
 }
 
 // one spin channel of gga_x_b88: -rho_s^(4/3) [Cx + beta x^2 / (1 + 6 beta x asinh x)]
-DQC_DEV D5 b88_spin5(D5 rs_, D5 sss) {
+template <class S>
+DQC_DEV D5T<S> b88_spin5(D5T<S> rs_, D5T<S> sss) {
+    using D5 = D5T<S>;
     const double beta = 0.0042, cx = 0.9305257363491;
     D5 r43 = rs_ * cbrt5(rs_);
     D5 y = sss / (r43 * r43);
-    return c5(0.0) - r43 * (cx + beta * y / (1.0 + (6.0 * beta) * xasinhx5(y)));
+    return c5<S>(0.0) - r43 * (cx + beta * y / (1.0 + (6.0 * beta) * xasinhx5(y)));
 }
 
 // gga_c_lyp, general spin form (Miehlich, Savin, Stoll, Preuss, CPL 157, 200 (1989), eq. 2)
-DQC_DEV D5 lyp_pol5(D5 ra, D5 rb, D5 saa, D5 sab, D5 sbb) {
+template <class S>
+DQC_DEV D5T<S> lyp_pol5(D5T<S> ra, D5T<S> rb, D5T<S> saa, D5T<S> sab, D5T<S> sbb) {
+    using D5 = D5T<S>;
     const double a = 0.04918, b = 0.132, c = 0.2533, d = 0.349, CF = 2.8712340001881915;
     D5 rho = ra + rb;
     D5 ir13 = 1.0 / cbrt5(rho);
@@ -130,7 +138,7 @@ DQC_DEV D5 lyp_pol5(D5 ra, D5 rb, D5 saa, D5 sab, D5 sbb) {
     D5 delta = c * ir13 + d * ir13 / den;
     D5 r2 = rho * rho;
     D5 r113 = r2 * rho / (ir13 * ir13);
-    D5 omega = exp5(c5(0.0) - c * ir13) / (den * r113);
+    D5 omega = exp5(c5<S>(0.0) - c * ir13) / (den * r113);
     D5 sig = saa + 2.0 * sab + sbb;
     D5 ra83 = ra * ra * cbrt5(ra) * cbrt5(ra), rb83 = rb * rb * cbrt5(rb) * cbrt5(rb);
     D5 t1 = (12.699208415745595 * CF) * (ra83 + rb83);  // 2^(11/3) C_F (ra^(8/3) + rb^(8/3))
@@ -138,10 +146,12 @@ DQC_DEV D5 lyp_pol5(D5 ra, D5 rb, D5 saa, D5 sab, D5 sbb) {
     D5 t3 = ((5.0 / 2.0) - (1.0 / 18.0) * delta) * (saa + sbb);
     D5 t4 = ((delta - 11.0) / 9.0) * ((ra / rho) * saa + (rb / rho) * sbb);
     D5 br = ra * rb * (t1 + t2 - t3 - t4) - (2.0 / 3.0) * r2 * sig + ((2.0 / 3.0) * r2 - ra * ra) * sbb + ((2.0 / 3.0) * r2 - rb * rb) * saa;
-    return c5(0.0) - (4.0 * a) * (ra * rb / (rho * den)) - (a * b) * (omega * br);
+    return c5<S>(0.0) - (4.0 * a) * (ra * rb / (rho * den)) - (a * b) * (omega * br);
 }
 
-DQC_DEV D5 pw92_pol_eps(D5 rho, D5 zeta, const double *a3) {
+template <class S>
+DQC_DEV D5T<S> pw92_pol_eps(D5T<S> rho, D5T<S> zeta, const double *a3) {
+    using D5 = D5T<S>;
     const double alpha1[3] = {0.21370, 0.20548, 0.11125}, b1[3] = {7.5957, 14.1189, 10.357},
                  b2[3] = {3.5876, 6.1977, 3.6231}, b3[3] = {1.6382, 3.3662, 0.88026}, b4[3] = {0.49294, 0.62517, 0.49671};
     const double fz20 = 1.709920934161365617563962776245;
@@ -152,17 +162,84 @@ DQC_DEV D5 pw92_pol_eps(D5 rho, D5 zeta, const double *a3) {
         D5 q1 = (2.0 * a3[i]) * (b1[i] * sq + b2[i] * rs + b3[i] * (rs * sq) + b4[i] * (rs * rs));
         g[i] = (-2.0 * a3[i]) * (1.0 + alpha1[i] * rs) * log1p5(1.0 / q1);
     }
-    D5 fz = (p5(1.0 + zeta, 4.0 / 3.0) + p5(1.0 - zeta, 4.0 / 3.0) - c5(2.0)) / c5(0.51984209978974632953);  // 2^(4/3)-2
+    D5 fz = (p5(1.0 + zeta, 4.0 / 3.0) + p5(1.0 - zeta, 4.0 / 3.0) - c5<S>(2.0)) / c5<S>(0.51984209978974632953);  // 2^(4/3)-2
     D5 z2 = zeta * zeta, z4 = z2 * z2;
-    return g[0] + z4 * fz * (g[1] - g[0] + g[2] / c5(fz20)) - fz * g[2] / c5(fz20);
+    return g[0] + z4 * fz * (g[1] - g[0] + g[2] / c5<S>(fz20)) - fz * g[2] / c5<S>(fz20);
 }
 
-DQC_DEV D5 pbe_x_unpol5(D5 r, D5 s, double kappa = kPbeKappa, double mu = kPbeMu, bool rpbe = false) {
+template <class S>
+DQC_DEV D5T<S> pbe_x_unpol5(D5T<S> r, D5T<S> s, double kappa = kPbeKappa, double mu = kPbeMu, bool rpbe = false) {
+    using D5 = D5T<S>;
     const double c2 = 4.0 * 9.5707800006273038;
     D5 r43 = r * cbrt5(r);
     D5 s2 = s / (c2 * (r43 * r43));
-    D5 F = rpbe ? (1.0 + kappa) - kappa * exp5(c5(0.0) - (mu / kappa) * s2) : (1.0 + kappa) - kappa / (1.0 + (mu / kappa) * s2);
+    D5 F = rpbe ? (1.0 + kappa) - kappa * exp5(c5<S>(0.0) - (mu / kappa) * s2) : (1.0 + kappa) - kappa / (1.0 + (mu / kappa) * s2);
     return (-0.75 * 0.98474502184269641) * (r43 * F);
+}
+
+// one term of a spin-polarised LDA / GGA functional at a point; called with a run-time id in the generic kernel and with
+// compile-time ids in the PBE-pair instantiation and the second-order kernels (the switch folds away -- the generic first-order
+// kernel holds 494 VGPRs, one wave per SIMD).  rho = u + d and the clamped zeta = (u - d) / rho come from the caller.
+template <bool EXT, class S>
+DQC_DEV D5T<S> xc_pol_term(const int tid_, const D5T<S> &u, const D5T<S> &d, const D5T<S> &suu, const D5T<S> &sud, const D5T<S> &sdd,
+                           const D5T<S> &rho, const D5T<S> &zeta) {
+    using D5 = D5T<S>;
+    D5 f;
+    bool ext_done = false;
+    if constexpr (EXT) {  // the round-4 functionals live in their own instantiation (see xc_funcs.hpp: xc_id_is_ext)
+        const int id_ = tid_;
+        if (xc_id_is_x_enh(id_)) {  // enhancement-factor exchange: exact spin scaling of the unpolarised form
+            f = 0.5 * (gga_x_by_enh(id_, 2.0 * u, 4.0 * suu) + gga_x_by_enh(id_, 2.0 * d, 4.0 * sdd));
+            ext_done = true;
+        } else if (id_ == DQC_XC_LDA_C_PZ || id_ == DQC_XC_GGA_C_P86) {
+            D5 fz = (p5(1.0 + zeta, 4.0 / 3.0) + p5(1.0 - zeta, 4.0 / 3.0) - c5<S>(2.0)) / c5<S>(0.51984209978974632953);
+            f = rho * pz81_eps(rho, fz, true);
+            if (id_ == DQC_XC_GGA_C_P86) {
+                D5 dz = 1.2599210498948732 * sqrt5(p5(0.5 * (1.0 + zeta), 5.0 / 3.0) + p5(0.5 * (1.0 - zeta), 5.0 / 3.0));
+                f = f + p86_gradient_term(rho, suu + 2.0 * sud + sdd, dz, true);
+            }
+            ext_done = true;
+        }
+    }
+    if (!ext_done)
+    switch (tid_) {
+    case DQC_XC_LDA_X:
+        f = (-0.75 * 0.98474502184269641 * 1.2599210498948732) * (u * cbrt5(u) + d * cbrt5(d));
+        break;
+    case DQC_XC_LDA_C_PW: {
+        const double a3[3] = {0.0310907, 0.01554535, 0.0168869};
+        f = rho * pw92_pol_eps(rho, zeta, a3);
+    } break;
+    case DQC_XC_LDA_C_PW_MOD: {
+        const double a3[3] = {0.0310906908696548950, 0.01554534543482745, 0.0168868639403896};
+        f = rho * pw92_pol_eps(rho, zeta, a3);
+    } break;
+    case DQC_XC_GGA_X_PBE: case DQC_XC_GGA_X_PBE_R: case DQC_XC_GGA_X_PBE_SOL: case DQC_XC_GGA_X_RPBE: {
+        // exchange: exact spin scaling of the unpolarised form (kappa, mu by member of the family)
+        const int id_ = tid_;
+        const double ka = id_ == DQC_XC_GGA_X_PBE_R ? 1.245 : kPbeKappa, mu_ = id_ == DQC_XC_GGA_X_PBE_SOL ? 10.0 / 81.0 : kPbeMu;
+        const bool rp = id_ == DQC_XC_GGA_X_RPBE;
+        f = 0.5 * (pbe_x_unpol5(2.0 * u, 4.0 * suu, ka, mu_, rp) + pbe_x_unpol5(2.0 * d, 4.0 * sdd, ka, mu_, rp));
+    } break;
+    case DQC_XC_LDA_C_VWN: f = rho * vwn_pol_eps(rho, zeta); break;
+    case DQC_XC_GGA_X_B88: f = b88_spin5(u, suu) + b88_spin5(d, sdd); break;
+    case DQC_XC_GGA_C_LYP: f = lyp_pol5(u, d, suu, sud, sdd); break;
+    default: {
+        const double a3[3] = {0.0310906908696548950, 0.01554534543482745, 0.0168868639403896};
+        const double beta = tid_ == DQC_XC_GGA_C_PBE_SOL ? 0.046 : kPbeBeta, gamma = 0.031090690869654895;
+        D5 eps = pw92_pol_eps(rho, zeta, a3);
+        D5 phi = 0.5 * (p5(1.0 + zeta, 2.0 / 3.0) + p5(1.0 - zeta, 2.0 / 3.0));
+        D5 phi3 = phi * phi * phi;
+        D5 sig = suu + 2.0 * sud + sdd;
+        D5 kf = cbrt5((3.0 * kPi * kPi) * rho);
+        D5 t2 = sig / (4.0 * (phi * phi) * ((4.0 / kPi) * kf) * (rho * rho));
+        D5 A = c5<S>(beta / gamma) / expm15(c5<S>(0.0) - eps / (gamma * phi3));
+        D5 At2 = A * t2;
+        D5 X = (beta / gamma) * t2 * (1.0 + At2) / (1.0 + At2 + At2 * At2);
+        f = rho * (eps + gamma * phi3 * log1p5(X));
+    } break;
+    }
+    return f;
 }
 
 
@@ -187,66 +264,7 @@ __global__ __launch_bounds__(256) void xc_pol_kernel(double *__restrict__ edens,
             const D5 rho = u + d;
             D5 zeta = (u - d) / rho;
             zeta.v = fmin(fmax(zeta.v, -1.0 + 1e-10), 1.0 - 1e-10);
-            // one term of the functional at this point; called with a run-time id in the generic kernel and with compile-time ids in
-            // the PBE-pair instantiation (PAIR = 1: the switch folds away -- the generic kernel holds 506 VGPRs, one wave per SIMD)
-            auto term = [&](const int tid_) -> D5 {
-                D5 f;
-                bool ext_done = false;
-                if constexpr (EXT) {  // the round-4 functionals live in their own instantiation (see xc_funcs.hpp: xc_id_is_ext)
-                    const int id_ = tid_;
-                    if (xc_id_is_x_enh(id_)) {  // enhancement-factor exchange: exact spin scaling of the unpolarised form
-                        f = 0.5 * (gga_x_by_enh(id_, 2.0 * u, 4.0 * suu) + gga_x_by_enh(id_, 2.0 * d, 4.0 * sdd));
-                        ext_done = true;
-                    } else if (id_ == DQC_XC_LDA_C_PZ || id_ == DQC_XC_GGA_C_P86) {
-                        D5 fz = (p5(1.0 + zeta, 4.0 / 3.0) + p5(1.0 - zeta, 4.0 / 3.0) - c5(2.0)) / c5(0.51984209978974632953);
-                        f = rho * pz81_eps(rho, fz, true);
-                        if (id_ == DQC_XC_GGA_C_P86) {
-                            D5 dz = 1.2599210498948732 * sqrt5(p5(0.5 * (1.0 + zeta), 5.0 / 3.0) + p5(0.5 * (1.0 - zeta), 5.0 / 3.0));
-                            f = f + p86_gradient_term(rho, suu + 2.0 * sud + sdd, dz, true);
-                        }
-                        ext_done = true;
-                    }
-                }
-                if (!ext_done)
-                switch (tid_) {
-                case DQC_XC_LDA_X:
-                    f = (-0.75 * 0.98474502184269641 * 1.2599210498948732) * (u * cbrt5(u) + d * cbrt5(d));
-                    break;
-                case DQC_XC_LDA_C_PW: {
-                    const double a3[3] = {0.0310907, 0.01554535, 0.0168869};
-                    f = rho * pw92_pol_eps(rho, zeta, a3);
-                } break;
-                case DQC_XC_LDA_C_PW_MOD: {
-                    const double a3[3] = {0.0310906908696548950, 0.01554534543482745, 0.0168868639403896};
-                    f = rho * pw92_pol_eps(rho, zeta, a3);
-                } break;
-                case DQC_XC_GGA_X_PBE: case DQC_XC_GGA_X_PBE_R: case DQC_XC_GGA_X_PBE_SOL: case DQC_XC_GGA_X_RPBE: {
-                    // exchange: exact spin scaling of the unpolarised form (kappa, mu by member of the family)
-                    const int id_ = tid_;
-                    const double ka = id_ == DQC_XC_GGA_X_PBE_R ? 1.245 : kPbeKappa, mu_ = id_ == DQC_XC_GGA_X_PBE_SOL ? 10.0 / 81.0 : kPbeMu;
-                    const bool rp = id_ == DQC_XC_GGA_X_RPBE;
-                    f = 0.5 * (pbe_x_unpol5(2.0 * u, 4.0 * suu, ka, mu_, rp) + pbe_x_unpol5(2.0 * d, 4.0 * sdd, ka, mu_, rp));
-                } break;
-                case DQC_XC_LDA_C_VWN: f = rho * vwn_pol_eps(rho, zeta); break;
-                case DQC_XC_GGA_X_B88: f = b88_spin5(u, suu) + b88_spin5(d, sdd); break;
-                case DQC_XC_GGA_C_LYP: f = lyp_pol5(u, d, suu, sud, sdd); break;
-                default: {
-                    const double a3[3] = {0.0310906908696548950, 0.01554534543482745, 0.0168868639403896};
-                    const double beta = tid_ == DQC_XC_GGA_C_PBE_SOL ? 0.046 : kPbeBeta, gamma = 0.031090690869654895;
-                    D5 eps = pw92_pol_eps(rho, zeta, a3);
-                    D5 phi = 0.5 * (p5(1.0 + zeta, 2.0 / 3.0) + p5(1.0 - zeta, 2.0 / 3.0));
-                    D5 phi3 = phi * phi * phi;
-                    D5 sig = suu + 2.0 * sud + sdd;
-                    D5 kf = cbrt5((3.0 * kPi * kPi) * rho);
-                    D5 t2 = sig / (4.0 * (phi * phi) * ((4.0 / kPi) * kf) * (rho * rho));
-                    D5 A = c5(beta / gamma) / expm15(c5(0.0) - eps / (gamma * phi3));
-                    D5 At2 = A * t2;
-                    D5 X = (beta / gamma) * t2 * (1.0 + At2) / (1.0 + At2 + At2 * At2);
-                    f = rho * (eps + gamma * phi3 * log1p5(X));
-                } break;
-                }
-                return f;
-            };
+            auto term = [&](const int tid_) -> D5 { return xc_pol_term<EXT>(tid_, u, d, suu, sud, sdd, rho, zeta); };
             if constexpr (PAIR == 1) {
                 const D5 f0 = term(DQC_XC_GGA_X_PBE);
                 e += terms.c[0] * f0.v;
@@ -804,5 +822,232 @@ extern "C" int dqc_xc_eval_mgga_pol2(double *d_edens, double *d_vrho_u, double *
     hipLaunchKernelGGL(xc_mgga_pol2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_edens, d_vrho_u, d_vrho_d, d_vgrad_u,
                        d_vgrad_d, d_vtau, d_rho_u, d_rho_d, d_grho_u, d_grho_d, d_tau_u, d_tau_d, n, t);
     DQC_CHECK_LAUNCH();
+    return DQC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Second functional derivatives on the grid (the response kernel f_xc of dqc_amd/response.py): the change of the potentials of
+// xc_kernel / xc_pol_kernel under a change (d rho, d grad rho) of the density, for a batch of nvec trial responses.
+// The functional bodies above are instantiated with the scalar Tan (value + one tangent): seeding the tangent of one input
+// with 1 makes the tangents of the gradient slots one row of the Hessian of e(rho, sigma) [e(rho_u, rho_d, sigma_uu, sigma_ud,
+// sigma_dd)], analytically.  Per grid point the Hessian is built ONCE (2 evaluations, 1 for an LDA term; 5 / 2 polarised) from the
+// ground-state density, which is read once; the nvec responses are then contracted with it.
+//   restricted:  d v_rho = e_rr d rho + e_rs d sigma,   d sigma = 2 grad rho . grad d rho
+//                d (2 v_sigma grad rho) = 2 (e_sr d rho + e_ss d sigma) grad rho + 2 e_s grad d rho
+//   polarised:   the same with the five inputs; d sigma_ud = grad rho_u . grad d rho_d + grad d rho_u . grad rho_d and
+//                d v_grad,u = 2 d v_uu grad rho_u + 2 v_uu grad d rho_u + d v_ud grad rho_d + v_ud grad d rho_d
+// One launch per term of the (coef, id) list with the functional fixed at COMPILE time (ID >= 0; ID = -1: the enhancement-factor
+// exchange table by its run-time id), accumulated into outputs the host zeroes first: the run-time switch over all functionals
+// costs the first-order polarised kernel 494 VGPRs with 6 doubles per number, and a number is 12 doubles here.
+// Same density cutoff as the first-order kernels: nothing is added (the output stays zero) where rho <= 1e-15.
+// ---------------------------------------------------------------------------------------------
+namespace dqc {
+
+template <int ID>
+__global__ __launch_bounds__(256) void xc_fxc_kernel(double *__restrict__ dvrho, double *__restrict__ dvgrad, const double *__restrict__ rho,
+                                                     const double *__restrict__ grho, const double *__restrict__ drho,
+                                                     const double *__restrict__ dgrho, int n, int nvec, int id_rt, double coef) {
+    constexpr bool GGA = ID < 0 || xc_id_is_gga(ID);
+    constexpr bool EXT = ID < 0 || xc_id_is_ext(ID);
+    const int id = ID < 0 ? id_rt : ID;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const double r = rho[i];
+        if (!(r > 1e-15)) continue;
+        double g[3] = {0.0, 0.0, 0.0};
+        if constexpr (GGA)
+            for (int k = 0; k < 3; k++) g[k] = grho[(size_t)k * n + i];
+        const double sigma = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+        double vs = 0.0, hrr, hrs = 0.0, hss = 0.0;
+        {
+            const DualT<Tan> dr{Tan{r, 1.0}, Tan{1.0, 0.0}, Tan{0.0, 0.0}}, ds{Tan{sigma, 0.0}, Tan{0.0, 0.0}, Tan{1.0, 0.0}};
+            const DualT<Tan> f = f_lda_gga<EXT, Tan>(id, dr, ds);
+            hrr = f.r.t;
+            hrs = f.s.t;
+            vs = f.s.v;
+        }
+        if constexpr (GGA) {
+            const DualT<Tan> dr{Tan{r, 0.0}, Tan{1.0, 0.0}, Tan{0.0, 0.0}}, ds{Tan{sigma, 1.0}, Tan{0.0, 0.0}, Tan{1.0, 0.0}};
+            hss = f_lda_gga<EXT, Tan>(id, dr, ds).s.t;
+        }
+        for (int v = 0; v < nvec; v++) {
+            const double dr = drho[(size_t)v * n + i];
+            if constexpr (GGA) {
+                const double *dg_ = dgrho + (size_t)v * 3 * n + i;
+                double *out = dvgrad + (size_t)v * 3 * n + i;
+                const double dg[3] = {dg_[0], dg_[n], dg_[2 * (size_t)n]};
+                const double dsig = 2.0 * (g[0] * dg[0] + g[1] * dg[1] + g[2] * dg[2]);
+                dvrho[(size_t)v * n + i] += coef * (hrr * dr + hrs * dsig);
+                const double dvs = hrs * dr + hss * dsig;
+                for (int k = 0; k < 3; k++) out[(size_t)k * n] += coef * (2.0 * dvs * g[k] + 2.0 * vs * dg[k]);
+            } else {
+                dvrho[(size_t)v * n + i] += coef * (hrr * dr);
+            }
+        }
+    }
+}
+
+template <int ID>
+__global__ __launch_bounds__(256) void xc_fxc_pol_kernel(double *__restrict__ dvu, double *__restrict__ dvd, double *__restrict__ dvgu,
+                                                         double *__restrict__ dvgd, const double *__restrict__ ru_,
+                                                         const double *__restrict__ rd_, const double *__restrict__ gu_,
+                                                         const double *__restrict__ gd_, const double *__restrict__ dru_,
+                                                         const double *__restrict__ drd_, const double *__restrict__ dgu_,
+                                                         const double *__restrict__ dgd_, int n, int nvec, int id_rt, double coef) {
+    constexpr bool GGA = ID < 0 || xc_id_is_gga(ID);
+    constexpr bool EXT = ID < 0 || xc_id_is_ext(ID);
+    constexpr int NV = GGA ? 5 : 2;  // inputs the term depends on
+    const int id = ID < 0 ? id_rt : ID;
+    using T5 = D5T<Tan>;
+    __shared__ double sh[NV * NV][256];  // this thread's Hessian: column threadIdx.x (each thread reads only what it wrote: no barrier)
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        double ru = ru_[i], rd = rd_[i];
+        if (!(ru + rd > 1e-15)) continue;
+        ru = fmax(ru, 0.5e-15);
+        rd = fmax(rd, 0.5e-15);
+        double gu[3] = {0, 0, 0}, gd[3] = {0, 0, 0};
+        if constexpr (GGA)
+            for (int k = 0; k < 3; k++) { gu[k] = gu_[(size_t)k * n + i]; gd[k] = gd_[(size_t)k * n + i]; }
+        const double in[5] = {ru, rd, gu[0] * gu[0] + gu[1] * gu[1] + gu[2] * gu[2], gu[0] * gd[0] + gu[1] * gd[1] + gu[2] * gd[2],
+                              gd[0] * gd[0] + gd[1] * gd[1] + gd[2] * gd[2]};
+        // first derivatives; the Hessian (row j: derivative along input j of the gradient) goes through LDS, one column per thread:
+        // the loop over the directions is NOT unrolled (unrolled, the compiler carries the tangents of all five directions at once:
+        // gga_c_pbe then spills 110 VGPRs), and a register array indexed by a run-time j would live in scratch
+        double v1[5] = {0, 0, 0, 0, 0};
+        if constexpr (ID < 0) {
+            // enhancement-factor exchange: e = (f(2 rho_u, 4 sigma_uu) + f(2 rho_d, 4 sigma_dd)) / 2 with the closed-shell f, two
+            // variables per spin channel and no cross terms: de/drho_s = f_r, de/dsigma_ss = 2 f_s, and a tangent seeded on
+            // 2 rho_s (4 sigma_ss) is 1/2 (1/4) of the derivative with respect to rho_s (sigma_ss)
+            for (int k = 0; k < 25; k++) sh[k][threadIdx.x] = 0.0;
+#pragma unroll 1
+            for (int c = 0; c < 4; c++) {
+                const int sp = c >> 1, dir = c & 1, a = sp ? 1 : 0, b = sp ? 4 : 2;
+                const double rs = 2.0 * (sp ? in[1] : in[0]), ss = 4.0 * (sp ? in[4] : in[2]);
+                const DualT<Tan> dr{Tan{rs, dir == 0 ? 1.0 : 0.0}, Tan{1.0, 0.0}, Tan{0.0, 0.0}};
+                const DualT<Tan> ds{Tan{ss, dir == 1 ? 1.0 : 0.0}, Tan{0.0, 0.0}, Tan{1.0, 0.0}};
+                const DualT<Tan> f = f_lda_gga<true, Tan>(id, dr, ds);
+                const double sc = dir == 0 ? 2.0 : 4.0;
+                const int row = dir == 0 ? a : b;
+                sh[row * 5 + a][threadIdx.x] = sc * f.r.t;
+                sh[row * 5 + b][threadIdx.x] = sc * 2.0 * f.s.t;
+                if (sp == 0) { v1[0] = f.r.v; v1[2] = 2.0 * f.s.v; }
+                else { v1[1] = f.r.v; v1[4] = 2.0 * f.s.v; }
+            }
+        } else {
+#pragma unroll 1
+            for (int j = 0; j < NV; j++) {
+                T5 x[5];
+#pragma unroll
+                for (int k = 0; k < 5; k++) {
+                    x[k] = var5<Tan>(in[k], k);
+                    x[k].v.t = k == j ? 1.0 : 0.0;
+                }
+                const T5 rho = x[0] + x[1];
+                T5 zeta = (x[0] - x[1]) / rho;
+                zeta.v.v = fmin(fmax(zeta.v.v, -1.0 + 1e-10), 1.0 - 1e-10);
+                const T5 f = xc_pol_term<EXT, Tan>(id, x[0], x[1], x[2], x[3], x[4], rho, zeta);
+#pragma unroll
+                for (int k = 0; k < NV; k++) {
+                    sh[j * NV + k][threadIdx.x] = f.d[k].t;
+                    v1[k] = f.d[k].v;  // (the same in every direction)
+                }
+            }
+        }
+        for (int v = 0; v < nvec; v++) {
+            double din[5] = {dru_[(size_t)v * n + i], drd_[(size_t)v * n + i], 0.0, 0.0, 0.0};
+            double dgu[3] = {0, 0, 0}, dgd[3] = {0, 0, 0};
+            if constexpr (GGA) {
+                for (int k = 0; k < 3; k++) {
+                    dgu[k] = dgu_[((size_t)v * 3 + k) * n + i];
+                    dgd[k] = dgd_[((size_t)v * 3 + k) * n + i];
+                }
+                din[2] = 2.0 * (gu[0] * dgu[0] + gu[1] * dgu[1] + gu[2] * dgu[2]);
+                din[3] = (gu[0] * dgd[0] + gu[1] * dgd[1] + gu[2] * dgd[2]) + (dgu[0] * gd[0] + dgu[1] * gd[1] + dgu[2] * gd[2]);
+                din[4] = 2.0 * (gd[0] * dgd[0] + gd[1] * dgd[1] + gd[2] * dgd[2]);
+            }
+            double dv[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < NV; k++) {
+#pragma unroll
+                for (int j = 0; j < NV; j++) dv[k] += sh[j * NV + k][threadIdx.x] * din[j];
+            }
+            dvu[(size_t)v * n + i] += coef * dv[0];
+            dvd[(size_t)v * n + i] += coef * dv[1];
+            if constexpr (GGA)
+                for (int k = 0; k < 3; k++) {
+                    dvgu[((size_t)v * 3 + k) * n + i] += coef * (2.0 * dv[2] * gu[k] + 2.0 * v1[2] * dgu[k] + dv[3] * gd[k] + v1[3] * dgd[k]);
+                    dvgd[((size_t)v * 3 + k) * n + i] += coef * (2.0 * dv[4] * gd[k] + 2.0 * v1[4] * dgd[k] + dv[3] * gu[k] + v1[3] * dgu[k]);
+                }
+        }
+    }
+}
+
+// the functional ids with an instantiation of their own (every LDA / GGA id that is not in the enhancement-factor table)
+#define DQC_FXC_IDS(X) X(DQC_XC_LDA_X) X(DQC_XC_LDA_C_PW) X(DQC_XC_LDA_C_PW_MOD) X(DQC_XC_LDA_C_VWN) X(DQC_XC_LDA_C_PZ) X(DQC_XC_GGA_X_PBE) \
+    X(DQC_XC_GGA_X_PBE_R) X(DQC_XC_GGA_X_PBE_SOL) X(DQC_XC_GGA_X_RPBE) X(DQC_XC_GGA_C_PBE) X(DQC_XC_GGA_C_PBE_SOL) X(DQC_XC_GGA_X_B88) \
+    X(DQC_XC_GGA_C_LYP) X(DQC_XC_GGA_C_P86)
+
+static int fxc_check_terms(const char *who, const int *ids, int nterm, bool have_grad, int nvec) {
+    if (nterm < 0 || nterm > 8) { set_error(std::string(who) + ": at most 8 functional terms"); return DQC_EINVAL; }
+    if (nvec < 0) { set_error(std::string(who) + ": negative number of trial vectors"); return DQC_EINVAL; }
+    for (int i = 0; i < nterm; i++) {
+        if (xc_host_is_gga(ids[i])) {
+            if (!have_grad) { set_error(std::string(who) + ": GGA functional needs the density gradients, their responses and the gradient outputs"); return DQC_EINVAL; }
+        } else if (!xc_host_is_lda(ids[i])) {
+            set_error(std::string(who) + ": only the LDA / GGA functional ids have a second-order kernel");
+            return DQC_EINVAL;
+        }
+    }
+    return DQC_OK;
+}
+
+}  // namespace dqc
+
+extern "C" int dqc_xc_eval_fxc(double *d_dvrho, double *d_dvgrad, const double *d_rho, const double *d_grho, const double *d_drho,
+                               const double *d_dgrho, int n, int nvec, const int *ids, const double *coefs, int nterm, void *stream) {
+    using namespace dqc;
+    const bool grad = d_grho && d_dgrho && d_dvgrad;
+    if (int rc = fxc_check_terms("dqc_xc_eval_fxc", ids, nterm, grad, nvec)) return rc;
+    if (n <= 0 || nvec == 0) return DQC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DQC_HIP(hipMemsetAsync(d_dvrho, 0, sizeof(double) * (size_t)nvec * n, st));
+    if (d_dvgrad) DQC_HIP(hipMemsetAsync(d_dvgrad, 0, sizeof(double) * (size_t)nvec * 3 * n, st));
+    int blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    for (int t = 0; t < nterm; t++) {
+        switch (ids[t]) {
+#define X(ID_) case ID_: hipLaunchKernelGGL(xc_fxc_kernel<ID_>, dim3(blocks), dim3(256), 0, st, d_dvrho, d_dvgrad, d_rho, d_grho, d_drho, d_dgrho, n, nvec, ids[t], coefs[t]); break;
+        DQC_FXC_IDS(X)
+#undef X
+        default: hipLaunchKernelGGL(xc_fxc_kernel<-1>, dim3(blocks), dim3(256), 0, st, d_dvrho, d_dvgrad, d_rho, d_grho, d_drho, d_dgrho, n, nvec, ids[t], coefs[t]); break;
+        }
+        DQC_CHECK_LAUNCH();
+    }
+    return DQC_OK;
+}
+
+extern "C" int dqc_xc_eval_fxc_pol(double *d_dvrho_u, double *d_dvrho_d, double *d_dvgrad_u, double *d_dvgrad_d, const double *d_rho_u,
+                                   const double *d_rho_d, const double *d_grho_u, const double *d_grho_d, const double *d_drho_u,
+                                   const double *d_drho_d, const double *d_dgrho_u, const double *d_dgrho_d, int n, int nvec,
+                                   const int *ids, const double *coefs, int nterm, void *stream) {
+    using namespace dqc;
+    const bool grad = d_grho_u && d_grho_d && d_dgrho_u && d_dgrho_d && d_dvgrad_u && d_dvgrad_d;
+    if (int rc = fxc_check_terms("dqc_xc_eval_fxc_pol", ids, nterm, grad, nvec)) return rc;
+    if (n <= 0 || nvec == 0) return DQC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DQC_HIP(hipMemsetAsync(d_dvrho_u, 0, sizeof(double) * (size_t)nvec * n, st));
+    DQC_HIP(hipMemsetAsync(d_dvrho_d, 0, sizeof(double) * (size_t)nvec * n, st));
+    if (d_dvgrad_u) DQC_HIP(hipMemsetAsync(d_dvgrad_u, 0, sizeof(double) * (size_t)nvec * 3 * n, st));
+    if (d_dvgrad_d) DQC_HIP(hipMemsetAsync(d_dvgrad_d, 0, sizeof(double) * (size_t)nvec * 3 * n, st));
+    int blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    for (int t = 0; t < nterm; t++) {
+        switch (ids[t]) {
+#define X(ID_) case ID_: hipLaunchKernelGGL(xc_fxc_pol_kernel<ID_>, dim3(blocks), dim3(256), 0, st, d_dvrho_u, d_dvrho_d, d_dvgrad_u, d_dvgrad_d, d_rho_u, d_rho_d, d_grho_u, d_grho_d, d_drho_u, d_drho_d, d_dgrho_u, d_dgrho_d, n, nvec, ids[t], coefs[t]); break;
+        DQC_FXC_IDS(X)
+#undef X
+        default: hipLaunchKernelGGL(xc_fxc_pol_kernel<-1>, dim3(blocks), dim3(256), 0, st, d_dvrho_u, d_dvrho_d, d_dvgrad_u, d_dvgrad_d, d_rho_u, d_rho_d, d_grho_u, d_grho_d, d_drho_u, d_drho_d, d_dgrho_u, d_dgrho_d, n, nvec, ids[t], coefs[t]); break;
+        }
+        DQC_CHECK_LAUNCH();
+    }
     return DQC_OK;
 }

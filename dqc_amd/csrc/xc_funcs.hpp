@@ -1,4 +1,4 @@
-// xc_funcs.hpp -- unpolarised LDA / GGA functionals with forward-mode first derivatives (dual numbers in (rho, sigma)),
+// xc_funcs.hpp -- unpolarised LDA / GGA functionals with forward-mode derivatives (dual numbers in (rho, sigma) over a scalar type),
 // shared by the stand-alone XC kernel (xc.hip) and the fused grid kernel (grid.hip).  Functional forms and the references
 // they are pinned to: see the header of xc.hip.
 #pragma once
@@ -6,56 +6,104 @@
 
 namespace dqc {
 
-struct Dual {  // value, d/drho, d/dsigma
-    double v, r, s;
+// The scalar underneath the dual numbers is a template parameter: `double` for the first-order kernels (value + gradient), `Tan`
+// (value + ONE tangent) for the second-order kernels of xc.hip, where the tangent of the gradient slots is a directional second
+// derivative.  The s_* functions are the elementary functions of either scalar; with S = double they are the plain libm calls.
+struct Tan {  // value, tangent
+    double v, t;
 };
-DQC_DEV Dual mk(double v, double r = 0.0, double s = 0.0) { return Dual{v, r, s}; }
-DQC_DEV Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.r + b.r, a.s + b.s}; }
-DQC_DEV Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.r - b.r, a.s - b.s}; }
-DQC_DEV Dual operator*(Dual a, Dual b) { return {a.v * b.v, a.r * b.v + a.v * b.r, a.s * b.v + a.v * b.s}; }
-DQC_DEV Dual operator/(Dual a, Dual b) {
-    double q = a.v / b.v, ib = 1.0 / b.v;
+DQC_DEV Tan operator+(Tan a, Tan b) { return {a.v + b.v, a.t + b.t}; }
+DQC_DEV Tan operator-(Tan a, Tan b) { return {a.v - b.v, a.t - b.t}; }
+DQC_DEV Tan operator*(Tan a, Tan b) { return {a.v * b.v, a.t * b.v + a.v * b.t}; }
+DQC_DEV Tan operator/(Tan a, Tan b) { const double ib = 1.0 / b.v, q = a.v * ib; return {q, (a.t - q * b.t) * ib}; }
+DQC_DEV Tan operator-(Tan a) { return {-a.v, -a.t}; }
+DQC_DEV Tan operator+(double a, Tan b) { return {a + b.v, b.t}; }
+DQC_DEV Tan operator+(Tan a, double b) { return {a.v + b, a.t}; }
+DQC_DEV Tan operator-(double a, Tan b) { return {a - b.v, -b.t}; }
+DQC_DEV Tan operator-(Tan a, double b) { return {a.v - b, a.t}; }
+DQC_DEV Tan operator*(double a, Tan b) { return {a * b.v, a * b.t}; }
+DQC_DEV Tan operator*(Tan a, double b) { return {a.v * b, a.t * b}; }
+DQC_DEV Tan operator/(Tan a, double b) { const double ib = 1.0 / b; return {a.v * ib, a.t * ib}; }
+DQC_DEV Tan operator/(double a, Tan b) { const double q = a / b.v; return {q, -q * b.t / b.v}; }
+
+DQC_DEV double s_val(double a) { return a; }
+DQC_DEV double s_val(Tan a) { return a.v; }
+template <class S> DQC_DEV S s_const(double c);
+template <> DQC_DEV double s_const<double>(double c) { return c; }
+template <> DQC_DEV Tan s_const<Tan>(double c) { return {c, 0.0}; }
+DQC_DEV double s_cbrt(double a) { return cbrt(a); }
+DQC_DEV double s_sqrt(double a) { return sqrt(a); }
+DQC_DEV double s_log(double a) { return log(a); }
+DQC_DEV double s_log1p(double a) { return log1p(a); }
+DQC_DEV double s_exp(double a) { return exp(a); }
+DQC_DEV double s_expm1(double a) { return expm1(a); }
+DQC_DEV double s_atan(double a) { return atan(a); }
+DQC_DEV double s_asinh(double a) { return asinh(a); }
+DQC_DEV double s_pow(double a, double e) { return pow(a, e); }
+DQC_DEV Tan s_cbrt(Tan a) { const double q = cbrt(a.v); return {q, a.t * q / (3.0 * a.v)}; }
+DQC_DEV Tan s_sqrt(Tan a) { const double q = sqrt(a.v); return {q, a.t * 0.5 / q}; }
+DQC_DEV Tan s_log(Tan a) { return {log(a.v), a.t / a.v}; }
+DQC_DEV Tan s_log1p(Tan a) { return {log1p(a.v), a.t / (1.0 + a.v)}; }
+DQC_DEV Tan s_exp(Tan a) { const double e = exp(a.v); return {e, a.t * e}; }
+DQC_DEV Tan s_expm1(Tan a) { return {expm1(a.v), a.t * exp(a.v)}; }
+DQC_DEV Tan s_atan(Tan a) { return {atan(a.v), a.t / (1.0 + a.v * a.v)}; }
+DQC_DEV Tan s_asinh(Tan a) { return {asinh(a.v), a.t / sqrt(1.0 + a.v * a.v)}; }
+DQC_DEV Tan s_pow(Tan a, double e) { const double f = pow(a.v, e); return {f, a.t * e * f / a.v}; }
+
+template <class S>
+struct DualT {  // value, d/drho, d/dsigma
+    S v, r, s;
+};
+using Dual = DualT<double>;
+template <class S = double>
+DQC_DEV DualT<S> mk(double v, double r = 0.0, double s = 0.0) { return DualT<S>{s_const<S>(v), s_const<S>(r), s_const<S>(s)}; }
+template <class S> DQC_DEV DualT<S> operator+(DualT<S> a, DualT<S> b) { return {a.v + b.v, a.r + b.r, a.s + b.s}; }
+template <class S> DQC_DEV DualT<S> operator-(DualT<S> a, DualT<S> b) { return {a.v - b.v, a.r - b.r, a.s - b.s}; }
+template <class S> DQC_DEV DualT<S> operator*(DualT<S> a, DualT<S> b) { return {a.v * b.v, a.r * b.v + a.v * b.r, a.s * b.v + a.v * b.s}; }
+template <class S> DQC_DEV DualT<S> operator/(DualT<S> a, DualT<S> b) {
+    S q = a.v / b.v, ib = 1.0 / b.v;
     return {q, (a.r - q * b.r) * ib, (a.s - q * b.s) * ib};
 }
-DQC_DEV Dual operator+(double a, Dual b) { return {a + b.v, b.r, b.s}; }
-DQC_DEV Dual operator+(Dual a, double b) { return {a.v + b, a.r, a.s}; }
-DQC_DEV Dual operator-(double a, Dual b) { return {a - b.v, -b.r, -b.s}; }
-DQC_DEV Dual operator-(Dual a, double b) { return {a.v - b, a.r, a.s}; }
-DQC_DEV Dual operator*(double a, Dual b) { return {a * b.v, a * b.r, a * b.s}; }
-DQC_DEV Dual operator*(Dual a, double b) { return {a.v * b, a.r * b, a.s * b}; }
-DQC_DEV Dual operator/(Dual a, double b) { double ib = 1.0 / b; return {a.v * ib, a.r * ib, a.s * ib}; }
-DQC_DEV Dual operator/(double a, Dual b) { return mk(a) / b; }
-DQC_DEV Dual dlog1p(Dual a) { double d = 1.0 / (1.0 + a.v); return {log1p(a.v), a.r * d, a.s * d}; }
-DQC_DEV Dual dexpm1(Dual a) { double e = exp(a.v); return {expm1(a.v), a.r * e, a.s * e}; }
-DQC_DEV Dual dsqrt(Dual a) { double q = sqrt(a.v), d = 0.5 / q; return {q, a.r * d, a.s * d}; }
-DQC_DEV Dual dcbrt(Dual a) { double q = cbrt(a.v), d = q / (3.0 * a.v); return {q, a.r * d, a.s * d}; }
+template <class S> DQC_DEV DualT<S> operator+(double a, DualT<S> b) { return {a + b.v, b.r, b.s}; }
+template <class S> DQC_DEV DualT<S> operator+(DualT<S> a, double b) { return {a.v + b, a.r, a.s}; }
+template <class S> DQC_DEV DualT<S> operator-(double a, DualT<S> b) { return {a - b.v, -b.r, -b.s}; }
+template <class S> DQC_DEV DualT<S> operator-(DualT<S> a, double b) { return {a.v - b, a.r, a.s}; }
+template <class S> DQC_DEV DualT<S> operator*(double a, DualT<S> b) { return {a * b.v, a * b.r, a * b.s}; }
+template <class S> DQC_DEV DualT<S> operator*(DualT<S> a, double b) { return {a.v * b, a.r * b, a.s * b}; }
+template <class S> DQC_DEV DualT<S> operator/(DualT<S> a, double b) { double ib = 1.0 / b; return {a.v * ib, a.r * ib, a.s * ib}; }
+template <class S> DQC_DEV DualT<S> operator/(double a, DualT<S> b) { return mk<S>(a) / b; }
+template <class S> DQC_DEV DualT<S> dlog1p(DualT<S> a) { S d = 1.0 / (1.0 + a.v); return {s_log1p(a.v), a.r * d, a.s * d}; }
+template <class S> DQC_DEV DualT<S> dexpm1(DualT<S> a) { S e = s_exp(a.v); return {s_expm1(a.v), a.r * e, a.s * e}; }
+template <class S> DQC_DEV DualT<S> dsqrt(DualT<S> a) { S q = s_sqrt(a.v), d = 0.5 / q; return {q, a.r * d, a.s * d}; }
+template <class S> DQC_DEV DualT<S> dcbrt(DualT<S> a) { S q = s_cbrt(a.v), d = q / (3.0 * a.v); return {q, a.r * d, a.s * d}; }
 
-DQC_DEV Dual dlog(Dual a) { double d = 1.0 / a.v; return {log(a.v), a.r * d, a.s * d}; }
-DQC_DEV Dual datan(Dual a) { double d = 1.0 / (1.0 + a.v * a.v); return {atan(a.v), a.r * d, a.s * d}; }
-DQC_DEV Dual dexp(Dual a) { double e = exp(a.v); return {e, a.r * e, a.s * e}; }
+template <class S> DQC_DEV DualT<S> dlog(DualT<S> a) { S d = 1.0 / a.v; return {s_log(a.v), a.r * d, a.s * d}; }
+template <class S> DQC_DEV DualT<S> datan(DualT<S> a) { S d = 1.0 / (1.0 + a.v * a.v); return {s_atan(a.v), a.r * d, a.s * d}; }
+template <class S> DQC_DEV DualT<S> dexp(DualT<S> a) { S e = s_exp(a.v); return {e, a.r * e, a.s * e}; }
 // g(y) = x asinh(x), x = sqrt(y): smooth in y = x^2 (the reduced gradient enters B88 only through it), g'(y) = (asinh(x)/x + 1/sqrt(1+y))/2
-DQC_DEV double xasinhx_val(double y, double &dg) {
-    const double x = sqrt(y);
-    const double ax = x > 1e-4 ? asinh(x) / x : 1.0 - y / 6.0 + 3.0 * y * y / 40.0;
-    dg = 0.5 * (ax + 1.0 / sqrt(1.0 + y));
+template <class S>
+DQC_DEV S xasinhx_val(S y, S &dg) {
+    const S x = s_sqrt(y);
+    const S ax = s_val(x) > 1e-4 ? s_asinh(x) / x : 1.0 - y / 6.0 + 3.0 * y * y / 40.0;
+    dg = 0.5 * (ax + 1.0 / s_sqrt(1.0 + y));
     return y * ax;
 }
-DQC_DEV Dual dxasinhx(Dual y) { double dg; const double v = xasinhx_val(y.v, dg); return {v, y.r * dg, y.s * dg}; }
+template <class S> DQC_DEV DualT<S> dxasinhx(DualT<S> y) { S dg; const S v = xasinhx_val(y.v, dg); return {v, y.r * dg, y.s * dg}; }
 
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kPbeKappa_ = 0.8040, kPbeMu_ = 0.2195149727645171;
 
-// number-type-generic spellings (Dual here, the five-variable D5 of the spin-polarised kernel in xc.hip) for the functionals that
+// number-type-generic spellings (DualT here, the five-variable D5T of the spin-polarised kernel in xc.hip) for the functionals that
 // are written once as templates: the exchange functionals given by an enhancement factor, PZ81 and P86
-DQC_DEV Dual dpow(Dual a, double e) { const double f = pow(a.v, e), d = e * f / a.v; return {f, a.r * d, a.s * d}; }
-DQC_DEV Dual n_exp(Dual a) { return dexp(a); }
-DQC_DEV Dual n_log(Dual a) { return dlog(a); }
-DQC_DEV Dual n_log1p(Dual a) { return dlog1p(a); }
-DQC_DEV Dual n_sqrt(Dual a) { return dsqrt(a); }
-DQC_DEV Dual n_cbrt(Dual a) { return dcbrt(a); }
-DQC_DEV Dual n_pow(Dual a, double e) { return dpow(a, e); }
-DQC_DEV Dual n_xasinhx(Dual a) { return dxasinhx(a); }
-DQC_DEV Dual n_floor(Dual a, double lo) { return a.v < lo ? Dual{lo, 0.0, 0.0} : a; }
+template <class S> DQC_DEV DualT<S> dpow(DualT<S> a, double e) { const S f = s_pow(a.v, e), d = e * f / a.v; return {f, a.r * d, a.s * d}; }
+template <class S> DQC_DEV DualT<S> n_exp(DualT<S> a) { return dexp(a); }
+template <class S> DQC_DEV DualT<S> n_log(DualT<S> a) { return dlog(a); }
+template <class S> DQC_DEV DualT<S> n_log1p(DualT<S> a) { return dlog1p(a); }
+template <class S> DQC_DEV DualT<S> n_sqrt(DualT<S> a) { return dsqrt(a); }
+template <class S> DQC_DEV DualT<S> n_cbrt(DualT<S> a) { return dcbrt(a); }
+template <class S> DQC_DEV DualT<S> n_pow(DualT<S> a, double e) { return dpow(a, e); }
+template <class S> DQC_DEV DualT<S> n_xasinhx(DualT<S> a) { return dxasinhx(a); }
+template <class S> DQC_DEV DualT<S> n_floor(DualT<S> a, double lo) { return s_val(a.v) < lo ? mk<S>(lo) : a; }
 
 // ---------------------------------------------------------------------------------------------
 // Exchange GGAs as a TABLE of enhancement factors (round 4): e_x = -(3/4)(3/pi)^(1/3) rho^(4/3) F(s^2), s = |grad rho| / (2 k_F rho);
@@ -73,7 +121,7 @@ DQC_DEV Dual n_floor(Dual a, double lo) { return a.v < lo ? Dual{lo, 0.0, 0.0} :
 // ---------------------------------------------------------------------------------------------
 constexpr double kX2S = 0.1282782438530421943003109254455883701296;   // 1 / (2 (6 pi^2)^(1/3))
 constexpr double kXFactorC = 0.9305257363491000250020102180716672510262;  // (3/8) (3/pi)^(1/3) 4^(2/3)
-__host__ __device__ inline bool xc_id_is_x_enh(int id) {
+__host__ __device__ constexpr bool xc_id_is_x_enh(int id) {
     return id == DQC_XC_GGA_X_PW91 || id == DQC_XC_GGA_X_B86 || id == DQC_XC_GGA_X_G96 || id == DQC_XC_GGA_X_PW86 ||
            id == DQC_XC_GGA_X_OPTX || id == DQC_XC_GGA_X_WC;
 }
@@ -129,7 +177,7 @@ template <class T>
 DQC_DEV T pz81_channel(T rs, int i) {
     const double gam[2] = {-0.1423, -0.0843}, b1[2] = {1.0529, 1.3981}, b2[2] = {0.3334, 0.2611};
     const double A[2] = {0.0311, 0.01555}, B[2] = {-0.048, -0.0269}, C[2] = {0.0020, 0.0007}, D[2] = {-0.0116, -0.0048};
-    if (rs.v >= 1.0) return gam[i] / (1.0 + b1[i] * n_sqrt(rs) + b2[i] * rs);
+    if (s_val(rs.v) >= 1.0) return gam[i] / (1.0 + b1[i] * n_sqrt(rs) + b2[i] * rs);
     T lr = n_log(rs);
     return A[i] * lr + B[i] + C[i] * (rs * lr) + D[i] * rs;
 }
@@ -153,45 +201,53 @@ DQC_DEV T p86_gradient_term(T rho, T sigma, T dz, bool pol) {
     return pol ? H / dz : H;
 }
 
-DQC_DEV Dual f_lda_x(Dual rho) {
+template <class S>
+DQC_DEV DualT<S> f_lda_x(DualT<S> rho) {
+    using Dual = DualT<S>;
     const double c = -0.75 * 0.98474502184269641;  // -(3/4) (3/pi)^(1/3)
     Dual r13 = dcbrt(rho);
     return c * (rho * r13);
 }
 
 // PW92 correlation energy per particle, unpolarised; a = 0.0310907 (lda_c_pw) or (1-ln2)/pi^2 (pw_mod)
-DQC_DEV Dual pw92_eps(Dual rho, double a) {
+template <class S>
+DQC_DEV DualT<S> pw92_eps(DualT<S> rho, double a) {
+    using Dual = DualT<S>;
     const double alpha1 = 0.21370, b1 = 7.5957, b2 = 3.5876, b3 = 1.6382, b4 = 0.49294;
-    Dual rs = dcbrt(mk(3.0 / (4.0 * kPi)) / rho);
+    Dual rs = dcbrt(mk<S>(3.0 / (4.0 * kPi)) / rho);
     Dual sq = dsqrt(rs);
     Dual q1 = (2.0 * a) * (b1 * sq + b2 * rs + b3 * (rs * sq) + b4 * (rs * rs));
     return (-2.0 * a) * (1.0 + alpha1 * rs) * dlog1p(1.0 / q1);
 }
 
-DQC_DEV Dual f_lda_c_pw(Dual rho) { return rho * pw92_eps(rho, 0.0310907); }
-DQC_DEV Dual f_lda_c_pw_mod(Dual rho) { return rho * pw92_eps(rho, 0.031090690869654895); }
+template <class S> DQC_DEV DualT<S> f_lda_c_pw(DualT<S> rho) { return rho * pw92_eps(rho, 0.0310907); }
+template <class S> DQC_DEV DualT<S> f_lda_c_pw_mod(DualT<S> rho) { return rho * pw92_eps(rho, 0.031090690869654895); }
 
 // the PBE exchange family: enhancement factor F(s^2) = 1 + kappa - kappa / (1 + mu s^2 / kappa) with (kappa, mu) =
 // (0.804, 0.21951) PBE, (1.245, 0.21951) revPBE, (0.804, 10/81) PBEsol; RPBE: F = 1 + kappa (1 - exp(-mu s^2 / kappa))
 constexpr double kPbeKappa = 0.8040, kPbeMu = 0.2195149727645171, kPbeBeta = 0.06672455060314922;
-DQC_DEV Dual f_gga_x_pbe(Dual rho, Dual sigma, double kappa = kPbeKappa, double mu = kPbeMu, bool rpbe = false) {
+template <class S>
+DQC_DEV DualT<S> f_gga_x_pbe(DualT<S> rho, DualT<S> sigma, double kappa = kPbeKappa, double mu = kPbeMu, bool rpbe = false) {
+    using Dual = DualT<S>;
     const double c2 = 4.0 * 9.5707800006273038;  // 4 (3 pi^2)^(2/3)
     Dual r13 = dcbrt(rho);
     Dual r43 = rho * r13;
     Dual s2 = sigma / (c2 * (r43 * r43));
-    Dual F = rpbe ? (1.0 + kappa) - kappa * dexp(mk(0.0) - (mu / kappa) * s2) : (1.0 + kappa) - kappa / (1.0 + (mu / kappa) * s2);
+    Dual F = rpbe ? (1.0 + kappa) - kappa * dexp(mk<S>(0.0) - (mu / kappa) * s2) : (1.0 + kappa) - kappa / (1.0 + (mu / kappa) * s2);
     const double c = -0.75 * 0.98474502184269641;
     return c * (r43 * F);
 }
 
 // PBE correlation; beta = 0.066725 (PBE) or 0.046 (PBEsol)
-DQC_DEV Dual f_gga_c_pbe(Dual rho, Dual sigma, double beta = kPbeBeta) {
+template <class S>
+DQC_DEV DualT<S> f_gga_c_pbe(DualT<S> rho, DualT<S> sigma, double beta = kPbeBeta) {
+    using Dual = DualT<S>;
     const double gamma = 0.031090690869654895;  // (1 - ln 2)/pi^2
     Dual eps = pw92_eps(rho, gamma);
     Dual kf = dcbrt((3.0 * kPi * kPi) * rho);
     Dual ks2 = (4.0 / kPi) * kf;
     Dual t2 = sigma / (4.0 * (ks2 * (rho * rho)));
-    Dual A = mk(beta / gamma) / dexpm1(mk(0.0) - eps / gamma);
+    Dual A = mk<S>(beta / gamma) / dexpm1(mk<S>(0.0) - eps / gamma);
     Dual At2 = A * t2;
     Dual X = (beta / gamma) * t2 * (1.0 + At2) / (1.0 + At2 + At2 * At2);
     Dual H = gamma * dlog1p(X);
@@ -209,14 +265,18 @@ DQC_DEV T vwn_fit(T x, double A, double b, double c, double x0, FL flog, FA fata
 }
 
 // lda_c_vwn (libxc id 7 = VWN5), unpolarised: the paramagnetic fit
-DQC_DEV Dual f_lda_c_vwn(Dual rho) {
-    Dual x = dsqrt(dcbrt(mk(3.0 / (4.0 * kPi)) / rho));
+template <class S>
+DQC_DEV DualT<S> f_lda_c_vwn(DualT<S> rho) {
+    using Dual = DualT<S>;
+    Dual x = dsqrt(dcbrt(mk<S>(3.0 / (4.0 * kPi)) / rho));
     return rho * vwn_fit(x, 0.0310907, 3.72744, 12.9352, -0.10498, [](Dual a) { return dlog(a); }, [](Dual a) { return datan(a); });
 }
 
 // gga_x_b88 (Becke, PRA 38, 3098 (1988)): e = sum_s -rho_s^(4/3) [Cx + beta x_s^2 / (1 + 6 beta x_s asinh x_s)], x_s = |grad rho_s| / rho_s^(4/3);
 // unpolarised: rho_s = rho / 2, sigma_ss = sigma / 4
-DQC_DEV Dual f_gga_x_b88(Dual rho, Dual sigma) {
+template <class S>
+DQC_DEV DualT<S> f_gga_x_b88(DualT<S> rho, DualT<S> sigma) {
+    using Dual = DualT<S>;
     const double beta = 0.0042, cx = 0.9305257363491;  // (3/2) (3 / (4 pi))^(1/3)
     Dual rs_ = 0.5 * rho;
     Dual r43 = rs_ * dcbrt(rs_);
@@ -227,7 +287,9 @@ DQC_DEV Dual f_gga_x_b88(Dual rho, Dual sigma) {
 // gga_c_lyp (Lee, Yang, Parr, PRB 37, 785 (1988) in the gradient-only form of Miehlich et al., CPL 157, 200 (1989)), closed shell:
 //   e = -a rho / (1 + d rho^(-1/3)) - a b omega [ C_F rho^(14/3) - rho^2 sigma (1/24 + 7 delta / 72) ]
 //   omega = exp(-c rho^(-1/3)) / (1 + d rho^(-1/3)) rho^(-11/3),  delta = c rho^(-1/3) + d rho^(-1/3) / (1 + d rho^(-1/3))
-DQC_DEV Dual f_gga_c_lyp(Dual rho, Dual sigma) {
+template <class S>
+DQC_DEV DualT<S> f_gga_c_lyp(DualT<S> rho, DualT<S> sigma) {
+    using Dual = DualT<S>;
     const double a = 0.04918, b = 0.132, c = 0.2533, d = 0.349, CF = 2.8712340001881915;  // (3/10) (3 pi^2)^(2/3)
     Dual r13 = dcbrt(rho);
     Dual ir13 = 1.0 / r13;
@@ -235,15 +297,15 @@ DQC_DEV Dual f_gga_c_lyp(Dual rho, Dual sigma) {
     Dual delta = c * ir13 + d * ir13 / den;
     Dual r2 = rho * rho;
     Dual r113 = r2 * rho * r13 * r13;                 // rho^(11/3)
-    Dual omega = dexp(mk(0.0) - c * ir13) / (den * r113);
+    Dual omega = dexp(mk<S>(0.0) - c * ir13) / (den * r113);
     Dual bracket = CF * (r113 * rho) - r2 * sigma * ((1.0 / 24.0) + (7.0 / 72.0) * delta);
-    return mk(0.0) - a * (rho / den) - (a * b) * (omega * bracket);
+    return mk<S>(0.0) - a * (rho / den) - (a * b) * (omega * bracket);
 }
 
-__host__ __device__ inline bool xc_id_is_lda(int id) {
+__host__ __device__ constexpr bool xc_id_is_lda(int id) {
     return id == DQC_XC_LDA_X || id == DQC_XC_LDA_C_PW || id == DQC_XC_LDA_C_PW_MOD || id == DQC_XC_LDA_C_VWN || id == DQC_XC_LDA_C_PZ;
 }
-__host__ __device__ inline bool xc_id_is_gga(int id) {
+__host__ __device__ constexpr bool xc_id_is_gga(int id) {
     return id == DQC_XC_GGA_X_PBE || id == DQC_XC_GGA_C_PBE || id == DQC_XC_GGA_X_B88 || id == DQC_XC_GGA_C_LYP || id == DQC_XC_GGA_X_PBE_R ||
            id == DQC_XC_GGA_X_PBE_SOL || id == DQC_XC_GGA_X_RPBE || id == DQC_XC_GGA_C_PBE_SOL || id == DQC_XC_GGA_C_P86 || xc_id_is_x_enh(id);
 }
@@ -253,11 +315,11 @@ inline bool xc_host_is_gga(int id) { return xc_id_is_gga(id); }
 // the functionals of round 4 (enhancement-factor exchange, PZ81, P86): kernels that may see one are compiled as their own
 // instantiation (EXT) -- folded into the one switch they cost the PBE / LDA kernels their registers (xc_kernel 34 -> 80 us on a
 // 20-atom grid) although no such term was asked for
-__host__ __device__ inline bool xc_id_is_ext(int id) { return xc_id_is_x_enh(id) || id == DQC_XC_LDA_C_PZ || id == DQC_XC_GGA_C_P86; }
+__host__ __device__ constexpr bool xc_id_is_ext(int id) { return xc_id_is_x_enh(id) || id == DQC_XC_LDA_C_PZ || id == DQC_XC_GGA_C_P86; }
 
 // one LDA / GGA functional of the kernel set at (rho, sigma) with its first derivatives
-template <bool EXT>
-DQC_DEV Dual f_lda_gga(int id, Dual dr, Dual ds) {
+template <bool EXT, class S = double>
+DQC_DEV DualT<S> f_lda_gga(int id, DualT<S> dr, DualT<S> ds) {
     if constexpr (EXT) {
         if (xc_id_is_x_enh(id)) return gga_x_by_enh(id, dr, ds);
         if (id == DQC_XC_LDA_C_PZ) return dr * pz81_eps(dr, dr, false);

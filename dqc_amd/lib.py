@@ -105,6 +105,8 @@ def load():
     lib.dqc_xc_eval.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_quad.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_pol.argtypes = [c_dp] * 9 + [c_int, ip, dp, c_int, c_vp]
+    lib.dqc_xc_eval_fxc.argtypes = [c_dp] * 6 + [c_int, c_int, ip, dp, c_int, c_vp]
+    lib.dqc_xc_eval_fxc_pol.argtypes = [c_dp] * 12 + [c_int, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_mgga.argtypes = [c_dp] * 7 + [c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_mgga_pol.argtypes = [c_dp] * 11 + [c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_mgga_pol2.argtypes = [c_dp] * 12 + [c_int, ip, dp, c_int, c_vp]
@@ -121,6 +123,9 @@ def load():
     lib.dqc_fock_finish.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_dp, c_int, c_int, c_int, c_vp]
     lib.dqc_fock_finish_hybrid.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.c_double, ctypes.c_double, c_dp, c_dp, c_dp, c_int,
                                            c_int, c_vp]
+    ll = ctypes.c_longlong
+    lib.dqc_resp_gemm.argtypes = [c_dp, c_dp, c_dp] + [c_int] * 6 + [ll, ll, ll, c_int, c_int, ctypes.c_double, c_dp, c_dp, c_dp, c_vp]
+    lib.dqc_resp_kappa2dm.argtypes = [c_dp] * 5 + [c_int] * 4 + [ctypes.c_double, c_vp]
     lib.dqc_padded_norb.argtypes = [c_int]
     lib.dqc_padded_norb.restype = c_int
     lib.dqc_grid_density_lr.argtypes = [c_dp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp, c_int, c_vp]
@@ -895,6 +900,49 @@ def xc_eval_pol(terms, rho_u, rho_d, grho_u, grho_d, want_e=True, want_v=True):
     return e, (vu, vd), (gu, gd)
 
 
+def _fxc_terms(terms, who):
+    for _, nm in terms:
+        if nm.startswith("mgga_"):
+            raise NotImplementedError("%s: no second-order kernel for the meta-GGA functional %s (LDA and GGA only)" % (who, nm))
+    ids = (ctypes.c_int * len(terms))(*[XC_IDS[nm] for _, nm in terms])
+    cfs = (ctypes.c_double * len(terms))(*[float(c) for c, _ in terms])
+    return ids, cfs
+
+
+def xc_eval_fxc(terms, rho, grho, drho, dgrho):
+    """second functional derivatives contracted with nvec trial responses: rho (n,), grho (3, n) or None (LDA); drho (nvec, n),
+    dgrho (nvec, 3, n) or None -> dvrho (nvec, n), dvgrad (nvec, 3, n) or None = d(2 vsigma grad rho), the layout of xc_eval"""
+    ids, cfs = _fxc_terms(terms, "xc_eval_fxc")
+    nvec, n = drho.shape
+    gga = grho is not None and dgrho is not None
+    rho, drho = rho.contiguous(), drho.contiguous()
+    grho, dgrho = (grho.contiguous(), dgrho.contiguous()) if gga else (None, None)
+    dv = torch.empty_like(drho)
+    dvg = torch.empty((nvec, 3, n), dtype=torch.float64, device=rho.device) if gga else None
+    with _on(rho.device) as st_:
+        _check(load().dqc_xc_eval_fxc(_ptr(dv), _ptr(dvg), _ptr(rho), _ptr(grho), _ptr(drho), _ptr(dgrho), n, nvec, ids, cfs,
+                                      len(terms), st_), "dqc_xc_eval_fxc")
+    return dv, dvg
+
+
+def xc_eval_fxc_pol(terms, rho_u, rho_d, grho_u, grho_d, drho_u, drho_d, dgrho_u, dgrho_d):
+    """spin-polarised xc_eval_fxc -> (dvrho_u, dvrho_d), (dvgrad_u, dvgrad_d) (None for LDA), each (nvec, n) / (nvec, 3, n)"""
+    ids, cfs = _fxc_terms(terms, "xc_eval_fxc_pol")
+    nvec, n = drho_u.shape
+    gga = grho_u is not None and dgrho_u is not None
+    c = lambda t: None if (t is None or not gga) else t.contiguous()  # noqa: E731
+    rho_u, rho_d, drho_u, drho_d = rho_u.contiguous(), rho_d.contiguous(), drho_u.contiguous(), drho_d.contiguous()
+    grho_u, grho_d, dgrho_u, dgrho_d = c(grho_u), c(grho_d), c(dgrho_u), c(dgrho_d)
+    dvu, dvd = torch.empty_like(drho_u), torch.empty_like(drho_u)
+    dgu = torch.empty((nvec, 3, n), dtype=torch.float64, device=rho_u.device) if gga else None
+    dgd = torch.empty((nvec, 3, n), dtype=torch.float64, device=rho_u.device) if gga else None
+    with _on(rho_u.device) as st_:
+        _check(load().dqc_xc_eval_fxc_pol(_ptr(dvu), _ptr(dvd), _ptr(dgu), _ptr(dgd), _ptr(rho_u), _ptr(rho_d), _ptr(grho_u), _ptr(grho_d),
+                                          _ptr(drho_u), _ptr(drho_d), _ptr(dgrho_u), _ptr(dgrho_d), n, nvec, ids, cfs, len(terms), st_),
+               "dqc_xc_eval_fxc_pol")
+    return (dvu, dvd), (dgu, dgd)
+
+
 def xc_eval_mgga(terms, rho, grho, tau, want_e=True, want_v=True):
     """-> edens, vrho, vgrad (3,n), vtau"""
     n = rho.shape[0]
@@ -1042,6 +1090,35 @@ def fock_finish_hybrid(work, x, nao, kfrac, vxc, vscale=None, exc=None, core=Non
                                              0.0 if vscale is None else float(vscale), float(kfrac), _ptr(exc), _ptr(core), _ptr(x),
                                              int(nao), int(north), st_), "dqc_fock_finish_hybrid")
     return fock, en
+
+
+def resp_kappa2dm(kappa, cv, co, scale):
+    """kappa (nvec, nv, no), C_v (nao, nv), C_o (nao, no) -> dD (nvec, nao, nao) = scale (C_v kappa C_o^T + transpose), two launches"""
+    nvec, nv, no = kappa.shape
+    nao = cv.shape[0]
+    dm = torch.empty((nvec, nao, nao), dtype=torch.float64, device=kappa.device)
+    t = torch.empty((nvec, nao, no), dtype=torch.float64, device=kappa.device)
+    with _on(kappa.device) as st_:
+        _check(load().dqc_resp_kappa2dm(_ptr(dm), _ptr(t), _ptr(kappa.contiguous()), _ptr(cv), _ptr(co), nao, nv, no, nvec, float(scale), st_),
+               "dqc_resp_kappa2dm")
+    return dm
+
+
+def resp_project(g, cv, co, alpha, ev=None, eo=None, kappa=None):
+    """g (nvec, nao, nao) -> alpha (C_v^T g[v] C_o) (nvec, nv, no), plus alpha (ev[a] - eo[i]) kappa[v][a][i] when kappa is given: two
+    launches (U = g C_o, then the projection with the diagonal term in its epilogue)"""
+    nvec, nao = g.shape[0], g.shape[1]
+    nv, no = cv.shape[1], co.shape[1]
+    u = torch.empty((nvec, nao, no), dtype=torch.float64, device=g.device)
+    out = torch.empty((nvec, nv, no), dtype=torch.float64, device=g.device)
+    g = g.contiguous()
+    with _on(g.device) as st_:
+        _check(load().dqc_resp_gemm(_ptr(u), _ptr(g), _ptr(co), nao, no, nao, nao, no, no, nao * nao, 0, nao * no, 0, nvec, 1.0, None, None,
+                                    None, st_), "dqc_resp_gemm[G C_o]")
+    with _on(g.device) as st_:
+        _check(load().dqc_resp_gemm(_ptr(out), _ptr(cv), _ptr(u), nv, no, nao, nv, no, no, 0, nao * no, nv * no, 1, nvec, float(alpha),
+                                    _ptr(ev), _ptr(eo), _ptr(None if kappa is None else kappa.contiguous()), st_), "dqc_resp_gemm[C_v^T U]")
+    return out
 
 
 def probe_stream_read(buf):

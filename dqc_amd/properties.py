@@ -60,6 +60,55 @@ def equadrupole(qc, unit="Debye*Angst"):
     return (elec + ion) * _unit(_QUADRUPOLE_UNITS, unit, "quadrupole")
 
 
+def _memo(qc, key, fcn):
+    """results of the orbital-Hessian properties are kept on the calculation object, for the converged state it holds: another
+    run() of the same object starts them afresh (response.state_memo)"""
+    from .response import state_memo
+    memo = state_memo(qc)
+    if key not in memo:
+        memo[key] = fcn()
+    return memo[key]
+
+
+def lowest_eival_orb_hessian(qc, tol=1e-6):
+    """lowest eigenvalue (one-element tensor) of the Hessian of the energy with respect to the orbital rotations, by block Davidson
+    on Hessian-vector products (dqc_amd/response.py: the variables are the non-redundant virtual <- occupied rotations
+    kappa_ai of C exp(kappa - kappa^T); `tol` is the residual norm of the eigenpair).
+
+    Difference from the reference (dqc/api/properties.py:238-299): it differentiates the energy with respect to a QR
+    parametrisation of the occupied orbitals, which contains redundant occupied-occupied directions.  The energy of equally occupied
+    orbitals does not change along them, so they contribute zero eigenvalues: the reference's value is min(0, this one).  The sign
+    test of `is_orb_min` is the same for both.
+
+    A Davidson iteration that stops short of `tol` warns: its value is then only an upper bound of the lowest eigenvalue."""
+    from .response import orbital_hessian
+    return _memo(qc, ("lowest_eival", float(tol)), lambda: orbital_hessian(qc).lowest(neig=1, tol=tol)[0].reshape(1))
+
+
+def is_orb_min(qc, threshold=-1e-3):
+    """True when the converged SCF state is a minimum with respect to orbital rotations, not a saddle point or an excited state:
+    the lowest eigenvalue of the orbital Hessian is above `threshold` (dqc/api/properties.py:301-319)"""
+    eival = lowest_eival_orb_hessian(qc)
+    return bool(torch.all(eival > threshold))
+
+
+def polarizability(qc, tol=1e-9):
+    """analytic static polarizability alpha[e, d] = d mu_e / d F_d (3, 3), atomic units: the response equations
+    H U_d = -d2E / dkappa dF_d are solved by preconditioned conjugate gradients on Hessian-vector products (dqc_amd/response.py), with
+    the dipole integrals `r0` of `edipole`; alpha[e, d] = -g_e . U_d, g_d = d2E / dkappa dF_d.  Needs a stable SCF state: on a saddle point the solver raises RuntimeError
+    when a search direction meets non-positive curvature (a field that does not couple to the unstable mode cannot notice it:
+    `is_orb_min` is the check); an unconverged solve warns."""
+    from .response import orbital_hessian
+
+    def compute():
+        oh = orbital_hessian(qc)
+        h = qc.get_system().get_hamiltonian()
+        g = oh.gradient_of(lib.int1e("r0", h._tab, h.device))  # (3, n)
+        u = oh.solve(-g, tol=tol)
+        return -(g @ u.T)
+    return _memo(qc, ("polarizability", float(tol)), compute)
+
+
 def optimal_geometry(qc, length_unit=None, gtol=1e-5, maxiter=200):
     """atom positions (natoms, 3) that minimise the SCF energy (properties.py:321-341, 486-510).  The reference minimises by
     autograd gradients of the energy with respect to the positions; here every step is a fresh `Mol.make_copy(moldesc=...)` +

@@ -131,6 +131,16 @@ int dqc_fock_finish(double *d_fock, double *d_energies, double *d_j_ao, double *
 int dqc_fock_finish_hybrid(double *d_fock, double *d_energies, double *d_work, const double *d_vxc, int ldv, int vraw, double vscale,
                            double kfrac, const double *d_exc, const double *d_core, const double *d_x, int nao, int north, void *stream);
 
+/* the small ends of an orbital-Hessian product (dqc_amd/response.py), tile-parallel and batched over nbatch / nvec trial vectors:
+ * dqc_resp_gemm: C[v] (M x N, row stride ldc, batch stride sc) = alpha op(A[v]) B[v], plus alpha (ea[m] - eb[n]) X[v][m][n] when d_x
+ * (dense (nbatch, M, N)) is given; op(A) = A (M x K) or, with transa, A^T (A stored K x M); sa / sb = 0: one operand for all.
+ * dqc_resp_kappa2dm: dD[v] = scale (C_v kappa[v] C_o^T + transpose) (nvec, nao, nao); d_t: scratch of nvec nao n_occ doubles. */
+int dqc_resp_gemm(double *d_c, const double *d_a, const double *d_b, int M, int N, int K, int lda, int ldb, int ldc, long long sa,
+                  long long sb, long long sc, int transa, int nbatch, double alpha, const double *d_ea, const double *d_eb, const double *d_x,
+                  void *stream);
+int dqc_resp_kappa2dm(double *d_dm, double *d_t, const double *d_kappa, const double *d_cv, const double *d_co, int nao, int nv, int no,
+                      int nvec, double scale, void *stream);
+
 /* Several density matrices in ONE pass over the tiles (unrestricted HF: J[D_u + D_d], K[2 D_u], K[2 D_d],
  * hcgto.py:238-241, hf.py:93-103; batched dm, base_hamilton.py:92-93).
  * d_dmJ (nj, nao, nao) -> d_J (nj, nao, nao);  d_dmK (nk, nao, nao) -> d_K (nk, nao, nao); either count may be 0.
@@ -212,6 +222,22 @@ int dqc_xc_eval_pol(double *d_edens, double *d_vrho_u, double *d_vrho_d, double 
 int dqc_xc_eval_mgga(double *d_edens, double *d_vrho, double *d_vgrad, double *d_vtau, const double *d_rho,
                      const double *d_grho, const double *d_tau, int n, const int *ids, const double *coefs,
                      int nterm, void *stream);
+
+/* SECOND functional derivatives (the response kernel f_xc): the change of the potentials dqc_xc_eval / dqc_xc_eval_pol write
+ * under a change of the density, for nvec trial responses at once, analytically (the functional bodies instantiated with a
+ * value-plus-tangent scalar).  Ground state d_rho (n), d_grho (3, n); responses d_drho (nvec, n), d_dgrho (nvec, 3, n).
+ * Outputs d_dvrho (nvec, n) = d v_rho and d_dvgrad (nvec, 3, n) = d (2 v_sigma grad rho) = 2 d v_sigma grad rho + 2 v_sigma
+ * grad d rho: per trial vector the (n), (3, n) layout of dqc_xc_eval, which dqc_grid_vxc consumes.  LDA-only term lists: the
+ * gradient arguments may be NULL.  Zero where rho <= 1e-15 (the cutoff of the first-order kernels).  LDA and GGA ids only
+ * (a DQC_XC_MGGA_* id is DQC_EINVAL). */
+int dqc_xc_eval_fxc(double *d_dvrho, double *d_dvgrad, const double *d_rho, const double *d_grho, const double *d_drho,
+                    const double *d_dgrho, int n, int nvec, const int *ids, const double *coefs, int nterm, void *stream);
+/* spin-polarised: d v_rho,s and d v_grad,u = 2 d v_uu grad rho_u + 2 v_uu grad d rho_u + d v_ud grad rho_d + v_ud grad d rho_d
+ * (u <-> d for the other spin), every derivative with the sigma_ud cross terms */
+int dqc_xc_eval_fxc_pol(double *d_dvrho_u, double *d_dvrho_d, double *d_dvgrad_u, double *d_dvgrad_d, const double *d_rho_u,
+                        const double *d_rho_d, const double *d_grho_u, const double *d_grho_d, const double *d_drho_u,
+                        const double *d_drho_d, const double *d_dgrho_u, const double *d_dgrho_d, int n, int nvec,
+                        const int *ids, const double *coefs, int nterm, void *stream);
 
 /* spin-polarised meta-GGA CORRELATION terms (CalcMGGALibXCPol, libxc_wrapper.py:221-378; DQC_XC_MGGA_C_SCAN): they depend
  * on rho_u, rho_d, |grad(rho_u + rho_d)|^2 and tau_u + tau_d only, so vsigma = (v, 2 v, v) for (uu, ud, dd) and both spins
