@@ -382,7 +382,8 @@ __global__ __launch_bounds__(FT_NT) void fock_out_kernel(double *__restrict__ fo
 //   resp_gemm_kernel   C[v] = alpha (op(A[v]) B[v])  [+ alpha (ea[m] - eb[n]) X[v][m][n]]       (batch stride 0: shared operand)
 //       T = C_v kappa (half-transformed rotation), U = G C_o, and the projection C_v^T U with the diagonal term
 //       (eps_a - eps_i) kappa_ai of canonical orbitals in its epilogue
-//   resp_dm_kernel     dD[v] = scale (T[v] C_o^T + C_o T[v]^T): ONE product over K = 2 n_occ, [T | C_o] [C_o | T]^T
+//   resp_dm_kernel     dD[v] = scale (T[v] C_o^T + sign C_o T[v]^T): ONE product over K = 2 n_occ, [T | C_o] [C_o | sign T]^T
+//       (sign = -1: the antisymmetric transition density of the A - B product)
 // One 4-wave block per 16 x 16 output tile (ft_tile): loads from clamped addresses, stores guarded.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FT_NT) void resp_gemm_kernel(double *__restrict__ c, const double *__restrict__ a, const double *__restrict__ b, int M,
@@ -415,7 +416,7 @@ __global__ __launch_bounds__(FT_NT) void resp_gemm_kernel(double *__restrict__ c
 }
 
 __global__ __launch_bounds__(FT_NT) void resp_dm_kernel(double *__restrict__ dm, const double *__restrict__ t_, const double *__restrict__ co,
-                                                        int nao, int no, double scale) {
+                                                        int nao, int no, double scale, double sign) {
     __shared__ double sred[4 * 256];
     const int lane = threadIdx.x & 63, lr = lane & 15, kq = lane >> 4;
     const int i0 = 16 * blockIdx.x, j0 = 16 * blockIdx.y, v = blockIdx.z;
@@ -429,7 +430,7 @@ __global__ __launch_bounds__(FT_NT) void resp_dm_kernel(double *__restrict__ dm,
         },
         [&](int k, int n) {
             const int nn = min(j0 + n, nao - 1), kk = min(k, K - 1);
-            const double val = kk < no ? co[(size_t)nn * no + kk] : t[(size_t)nn * no + (kk - no)];
+            const double val = kk < no ? co[(size_t)nn * no + kk] : sign * t[(size_t)nn * no + (kk - no)];
             return (j0 + n < nao && k < K) ? val : 0.0;
         }, sred);
     if (threadIdx.x < 64) {
@@ -603,8 +604,34 @@ int dqc_resp_kappa2dm(double *d_dm, double *d_t, const double *d_kappa, const do
     hipLaunchKernelGGL(resp_gemm_kernel, dim3((nao + 15) / 16, (no + 15) / 16, nvec), dim3(FT_NT), 0, st, d_t, d_cv, d_kappa, nao, no, nv, nv, no, no,
                        0LL, (long long)nv * no, (long long)nao * no, 0, 1.0, nullptr, nullptr, nullptr, 0LL);
     DQC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(resp_dm_kernel, dim3((nao + 15) / 16, (nao + 15) / 16, nvec), dim3(FT_NT), 0, st, d_dm, d_t, d_co, nao, no, scale);
+    hipLaunchKernelGGL(resp_dm_kernel, dim3((nao + 15) / 16, (nao + 15) / 16, nvec), dim3(FT_NT), 0, st, d_dm, d_t, d_co, nao, no, scale, 1.0);
     DQC_CHECK_LAUNCH();
+    return DQC_OK;
+}
+
+int dqc_resp_kappa2dm_pm(double *d_dm_plus, double *d_dm_minus, double *d_t, const double *d_kappa, const double *d_cv, const double *d_co,
+                         int nao, int nv, int no, int nvec, double scale, void *stream) {
+    // dD+[v] = scale (C_v kappa[v] C_o^T + transpose) and dD-[v] = scale (C_v kappa[v] C_o^T - transpose) from ONE half-transformation
+    // C_v kappa[v] (d_t, as dqc_resp_kappa2dm); either output may be null
+    using namespace dqc;
+    if (nvec <= 0 || nao <= 0) return DQC_OK;
+    if (nv <= 0 || no <= 0 || nvec > 65535 || (!d_dm_plus && !d_dm_minus) || !d_t || !d_kappa || !d_cv || !d_co) {
+        set_error("dqc_resp_kappa2dm_pm: needs n_virt > 0, n_occ > 0, an output and no null input");
+        return DQC_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(resp_gemm_kernel, dim3((nao + 15) / 16, (no + 15) / 16, nvec), dim3(FT_NT), 0, st, d_t, d_cv, d_kappa, nao, no, nv, nv, no, no,
+                       0LL, (long long)nv * no, (long long)nao * no, 0, 1.0, nullptr, nullptr, nullptr, 0LL);
+    DQC_CHECK_LAUNCH();
+    const dim3 grid((nao + 15) / 16, (nao + 15) / 16, nvec);
+    if (d_dm_plus) {
+        hipLaunchKernelGGL(resp_dm_kernel, grid, dim3(FT_NT), 0, st, d_dm_plus, d_t, d_co, nao, no, scale, 1.0);
+        DQC_CHECK_LAUNCH();
+    }
+    if (d_dm_minus) {
+        hipLaunchKernelGGL(resp_dm_kernel, grid, dim3(FT_NT), 0, st, d_dm_minus, d_t, d_co, nao, no, scale, -1.0);
+        DQC_CHECK_LAUNCH();
+    }
     return DQC_OK;
 }
 

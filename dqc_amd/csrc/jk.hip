@@ -430,9 +430,15 @@ __global__ __launch_bounds__(256, NK ? 3 : 1) void jk_multi_kernel(const double 
 }
 
 #undef JKM_LOAD
-// nmat matrices in / out: symmetrise + pad the densities, clear the accumulators
+// nmat matrices in / out: symmetrise + pad the densities, clear the accumulators.  kanti: bit q set = exchange density q of this
+// pass is ANTISYMMETRIC, (D - D^T) / 2 is what goes into the work buffer.  The tile kernels need no other change for it: every
+// exchange contraction reads D[bra block, ket block] in that order (D[J,K], D[I,K], D[J,L], D[I,L]: rows from the bra pair, columns
+// from the ket pair), and the weights f only count how many of the 8 permutations map a tile's ordered block quadruple onto
+// itself.  The four contractions cover the images that keep bra and ket in place; the four bra <-> ket images are their transposes
+// with D^T in place of D, so K[D] = acc[D] + acc[D^T]^T for ANY D: acc + acc^T for a symmetric, acc - acc^T for an antisymmetric D
+// (jk_multi_finish_kernel).
 __global__ void jk_multi_prep_kernel(double *__restrict__ work, const double *__restrict__ dmj, int nj, const double *__restrict__ dmk,
-                                     int nk, int nao, int npad) {
+                                     int nk, int nao, int npad, unsigned kanti) {
     const size_t n2 = (size_t)npad * npad, nn = (size_t)nao * nao;
     const int nd = nj + nk;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n2 * nd; e += (size_t)gridDim.x * blockDim.x) {
@@ -441,14 +447,15 @@ __global__ void jk_multi_prep_kernel(double *__restrict__ work, const double *__
         const int i = r / npad, j = r % npad;
         const double *dm = q < nj ? dmj + (size_t)q * nn : dmk + (size_t)(q - nj) * nn;
         double v = 0.0;
-        if (i < nao && j < nao) v = 0.5 * (dm[(size_t)i * nao + j] + dm[(size_t)j * nao + i]);
+        const bool anti = q >= nj && ((kanti >> (q - nj)) & 1u);
+        if (i < nao && j < nao) v = anti ? 0.5 * (dm[(size_t)i * nao + j] - dm[(size_t)j * nao + i]) : 0.5 * (dm[(size_t)i * nao + j] + dm[(size_t)j * nao + i]);
         work[e] = v;
         work[n2 * nd + e] = 0.0;
     }
 }
 
 __global__ void jk_multi_finish_kernel(double *__restrict__ J, int nj, double *__restrict__ K, int nk, const double *__restrict__ work,
-                                       int nao, int npad, const double *__restrict__ dscp) {
+                                       int nao, int npad, const double *__restrict__ dscp, unsigned kanti) {
     const double dsc = dscp ? *dscp : 0.0;
     const size_t n2 = (size_t)npad * npad, nn = (size_t)nao * nao;
     const double *acc = work + (size_t)(nj + nk) * n2;
@@ -456,7 +463,8 @@ __global__ void jk_multi_finish_kernel(double *__restrict__ J, int nj, double *_
         const int q = e / nn;
         const size_t r = e - (size_t)q * nn;
         const int i = r / nao, j = r % nao;
-        const double v = det_value(acc[q * n2 + (size_t)i * npad + j], dsc) + det_value(acc[q * n2 + (size_t)j * npad + i], dsc);
+        const double a = det_value(acc[q * n2 + (size_t)i * npad + j], dsc), at = det_value(acc[q * n2 + (size_t)j * npad + i], dsc);
+        const double v = (q >= nj && ((kanti >> (q - nj)) & 1u)) ? a - at : a + at;
         if (q < nj) J[e] = v;
         else K[e - (size_t)nj * nn] = v;
     }
@@ -988,8 +996,24 @@ size_t dqc_jk_multi_work_doubles(int nao, int nj, int nk) {
     return 2 * (size_t)(nj + (nk > 2 ? 2 : nk)) * npad * npad + 8;
 }
 
+static int jk_from_tiles_multi_impl(double *d_J, const double *d_dmJ, int nj, double *d_K, const double *d_dmK, int nk, const int *k_antisym,
+                                    const double *d_tiles, int nao, double *d_work, void *stream);
+
 int dqc_jk_from_tiles_multi(double *d_J, const double *d_dmJ, int nj, double *d_K, const double *d_dmK, int nk,
                             const double *d_tiles, int nao, double *d_work, void *stream) {
+    return jk_from_tiles_multi_impl(d_J, d_dmJ, nj, d_K, d_dmK, nk, nullptr, d_tiles, nao, d_work, stream);
+}
+
+int dqc_jk_from_tiles_multi_asym(double *d_J, const double *d_dmJ, int nj, double *d_K, const double *d_dmK, int nk, const int *k_antisym,
+                                 const double *d_tiles, int nao, double *d_work, void *stream) {
+    // dqc_jk_from_tiles_multi with a flag per exchange right-hand side (HOST array of nk ints; null: all symmetric): a flagged
+    // one is antisymmetrised, (D - D^T) / 2, and its K[D]_pq = (pr|qs) D_rs comes back antisymmetric.  Symmetric and antisymmetric
+    // right-hand sides share a pass (two per pass, in the order given); the unflagged results are those of dqc_jk_from_tiles_multi.
+    return jk_from_tiles_multi_impl(d_J, d_dmJ, nj, d_K, d_dmK, nk, k_antisym, d_tiles, nao, d_work, stream);
+}
+
+static int jk_from_tiles_multi_impl(double *d_J, const double *d_dmJ, int nj, double *d_K, const double *d_dmK, int nk, const int *k_antisym,
+                                    const double *d_tiles, int nao, double *d_work, void *stream) {
     using namespace dqc;
     if (nao <= 0 || (nj <= 0 && nk <= 0)) return DQC_OK;
     if (nj < 0 || nk < 0) { set_error("dqc_jk_from_tiles_multi: negative matrix count"); return DQC_EINVAL; }
@@ -1002,7 +1026,9 @@ int dqc_jk_from_tiles_multi(double *d_J, const double *d_dmJ, int nj, double *d_
     int kdone = 0, first = 1;
     while (first || kdone < nk) {
         const int njp = first ? nj : 0, nkp = std::min(2, nk - kdone);
-        hipLaunchKernelGGL(jk_multi_prep_kernel, dim3(64), dim3(256), 0, st, d_work, d_dmJ, njp, d_dmK + (size_t)kdone * nn, nkp, nao, npad);
+        unsigned kanti = 0;
+        for (int q = 0; k_antisym && q < nkp; q++) kanti |= k_antisym[kdone + q] ? 1u << q : 0u;
+        hipLaunchKernelGGL(jk_multi_prep_kernel, dim3(64), dim3(256), 0, st, d_work, d_dmJ, njp, d_dmK + (size_t)kdone * nn, nkp, nao, npad, kanti);
         DQC_CHECK_LAUNCH();
         double *dscp = nullptr;
         if (deterministic_mode()) {
@@ -1024,7 +1050,7 @@ int dqc_jk_from_tiles_multi(double *d_J, const double *d_dmJ, int nj, double *d_
         else if (nkp == 1) hipLaunchKernelGGL(jk_multi_kernel<1>, dim3(grid), dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, njp, nao);
         else hipLaunchKernelGGL(jk_multi_kernel<0>, dim3(grid), dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, njp, nao);
         DQC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(jk_multi_finish_kernel, dim3(64), dim3(256), 0, st, d_J, njp, d_K + (size_t)kdone * nn, nkp, d_work, nao, npad, dscp);
+        hipLaunchKernelGGL(jk_multi_finish_kernel, dim3(64), dim3(256), 0, st, d_J, njp, d_K + (size_t)kdone * nn, nkp, d_work, nao, npad, dscp, kanti);
         DQC_CHECK_LAUNCH();
         kdone += nkp;
         first = 0;

@@ -886,7 +886,10 @@ __global__ __launch_bounds__(256) void xc_fxc_kernel(double *__restrict__ dvrho,
     }
 }
 
-template <int ID>
+// TRIPLET: the spin-flip response of a CLOSED shell.  ru_ / gu_ / dru_ / dgu_ then hold the TOTAL rho, grad rho, d rho, grad d rho
+// (the restricted kernel's inputs; the *_d pointers are not read): the ground state is rho_u = rho_d = rho / 2, the response
+// d rho_u = -d rho_d = d rho / 2, halved in registers, and only the spin-up potentials dvu / dvgu are written (d v_d = -d v_u).
+template <int ID, bool TRIPLET = false>
 __global__ __launch_bounds__(256) void xc_fxc_pol_kernel(double *__restrict__ dvu, double *__restrict__ dvd, double *__restrict__ dvgu,
                                                          double *__restrict__ dvgd, const double *__restrict__ ru_,
                                                          const double *__restrict__ rd_, const double *__restrict__ gu_,
@@ -900,13 +903,16 @@ __global__ __launch_bounds__(256) void xc_fxc_pol_kernel(double *__restrict__ dv
     using T5 = D5T<Tan>;
     __shared__ double sh[NV * NV][256];  // this thread's Hessian: column threadIdx.x (each thread reads only what it wrote: no barrier)
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        double ru = ru_[i], rd = rd_[i];
+        double ru = TRIPLET ? 0.5 * ru_[i] : ru_[i], rd = TRIPLET ? ru : rd_[i];
         if (!(ru + rd > 1e-15)) continue;
         ru = fmax(ru, 0.5e-15);
         rd = fmax(rd, 0.5e-15);
         double gu[3] = {0, 0, 0}, gd[3] = {0, 0, 0};
         if constexpr (GGA)
-            for (int k = 0; k < 3; k++) { gu[k] = gu_[(size_t)k * n + i]; gd[k] = gd_[(size_t)k * n + i]; }
+            for (int k = 0; k < 3; k++) {
+                gu[k] = TRIPLET ? 0.5 * gu_[(size_t)k * n + i] : gu_[(size_t)k * n + i];
+                gd[k] = TRIPLET ? gu[k] : gd_[(size_t)k * n + i];
+            }
         const double in[5] = {ru, rd, gu[0] * gu[0] + gu[1] * gu[1] + gu[2] * gu[2], gu[0] * gd[0] + gu[1] * gd[1] + gu[2] * gd[2],
                               gd[0] * gd[0] + gd[1] * gd[1] + gd[2] * gd[2]};
         // first derivatives; the Hessian (row j: derivative along input j of the gradient) goes through LDS, one column per thread:
@@ -953,12 +959,15 @@ __global__ __launch_bounds__(256) void xc_fxc_pol_kernel(double *__restrict__ dv
             }
         }
         for (int v = 0; v < nvec; v++) {
-            double din[5] = {dru_[(size_t)v * n + i], drd_[(size_t)v * n + i], 0.0, 0.0, 0.0};
+            double din[5] = {dru_[(size_t)v * n + i], 0.0, 0.0, 0.0, 0.0};
+            if constexpr (TRIPLET) { din[0] *= 0.5; din[1] = -din[0]; }
+            else din[1] = drd_[(size_t)v * n + i];
             double dgu[3] = {0, 0, 0}, dgd[3] = {0, 0, 0};
             if constexpr (GGA) {
                 for (int k = 0; k < 3; k++) {
                     dgu[k] = dgu_[((size_t)v * 3 + k) * n + i];
-                    dgd[k] = dgd_[((size_t)v * 3 + k) * n + i];
+                    if constexpr (TRIPLET) { dgu[k] *= 0.5; dgd[k] = -dgu[k]; }
+                    else dgd[k] = dgd_[((size_t)v * 3 + k) * n + i];
                 }
                 din[2] = 2.0 * (gu[0] * dgu[0] + gu[1] * dgu[1] + gu[2] * dgu[2]);
                 din[3] = (gu[0] * dgd[0] + gu[1] * dgd[1] + gu[2] * dgd[2]) + (dgu[0] * gd[0] + dgu[1] * gd[1] + dgu[2] * gd[2]);
@@ -971,11 +980,12 @@ __global__ __launch_bounds__(256) void xc_fxc_pol_kernel(double *__restrict__ dv
                 for (int j = 0; j < NV; j++) dv[k] += sh[j * NV + k][threadIdx.x] * din[j];
             }
             dvu[(size_t)v * n + i] += coef * dv[0];
-            dvd[(size_t)v * n + i] += coef * dv[1];
+            if constexpr (!TRIPLET) dvd[(size_t)v * n + i] += coef * dv[1];
             if constexpr (GGA)
                 for (int k = 0; k < 3; k++) {
                     dvgu[((size_t)v * 3 + k) * n + i] += coef * (2.0 * dv[2] * gu[k] + 2.0 * v1[2] * dgu[k] + dv[3] * gd[k] + v1[3] * dgd[k]);
-                    dvgd[((size_t)v * 3 + k) * n + i] += coef * (2.0 * dv[4] * gd[k] + 2.0 * v1[4] * dgd[k] + dv[3] * gu[k] + v1[3] * dgu[k]);
+                    if constexpr (!TRIPLET)
+                        dvgd[((size_t)v * 3 + k) * n + i] += coef * (2.0 * dv[4] * gd[k] + 2.0 * v1[4] * dgd[k] + dv[3] * gu[k] + v1[3] * dgu[k]);
                 }
         }
     }
@@ -1046,6 +1056,32 @@ extern "C" int dqc_xc_eval_fxc_pol(double *d_dvrho_u, double *d_dvrho_d, double 
         DQC_FXC_IDS(X)
 #undef X
         default: hipLaunchKernelGGL(xc_fxc_pol_kernel<-1>, dim3(blocks), dim3(256), 0, st, d_dvrho_u, d_dvrho_d, d_dvgrad_u, d_dvgrad_d, d_rho_u, d_rho_d, d_grho_u, d_grho_d, d_drho_u, d_drho_d, d_dgrho_u, d_dgrho_d, n, nvec, ids[t], coefs[t]); break;
+        }
+        DQC_CHECK_LAUNCH();
+    }
+    return DQC_OK;
+}
+
+extern "C" int dqc_xc_eval_fxc_triplet(double *d_dvrho, double *d_dvgrad, const double *d_rho, const double *d_grho, const double *d_drho,
+                                       const double *d_dgrho, int n, int nvec, const int *ids, const double *coefs, int nterm, void *stream) {
+    // the spin-flip (triplet) response of a closed shell: d v_u of the polarised second-order kernel at rho_u = rho_d = rho / 2 under
+    // d rho_u = -d rho_d = d rho / 2 (likewise the gradients), from the TOTAL (rho, grad rho, d rho, grad d rho) -- the arguments and
+    // the output layout of dqc_xc_eval_fxc; the halves are formed in registers (xc_fxc_pol_kernel<ID, true>)
+    using namespace dqc;
+    const bool grad = d_grho && d_dgrho && d_dvgrad;
+    if (int rc = fxc_check_terms("dqc_xc_eval_fxc_triplet", ids, nterm, grad, nvec)) return rc;
+    if (n <= 0 || nvec == 0) return DQC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DQC_HIP(hipMemsetAsync(d_dvrho, 0, sizeof(double) * (size_t)nvec * n, st));
+    if (d_dvgrad) DQC_HIP(hipMemsetAsync(d_dvgrad, 0, sizeof(double) * (size_t)nvec * 3 * n, st));
+    int blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    for (int t = 0; t < nterm; t++) {
+        switch (ids[t]) {
+#define X(ID_) case ID_: hipLaunchKernelGGL((xc_fxc_pol_kernel<ID_, true>), dim3(blocks), dim3(256), 0, st, d_dvrho, nullptr, d_dvgrad, nullptr, d_rho, nullptr, d_grho, nullptr, d_drho, nullptr, d_dgrho, nullptr, n, nvec, ids[t], coefs[t]); break;
+        DQC_FXC_IDS(X)
+#undef X
+        default: hipLaunchKernelGGL((xc_fxc_pol_kernel<-1, true>), dim3(blocks), dim3(256), 0, st, d_dvrho, nullptr, d_dvgrad, nullptr, d_rho, nullptr, d_grho, nullptr, d_drho, nullptr, d_dgrho, nullptr, n, nvec, ids[t], coefs[t]); break;
         }
         DQC_CHECK_LAUNCH();
     }

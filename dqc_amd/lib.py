@@ -100,6 +100,7 @@ def load():
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
     lib.dqc_jk_multi_work_doubles.restype = c_sz
     lib.dqc_jk_from_tiles_multi.argtypes = [c_dp, c_dp, c_int, c_dp, c_dp, c_int, c_dp, c_int, c_dp, c_vp]
+    lib.dqc_jk_from_tiles_multi_asym.argtypes = [c_dp, c_dp, c_int, c_dp, c_dp, c_int, ctypes.POINTER(c_int), c_dp, c_int, c_dp, c_vp]
     lib.dqc_eval_gto.argtypes = [c_int, c_dp, c_dp, c_int] + tab + [c_vp]
     lib.dqc_grid_density.argtypes = [c_dp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_vp]
     lib.dqc_xc_eval.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_int, ip, dp, c_int, c_vp]
@@ -107,6 +108,7 @@ def load():
     lib.dqc_xc_eval_pol.argtypes = [c_dp] * 9 + [c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_fxc.argtypes = [c_dp] * 6 + [c_int, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_fxc_pol.argtypes = [c_dp] * 12 + [c_int, c_int, ip, dp, c_int, c_vp]
+    lib.dqc_xc_eval_fxc_triplet.argtypes = [c_dp] * 6 + [c_int, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_mgga.argtypes = [c_dp] * 7 + [c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_mgga_pol.argtypes = [c_dp] * 11 + [c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_mgga_pol2.argtypes = [c_dp] * 12 + [c_int, ip, dp, c_int, c_vp]
@@ -126,6 +128,7 @@ def load():
     ll = ctypes.c_longlong
     lib.dqc_resp_gemm.argtypes = [c_dp, c_dp, c_dp] + [c_int] * 6 + [ll, ll, ll, c_int, c_int, ctypes.c_double, c_dp, c_dp, c_dp, c_vp]
     lib.dqc_resp_kappa2dm.argtypes = [c_dp] * 5 + [c_int] * 4 + [ctypes.c_double, c_vp]
+    lib.dqc_resp_kappa2dm_pm.argtypes = [c_dp] * 6 + [c_int] * 4 + [ctypes.c_double, c_vp]
     lib.dqc_padded_norb.argtypes = [c_int]
     lib.dqc_padded_norb.restype = c_int
     lib.dqc_grid_density_lr.argtypes = [c_dp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp, c_int, c_vp]
@@ -714,9 +717,11 @@ def jk_part(tiles_part, dm_ao, work, with_k, t0, t1):
     return J, K
 
 
-def jk_multi(tiles, dms_j, dms_k, work=None):
+def jk_multi(tiles, dms_j, dms_k, work=None, k_antisym=None):
     """ONE pass over the tiles for several density matrices: dms_j (nj, nao, nao) -> J (nj, nao, nao), dms_k (nk, nao, nao)
-    -> K (nk, nao, nao) (plain K, not -K/2); either may be None.  AO basis, symmetrised."""
+    -> K (nk, nao, nao) (plain K, not -K/2); either may be None.  AO basis, symmetrised.
+    k_antisym: a sequence of nk flags; a flagged exchange density is ANTISYMMETRISED instead, (D - D^T) / 2, and its K[D]_pq =
+    (pr|qs) D_rs is antisymmetric (dqc_jk_from_tiles_multi_asym; two exchange densities of either kind share a pass)."""
     ref = dms_j if dms_j is not None else dms_k
     nao, dev = ref.shape[-1], ref.device
     nj = 0 if dms_j is None else dms_j.shape[0]
@@ -726,6 +731,16 @@ def jk_multi(tiles, dms_j, dms_k, work=None):
         work = torch.empty(need, dtype=torch.float64, device=dev)
     J = torch.empty((nj, nao, nao), dtype=torch.float64, device=dev) if nj else None
     K = torch.empty((nk, nao, nao), dtype=torch.float64, device=dev) if nk else None
+    if k_antisym is not None:
+        flags = [1 if f else 0 for f in k_antisym]
+        if len(flags) != nk:
+            raise ValueError("jk_multi: k_antisym needs one flag per exchange density (%d), got %d" % (nk, len(flags)))
+        mask = (ctypes.c_int * max(nk, 1))(*flags)
+        with _on(dev) as st_:
+            _check(load().dqc_jk_from_tiles_multi_asym(_ptr(J), _ptr(None if dms_j is None else dms_j.contiguous()), nj,
+                                                       _ptr(K), _ptr(None if dms_k is None else dms_k.contiguous()), nk, mask,
+                                                       _ptr(tiles), nao, _ptr(work), st_), "dqc_jk_from_tiles_multi_asym")
+        return J, K
     with _on(dev) as st_:
         _check(load().dqc_jk_from_tiles_multi(_ptr(J), _ptr(None if dms_j is None else dms_j.contiguous()), nj,
                                               _ptr(K), _ptr(None if dms_k is None else dms_k.contiguous()), nk,
@@ -925,6 +940,22 @@ def xc_eval_fxc(terms, rho, grho, drho, dgrho):
     return dv, dvg
 
 
+def xc_eval_fxc_triplet(terms, rho, grho, drho, dgrho):
+    """the spin-flip (triplet) response of a closed shell, arguments and outputs as xc_eval_fxc (TOTAL density and response in): the
+    spin-up output of xc_eval_fxc_pol at rho_u = rho_d = rho / 2 under d rho_u = -d rho_d = d rho / 2, halved inside the kernel"""
+    ids, cfs = _fxc_terms(terms, "xc_eval_fxc_triplet")
+    nvec, n = drho.shape
+    gga = grho is not None and dgrho is not None
+    rho, drho = rho.contiguous(), drho.contiguous()
+    grho, dgrho = (grho.contiguous(), dgrho.contiguous()) if gga else (None, None)
+    dv = torch.empty_like(drho)
+    dvg = torch.empty((nvec, 3, n), dtype=torch.float64, device=rho.device) if gga else None
+    with _on(rho.device) as st_:
+        _check(load().dqc_xc_eval_fxc_triplet(_ptr(dv), _ptr(dvg), _ptr(rho), _ptr(grho), _ptr(drho), _ptr(dgrho), n, nvec, ids, cfs,
+                                              len(terms), st_), "dqc_xc_eval_fxc_triplet")
+    return dv, dvg
+
+
 def xc_eval_fxc_pol(terms, rho_u, rho_d, grho_u, grho_d, drho_u, drho_d, dgrho_u, dgrho_d):
     """spin-polarised xc_eval_fxc -> (dvrho_u, dvrho_d), (dvgrad_u, dvgrad_d) (None for LDA), each (nvec, n) / (nvec, 3, n)"""
     ids, cfs = _fxc_terms(terms, "xc_eval_fxc_pol")
@@ -1102,6 +1133,20 @@ def resp_kappa2dm(kappa, cv, co, scale):
         _check(load().dqc_resp_kappa2dm(_ptr(dm), _ptr(t), _ptr(kappa.contiguous()), _ptr(cv), _ptr(co), nao, nv, no, nvec, float(scale), st_),
                "dqc_resp_kappa2dm")
     return dm
+
+
+def resp_kappa2dm_pm(kappa, cv, co, scale, plus=True, minus=True):
+    """-> (dD+, dD-) = scale (C_v kappa C_o^T +- transpose), each (nvec, nao, nao) or None when not asked for: one half-transformation
+    C_v kappa and one launch per output"""
+    nvec, nv, no = kappa.shape
+    nao = cv.shape[0]
+    dp = torch.empty((nvec, nao, nao), dtype=torch.float64, device=kappa.device) if plus else None
+    dm = torch.empty((nvec, nao, nao), dtype=torch.float64, device=kappa.device) if minus else None
+    t = torch.empty((nvec, nao, no), dtype=torch.float64, device=kappa.device)
+    with _on(kappa.device) as st_:
+        _check(load().dqc_resp_kappa2dm_pm(_ptr(dp), _ptr(dm), _ptr(t), _ptr(kappa.contiguous()), _ptr(cv), _ptr(co), nao, nv, no, nvec,
+                                           float(scale), st_), "dqc_resp_kappa2dm_pm")
+    return dp, dm
 
 
 def resp_project(g, cv, co, alpha, ev=None, eo=None, kappa=None):

@@ -70,7 +70,7 @@ def _memo(qc, key, fcn):
     return memo[key]
 
 
-def lowest_eival_orb_hessian(qc, tol=1e-6):
+def lowest_eival_orb_hessian(qc, tol=1e-6, triplet=False):
     """lowest eigenvalue (one-element tensor) of the Hessian of the energy with respect to the orbital rotations, by block Davidson
     on Hessian-vector products (dqc_amd/response.py: the variables are the non-redundant virtual <- occupied rotations
     kappa_ai of C exp(kappa - kappa^T); `tol` is the residual norm of the eigenpair).
@@ -80,16 +80,67 @@ def lowest_eival_orb_hessian(qc, tol=1e-6):
     orbitals does not change along them, so they contribute zero eigenvalues: the reference's value is min(0, this one).  The sign
     test of `is_orb_min` is the same for both.
 
+    `triplet=True` (restricted calculations; ValueError on an unrestricted one, whose Hessian contains these directions already): the
+    Hessian 4 (A+B)^T along the spin-flip rotations dD_u = -dD_d, which a restricted calculation cannot take -- a negative value is the
+    RHF -> UHF instability.
+
     A Davidson iteration that stops short of `tol` warns: its value is then only an upper bound of the lowest eigenvalue."""
     from .response import orbital_hessian
-    return _memo(qc, ("lowest_eival", float(tol)), lambda: orbital_hessian(qc).lowest(neig=1, tol=tol)[0].reshape(1))
+    if not triplet:
+        return _memo(qc, ("lowest_eival", float(tol)), lambda: orbital_hessian(qc).lowest(neig=1, tol=tol)[0].reshape(1))
+    if qc._engine.polarized:
+        raise ValueError("lowest_eival_orb_hessian: triplet=True is for restricted calculations (the Hessian of an unrestricted one "
+                         "contains the spin-flip directions already)")
+    return _memo(qc, ("lowest_eival_triplet", float(tol)), lambda: orbital_hessian(qc, "triplet").lowest(neig=1, tol=tol)[0].reshape(1))
 
 
-def is_orb_min(qc, threshold=-1e-3):
+def is_orb_min(qc, threshold=-1e-3, triplet=False):
     """True when the converged SCF state is a minimum with respect to orbital rotations, not a saddle point or an excited state:
-    the lowest eigenvalue of the orbital Hessian is above `threshold` (dqc/api/properties.py:301-319)"""
-    eival = lowest_eival_orb_hessian(qc)
+    the lowest eigenvalue of the orbital Hessian is above `threshold` (dqc/api/properties.py:301-319).  `triplet=True`: with respect
+    to the spin-flip rotations of a restricted calculation (lowest_eival_orb_hessian)."""
+    eival = lowest_eival_orb_hessian(qc, triplet=triplet) if triplet else lowest_eival_orb_hessian(qc)
     return bool(torch.all(eival > threshold))
+
+
+class Excitations:
+    """what `excitations` returns: `energies` (nstates,) in Hartree, ascending; `transition_dipoles` (nstates, 3) and `osc_strengths`
+    (nstates,) (length gauge; zero for triplets); `xpy`, `xmy` (nstates, n): X+Y and X-Y in the variables of dqc_amd/response.py,
+    (X+Y) . (X-Y) = 1 (TDA: xpy = X, X . X = 1, xmy None); `spin`, `tda`, `residual` (largest residual norm of the solver)"""
+
+    def __init__(self, energies, transition_dipoles, osc_strengths, xpy, xmy, spin, tda, residual):
+        self.energies, self.transition_dipoles, self.osc_strengths = energies, transition_dipoles, osc_strengths
+        self.xpy, self.xmy, self.spin, self.tda, self.residual = xpy, xmy, spin, tda, residual
+
+    def __repr__(self):
+        return "Excitations(%s%s, energies=%s, osc_strengths=%s)" % (self.spin, ", TDA" if self.tda else "", self.energies.tolist(),
+                                                                      self.osc_strengths.tolist())
+
+
+def excitations(qc, nstates=5, spin="singlet", tda=False, tol=1e-6):
+    """the `nstates` lowest excitation energies of a converged HF / KS calculation by linear response (TDHF / TDDFT; `tda=True`: the
+    Tamm-Dancoff approximation, CIS for Hartree-Fock), with transition dipoles and oscillator strengths f = (2 / 3) w |mu|^2 -> an
+    `Excitations` object.  `spin`: "singlet", or "triplet" for a restricted calculation (an unrestricted one has one channel:
+    ValueError).  Iterative (block Davidson on the operator products of dqc_amd/response.py); `tol`: residual norm; `nstates` is clipped
+    to the number of rotations.  RuntimeError when the SCF state is not a minimum in the channel asked for (is_orb_min(qc,
+    triplet=...)).  Unsupported configurations: those of the orbital Hessian (NotImplementedError)."""
+    from .response import orbital_hessian
+    if spin not in ("singlet", "triplet"):
+        raise ValueError("excitations: spin is \"singlet\" or \"triplet\", not %r" % (spin,))
+    if spin == "triplet" and qc._engine.polarized:
+        raise ValueError("excitations: spin=\"triplet\" needs a restricted calculation (spin-flip response of an unrestricted reference "
+                         "is not provided)")
+
+    def compute():
+        oh = orbital_hessian(qc, spin)
+        w, xpy, xmy = oh.excite(nstates=min(int(nstates), oh.n), tda=tda, tol=tol)
+        if spin == "triplet":
+            mu = torch.zeros((w.numel(), 3), dtype=w.dtype, device=w.device)
+        else:
+            h = qc.get_system().get_hamiltonian()
+            r = oh.gradient_of(lib.int1e("r0", h._tab, h.device)) / oh.pref  # (3, n): r_ai per spin block
+            mu = (1.0 if oh.polarized else 2.0 ** 0.5) * (xpy @ r.T)
+        return Excitations(w, mu, (2.0 / 3.0) * w * (mu * mu).sum(1), xpy, xmy, spin, bool(tda), oh.last_residual)
+    return _memo(qc, ("excitations", int(nstates), spin, bool(tda), float(tol)), compute)
 
 
 def polarizability(qc, tol=1e-9):

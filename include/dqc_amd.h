@@ -140,6 +140,10 @@ int dqc_resp_gemm(double *d_c, const double *d_a, const double *d_b, int M, int 
                   void *stream);
 int dqc_resp_kappa2dm(double *d_dm, double *d_t, const double *d_kappa, const double *d_cv, const double *d_co, int nao, int nv, int no,
                       int nvec, double scale, void *stream);
+/* dD+[v] = scale (C_v kappa[v] C_o^T + transpose) and the ANTISYMMETRIC dD-[v] = scale (C_v kappa[v] C_o^T - transpose) (the transition
+ * density of the A - B product of linear response) from one half-transformation C_v kappa[v]; either output may be NULL. */
+int dqc_resp_kappa2dm_pm(double *d_dm_plus, double *d_dm_minus, double *d_t, const double *d_kappa, const double *d_cv, const double *d_co,
+                         int nao, int nv, int no, int nvec, double scale, void *stream);
 
 /* Several density matrices in ONE pass over the tiles (unrestricted HF: J[D_u + D_d], K[2 D_u], K[2 D_d],
  * hcgto.py:238-241, hf.py:93-103; batched dm, base_hamilton.py:92-93).
@@ -149,6 +153,12 @@ int dqc_resp_kappa2dm(double *d_dm, double *d_t, const double *d_kappa, const do
 size_t dqc_jk_multi_work_doubles(int nao, int nj, int nk);
 int dqc_jk_from_tiles_multi(double *d_J, const double *d_dmJ, int nj, double *d_K, const double *d_dmK, int nk,
                             const double *d_tiles, int nao, double *d_work, void *stream);
+/* the same with a flag per exchange right-hand side: k_antisym is a HOST array of nk ints (NULL: all symmetric).  A flagged
+ * right-hand side enters as (D - D^T) / 2 and its K[D]_pq = (pr|qs) D_rs comes back antisymmetric (accumulator minus its
+ * transpose); symmetric and antisymmetric right-hand sides share a pass, and the unflagged results are those of
+ * dqc_jk_from_tiles_multi, bit for bit in the deterministic mode. */
+int dqc_jk_from_tiles_multi_asym(double *d_J, const double *d_dmJ, int nj, double *d_K, const double *d_dmK, int nk, const int *k_antisym,
+                                 const double *d_tiles, int nao, double *d_work, void *stream);
 
 /* ---- AO values on the grid -----------------------------------------------------------------
  * Replaces GTOval_sph / GTOval_ip_sph (dqc/hamilton/intor/gtoeval.py:196-239) with the
@@ -238,6 +248,12 @@ int dqc_xc_eval_fxc_pol(double *d_dvrho_u, double *d_dvrho_d, double *d_dvgrad_u
                         const double *d_rho_d, const double *d_grho_u, const double *d_grho_d, const double *d_drho_u,
                         const double *d_drho_d, const double *d_dgrho_u, const double *d_dgrho_d, int n, int nvec,
                         const int *ids, const double *coefs, int nterm, void *stream);
+
+/* the spin-flip (triplet) response of a CLOSED shell: d v_u of dqc_xc_eval_fxc_pol at rho_u = rho_d = rho / 2 under
+ * d rho_u = -d rho_d = d rho / 2 (likewise the gradients), evaluated from the TOTAL density and response -- the arguments, the
+ * output layout and the cutoff of dqc_xc_eval_fxc (d v_d = -d v_u is not written). */
+int dqc_xc_eval_fxc_triplet(double *d_dvrho, double *d_dvgrad, const double *d_rho, const double *d_grho, const double *d_drho,
+                            const double *d_dgrho, int n, int nvec, const int *ids, const double *coefs, int nterm, void *stream);
 
 /* spin-polarised meta-GGA CORRELATION terms (CalcMGGALibXCPol, libxc_wrapper.py:221-378; DQC_XC_MGGA_C_SCAN): they depend
  * on rho_u, rho_d, |grad(rho_u + rho_d)|^2 and tau_u + tau_d only, so vsigma = (v, 2 v, v) for (uu, ud, dd) and both spins
