@@ -158,7 +158,6 @@ class HamiltonMI355(_Base):
         # two-electron energies of the last build, and the orbital factors of the last two ao_orb2dm results (the spin-up and
         # spin-down matrices of an unrestricted iteration); per weight tensor: the last two occupation checks
         self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors = _Memo(), _Memo(), _Memo(), _Memo(2)
-        self._hybpol_memo = _Memo()  # a E_K of the last unrestricted hybrid build
         self._w_checked = _Memo(2)
         # which density kernel the grid passes took: "factor" (rank-n_occ kernel, D = ao_orb2dm(...) recognised), "dense" (anonymous
         # full matrix: 0.84 instead of 0.50 ms on a 20-atom molecule).  A caller that forms more than two density matrices before
@@ -167,7 +166,7 @@ class HamiltonMI355(_Base):
 
     def clear_memos(self):
         """forget what was remembered per density matrix (a graph capture's tensors belong to its private pool)"""
-        for m in (self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors, self._hybpol_memo):
+        for m in (self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors):
             m.clear()
 
     # ------------------------------------------------------------------ properties
@@ -894,13 +893,14 @@ class HamiltonMI355(_Base):
             return fn()
 
     @staticmethod
-    def _rejoin(side, out=None):
-        """this stream waits for what _beside enqueued on `side`; `out` was allocated there and is read and later freed here"""
+    def _rejoin(side, *outs):
+        """this stream waits for what _beside enqueued on `side`; `outs` were allocated there and are read and later freed here"""
         if side is not None:
             main = torch.cuda.current_stream(side.device)
             main.wait_stream(side)
-            if out is not None:
-                out.record_stream(main)
+            for t in outs:
+                if t is not None:
+                    t.record_stream(main)
 
     def _prep(self, work, dm, fac, with_k):
         """dqc_fock_prep: the symmetric AO density into `work`, its accumulators zeroed -- L L^T when the orbital factor `fac` is one
@@ -918,232 +918,177 @@ class HamiltonMI355(_Base):
         # (exc[:1]: the result, the rest of the buffer is the kernel's per-block scratch; sharded: the quadrature of this rank's slab)
         return potinfo, None if exc is None else self._allsum(exc[:1])
 
-    def get_elrep_plus_vxc(self, dm, core=None):
-        """J[D] + Vxc[D] of ONE restricted density matrix as a plain tensor in the orthogonalised basis -- the sum
-        `_KSEngine.__dm2fock` forms (ks.py:176-187) -- with a single AO -> orthogonal conversion X^T (J_ao + V_ao) X instead
-        of one per operator.  Same numbers as get_elrep(dm) + get_vxc(dm) up to round-off."""
-        return self._elrep_plus_vxc(dm, core, lambda: None)
+    def _vxc_sums(self, potinfo):
+        """(Vxc sums, their fixed-point scale) for the fused finish.  LDA / GGA: the Vxc kernel's raw cross-block sums (their
+        symmetrisation is part of the finish's combine kernel: one launch less); meta-GGA: the symmetric AO matrix and None"""
+        if self.xcfamily == 4:
+            return self._vxc_ao_from_potinfo(potinfo), None
+        vg = potinfo.grad if self.xcfamily == 2 else None
+        return lib.grid_vxc_raw(self._ao, self._nao_ao, self.dvolume, potinfo.value.contiguous(), None if vg is None else vg.contiguous())
 
-    def _elrep_plus_vxc(self, dm, core, mark):
-        """get_elrep_plus_vxc with mark() called between its six stages (timed_fock_kernels).  The small-matrix ends go through the
-        fused kernels of csrc/fock.hip unless the Coulomb pass has a side stream to run on"""
-        assert self.xc is not None and dm.dim() == 2
-        fac = self._factor_of(dm)
-        side = self._coulomb_side(dm.device)
-        if side is None and self._fused_build_ok(dm):
-            return self._elrep_plus_vxc_fused(dm, fac, core, mark)
+    # The two-electron part of a Fock matrix, X^T (J - k K / 2 + V) X + core, is ONE build per spin treatment: _fock2e (restricted)
+    # and _fock2e_pol (unrestricted).  Five steps -- AO density (from the orbital factor or X D X^T), tile pass (in line or beside
+    # the grid pass on a side stream), grid pass (density, functional, Vxc), the streams rejoined, the finish with the traces -- in a
+    # fused form (csrc/fock.hip) and a torch form (DQC_AMD_FUSED_FOCK=0, anonymous or strided input, density fitting, direct SCF, a
+    # tile store spread over ranks: what the fused kernels are tested against).  What differs between the flavours is this table;
+    # every row is a measured path and is kept as found (DESIGN.md section 5b):
+    #
+    #   flavour              kfrac  vxc   _coulomb_side(own=)  with a registered side stream                 energies remembered
+    #   restricted KS        None   True  own=False            takes the torch form                          E_J, E_xc
+    #   restricted HF        1.0    False never beside         --                                            E_J, E_K
+    #   restricted hybrid    a      True  own=True             stays fused, tile pass on that stream         E_J, E_xc, a E_K
+    #   unrestricted KS      None         own=True             fused only when the stream is its own / none  none
+    #   unrestricted hybrid  a            own=True             -- (no fused form: jk_multi)                  a E_K, keyed on the pair
+    #
+    # The torch form takes the AO density of restricted KS from a one-panel factor (one thin GEMM); the builds with K use X D X^T.
+
+    def _fock2e(self, dm, kfrac, vxc, core, mark=None):
+        """J[D] - kfrac K[D] / 2 + Vxc[D] (+ core) of ONE restricted density matrix, orthogonalised basis.  kfrac None: no exchange;
+        1.0 without `vxc`: Hartree-Fock; a with `vxc`: a hybrid.  `mark()` is called between the six stages (timed_fock_kernels).  The
+        two-electron energies of THIS density fall out of the build (tr D J = tr D_ao J_ao) and are remembered under the identity +
+        version of `dm`, so that dm2energy(dm) right after dm2scp(dm) streams neither the tiles nor the grid again"""
+        assert dm.dim() == 2 and (self.xc is not None or not vxc)
+        with_k, hybrid = kfrac is not None, kfrac is not None and vxc
+        if with_k and self._df is not None:  # hcgto.py:229-230
+            raise RuntimeError("Exact exchange cannot be computed with density fitting")
+        if hybrid:
+            self._check_hybrid(kfrac)
+        mark = mark or (lambda: None)
         n = self._nao_ao
+        side = self._coulomb_side(dm.device, own=hybrid) if vxc else None
+        fused = (side is None or hybrid) and self._fused_build_ok(dm)
+        fac = self._factor_of(dm) if fused or vxc else None
+        exc = vm = vsc = jao = kao = None
+        if fused:
+            x, work, tiles = self._orthozer, self._jkwork, self._tiles
         mark()
-        if fac is not None and len(fac) == 1:  # D_ao = L_ao L_ao^T: one thin GEMM instead of X D X^T
+        if fused:  # D_ao + zeroed accumulators in ONE launch
+            self._prep(work, dm, fac, with_k)
+        elif fac is not None and len(fac) == 1 and not with_k:  # D_ao = L_ao L_ao^T: one thin GEMM instead of X D X^T
             dao = (fac[0][0] @ fac[0][1])[:n, :n].contiguous()
         else:
             dao = self._unconvert_dm(dm)
         mark()
-        if self._tile_slice is not None:  # tile store spread over the ranks: J, Vxc and E_xc parts travel in one all_reduce
+        if self._tile_slice is not None and not with_k:  # tile store spread over the ranks: J, Vxc and E_xc parts travel in one all_reduce
             self._deferred = []
         try:
-            if self._df is not None:
+            # (on a side stream: the tile stream on its own compute units, beside this molecule's grid pass)
+            if fused:
+                self._beside(side, lambda: lib.jk_stream_prepared(tiles, n, work, with_k))
+            elif self._df is not None:
                 jao = self._df.coulomb_ao(dao)
-            else:  # (on a side stream: the tile stream on its own compute units, beside this molecule's grid pass)
-                jao = self._beside(side, lambda: self._jk_ao(dao, False)[0], dao)
+            else:
+                jao, kao = self._beside(side, lambda: self._jk_ao(dao, with_k), dao)
             mark()
-            densinfo = self._dm2densinfo(dm)
-            mark()
-            potinfo, exc = self._vxc_exc(densinfo)
-            mark()
-            vm = self._vxc_ao_from_potinfo(potinfo)
-            self._rejoin(side, jao)
+            if vxc:
+                densinfo = self._dm2densinfo(dm)
+                mark()
+                potinfo, exc = self._vxc_exc(densinfo)
+                mark()
+                vm, vsc = self._vxc_sums(potinfo) if fused else (self._vxc_ao_from_potinfo(potinfo), None)
+            self._rejoin(side, jao, kao)
             if self._deferred is not None:
                 self._allsum_flush()
         finally:
             self._deferred = None  # (an exception in between must not leave later _allsum calls queued for ever)
         mark()
-        # the two-electron energies of THIS density fall out of the build (tr D J = tr D_ao J_ao): remembered under the
-        # identity + version of `dm`, so that dm2energy(dm) right after dm2scp(dm) streams neither the tiles nor the grid again
-        self._energy_memo.put(_Energies(j=0.5 * (dao * jao).sum(), xc=None if exc is None else exc[0]), dm)
-        mat = self._sym_orth(jao + vm[:n, :n])
-        mat = mat if core is None else core + mat
-        mark()
-        return mat
-
-    def _elrep_plus_vxc_fused(self, dm, fac, core, mark):
-        """get_elrep_plus_vxc with the small-matrix ends fused (csrc/fock.hip): AO density (from the orbital factor when it is known,
-        else X D X^T) + zeroed accumulators in ONE launch, the tile pass, the grid pass, then J's symmetrisation, tr D J / 2,
-        X^T (J + V_ao) X and its symmetrisation in ONE launch"""
-        n, x, work = self._nao_ao, self._orthozer, self._jkwork
-        tiles = self._tiles
-        mark()
-        self._prep(work, dm, fac, False)
-        mark()
-        lib.jk_stream_prepared(tiles, n, work, False)
-        mark()
-        densinfo = self._dm2densinfo(dm)
-        mark()
-        potinfo, exc = self._vxc_exc(densinfo)
-        mark()
-        if self.xcfamily != 4:
-            # LDA / GGA: the Vxc kernel's raw cross-block sums go straight into the finish (their symmetrisation is part of its
-            # combine kernel: one launch less)
-            vg = potinfo.grad if self.xcfamily == 2 else None
-            vraw, vsc = lib.grid_vxc_raw(self._ao, n, self.dvolume, potinfo.value.contiguous(), None if vg is None else vg.contiguous())
-            mark()
-            mat, en = lib.fock_finish_vraw(work, x, n, vraw, vsc, core=core)
+        if fused:  # symmetrised J / K, the traces, X^T (J - kfrac K / 2 + V) X, its symmetrisation and the core Hamiltonian in ONE launch
+            mat, en, _ = lib.fock_finish(work, x, n, with_k, vxc_ao=vm, core=core, vscale=vsc, kfrac=kfrac if hybrid else None, exc=exc)
+            ej, ek = en[0], en[1] if with_k else None
+            exc = en[2:] if hybrid and exc is not None else exc
         else:
-            vm = self._vxc_ao_from_potinfo(potinfo)
-            mark()
-            mat, en, _ = lib.fock_finish(work, x, n, False, vxc_ao=vm, core=core)  # (core: the one-electron part, added in the same launch)
+            ej, ek = 0.5 * (dao * jao).sum(), -0.25 * kfrac * (dao * kao).sum() if with_k else None
+            m = jao if not with_k else jao - (0.5 * kfrac) * kao
+            mat = self._sym_orth(m if not vxc else m + vm[:n, :n])
+            mat = mat if core is None else core + mat
+        self._energy_memo.put(_Energies(j=ej, xc=None if exc is None else exc[0], k=None if vxc else ek, ka=ek if vxc else None), dm)
         mark()
-        self._energy_memo.put(_Energies(j=en[0], xc=None if exc is None else exc[0]), dm)
         return mat
 
-    def get_elrep_plus_vxc_pol(self, dm: SpinParam, core=None):
-        """J[D_u + D_d] + Vxc_s[D_u, D_d] of an unrestricted pair of density matrices as a stacked (2, nao, nao) tensor in the
-        orthogonalised basis -- the sums the polarised `_KSEngine.__dm2fock` forms (ks.py:176-187, hf.py:93-103) -- with ONE batched
-        AO -> orthogonal conversion X^T (J_ao + V_s,ao) X of the two sums instead of one per operator (three), the AO-basis total
-        density from the two orbital factors when they are known, and the Coulomb stream over the tile store (HBM-bound) enqueued on
-        a second stream BESIDE the two-spin grid pass (its Vxc products are bound by the matrix cores; a graph capture: one stream).
-        With both factors known the ends are fused (csrc/fock.hip): L L^T of the stacked factor [L_u | L_d] in one launch, then per
-        spin M_s = J + V_s, X^T M_s X, the symmetrisation and the core Hamiltonian in one launch each.  Needs `tiles_resident`.
-        Same numbers as get_elrep(dm.u + dm.d) + get_vxc(dm) up to round-off."""
+    def _fock2e_pol(self, dm: SpinParam, kfrac, core):
+        """stacked (2, nao, nao)  J[D_u + D_d] - kfrac K[D_s] + Vxc_s[D_u, D_d] (+ core) of an unrestricted pair, orthogonalised basis
+        (a get_exchange(dm) is -a K[2 D_s] / 2 = -a K[D_s] per spin, hcgto.py:238-241); kfrac None: no exchange.  Needs
+        `tiles_resident`.  The pass over the tile store (HBM-bound) is enqueued on a second stream BESIDE the two-spin grid pass (its
+        Vxc products are bound by the matrix cores; a graph capture: one stream), and the two sums take ONE batched AO -> orthogonal
+        conversion.  Without exchange and with both factors one panel the ends are fused: L L^T of the stacked factor [L_u | L_d] in one
+        launch, then per spin J + V_s, X^T . X, the symmetrisation and the core Hamiltonian in one launch each.  With exchange: J and
+        the two K from ONE pass (dqc_jk_from_tiles_multi), and a E_K of the pair is remembered"""
         assert self.xc is not None and dm.u.dim() == 2 and self.tiles_resident
+        if kfrac is not None:
+            self._check_hybrid(kfrac)
         n, x = self._nao_ao, self._orthozer
         fu, fd = self._factor_of(dm.u), self._factor_of(dm.d)
         one = fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1
         side = self._coulomb_side(dm.u.device, own=True)
-        # (a side stream registered for this stream takes the torch form, as in the restricted build)
-        fused = one and (side is None or side is self._j_stream) and self._fused_build_ok(dm.u)
-        if fused:
-            work, tiles = self._jkwork, self._tiles
-            self._prep(work, None, [(torch.cat([fu[0][0], fd[0][0]], dim=1),)], False)
-            self._beside(side, lambda: lib.jk_stream_prepared(tiles, n, work, False))
-        else:
-            def coulomb():  # (the AO-basis total density and its Coulomb matrix: nothing the grid pass waits for)
-                if one:
-                    return self._jk_ao((fu[0][0] @ fu[0][1] + fd[0][0] @ fd[0][1])[:n, :n].contiguous(), False)[0]
-                return self._jk_ao(self._unconvert_dm(dm.u + dm.d), False)[0]
+        fused = kfrac is None and one and (side is None or side is self._j_stream) and self._fused_build_ok(dm.u)
+        work, tiles = self._jkwork, self._tiles if fused or kfrac is not None else None  # (else reached for on the side stream, by _jk_ao)
 
-            jao = self._beside(side, coulomb)
-        potinfo = self.xc.get_vxc(self._dm2densinfo_pol(dm))
-        vu = self._vxc_ao_from_potinfo(potinfo.u)
-        vd = self._vxc_ao_from_potinfo(potinfo.d)
-        self._rejoin(side, None if fused else jao)
-        if fused:  # (the two finishes share the scratch regions of the work buffer: stream order keeps them apart)
-            return torch.stack([lib.fock_finish(work, x, n, False, vxc_ao=v, core=core)[0] for v in (vu, vd)])
-        mat = x.transpose(-2, -1) @ torch.stack([jao + vu[:n, :n], jao + vd[:n, :n]]) @ x
-        mat = (mat + mat.transpose(-2, -1)) * 0.5
-        return mat if core is None else core + mat
-
-    def _memo_energy(self, dm, field):
-        """E_J, E_xc or E_K (`field` "j", "xc", "k", or 2, 3, 4 as callers of the positional memo name them) of `dm` when the last
-        build formed it, else None"""
-        e = self._energy_memo.get(dm)
-        return None if e is None else getattr(e, {2: "j", 3: "xc", 4: "k"}.get(field, field))
-
-    def get_elrep_plus_exchange(self, dm, core=None):
-        """J[D] - K[D] / 2 of ONE restricted density matrix as a plain tensor in the orthogonalised basis -- the sum a restricted
-        Hartree-Fock Fock build forms from get_elrep(dm) and get_exchange(dm) (hf.py:198-199, hcgto.py:204-241) -- with a single
-        AO -> orthogonal conversion X^T (J_ao - K_ao / 2) X instead of one per operator (two rocBLAS GEMMs of ~10 us each at
-        nao ~ 100, where the whole tile pass takes 58 us).  Same numbers as the operators' sum up to round-off."""
-        if self._df is not None:  # hcgto.py:229-230
-            raise RuntimeError("Exact exchange cannot be computed with density fitting")
-        assert dm.dim() == 2
-        if self._fused_build_ok(dm):
-            # D_ao + zeroed accumulators, the tile pass, then symmetrised J / K, the two traces and X^T (J - K / 2) X: three
-            # launches (csrc/fock.hip) instead of sixteen
-            n, work, tiles = self._nao_ao, self._jkwork, self._tiles
-            self._prep(work, dm, self._factor_of(dm), True)
-            lib.jk_stream_prepared(tiles, n, work, True)
-            mat, en, _ = lib.fock_finish(work, self._orthozer, n, True, core=core)
-            self._energy_memo.put(_Energies(j=en[0], k=en[1]), dm)
-            return mat
-        dao = self._unconvert_dm(dm)
-        J, K = self._jk_ao(dao, True)
-        # the two-electron energies of THIS density fall out of the build: remembered like get_elrep_plus_vxc's
-        self._energy_memo.put(_Energies(j=0.5 * (dao * J).sum(), k=-0.25 * (dao * K).sum()), dm)
-        mat = self._sym_orth(J - 0.5 * K)
-        return mat if core is None else core + mat
-
-    def get_elrep_plus_exchange_plus_vxc(self, dm, core=None):
-        """J[D] - a K[D] / 2 + Vxc[D] of ONE restricted density matrix as a plain tensor in the orthogonalised basis: the
-        two-electron part of a HYBRID Kohn-Sham Fock matrix, a = the exact-exchange fraction of the functional given to setup_grid
-        (get_elrep(dm) + a get_exchange(dm) + get_vxc(dm) up to round-off).  The J + K pass over the ERI tiles runs on a second
-        stream beside the density / XC / Vxc grid passes (in line inside a graph capture); the ends are the fused kernels of
-        csrc/fock.hip, the last of them dqc_fock_finish_hybrid: X^T (J - a K / 2 + V) X + core and the traces E_J, a E_K."""
-        a = self.exx_fraction
-        assert self.xc is not None and dm.dim() == 2
-        self._check_hybrid(a)
-        n = self._nao_ao
-        fac = self._factor_of(dm)
-        if self._fused_build_ok(dm):
-            x, work, tiles = self._orthozer, self._jkwork, self._tiles
-            side = self._coulomb_side(dm.device, own=True)
-            self._prep(work, dm, fac, True)
-            self._beside(side, lambda: lib.jk_stream_prepared(tiles, n, work, True))
-            potinfo, exc = self._vxc_exc(self._dm2densinfo(dm))
-            if self.xcfamily != 4:
-                vg = potinfo.grad if self.xcfamily == 2 else None
-                vm, vsc = lib.grid_vxc_raw(self._ao, n, self.dvolume, potinfo.value.contiguous(), None if vg is None else vg.contiguous())
-            else:
-                vm, vsc = self._vxc_ao_from_potinfo(potinfo), None
-            self._rejoin(side)
-            mat, en = lib.fock_finish_hybrid(work, x, n, a, vm, vscale=vsc, exc=exc, core=core)
-            self._energy_memo.put(_Energies(j=en[0], xc=None if exc is None else en[2], ka=en[1]), dm)
-            return mat
-        # the torch form of the same sum (DQC_AMD_FUSED_FOCK=0, an anonymous or strided input): what the fused kernels are tested against
-        dao = self._unconvert_dm(dm)
-        side = self._coulomb_side(dm.device, own=True)
-        jk = self._beside(side, lambda: self._jk_ao(dao, True), dao)
-        potinfo, exc = self._vxc_exc(self._dm2densinfo(dm))
-        vm = self._vxc_ao_from_potinfo(potinfo)
-        self._rejoin(side, jk[0])
-        self._rejoin(side, jk[1])
-        self._energy_memo.put(_Energies(j=0.5 * (dao * jk[0]).sum(), xc=None if exc is None else exc[0],
-                                        ka=-0.25 * a * (dao * jk[1]).sum()), dm)
-        mat = self._sym_orth(jk[0] - (0.5 * a) * jk[1] + vm[:n, :n])
-        return mat if core is None else core + mat
-
-    def get_elrep_plus_exchange_plus_vxc_pol(self, dm: SpinParam, core=None):
-        """the unrestricted form: stacked (2, nao, nao)  J[D_u + D_d] - a K[D_s] + Vxc_s[D_u, D_d]  (a get_exchange(dm) is -a K[2 D_s] / 2
-        = -a K[D_s] per spin, hcgto.py:238-241).  J and the two K from ONE pass over the tiles (dqc_jk_from_tiles_multi) on a second
-        stream beside the two-spin grid pass, one batched AO -> orthogonal conversion of the two sums"""
-        a = self.exx_fraction
-        assert self.xc is not None and dm.u.dim() == 2 and self.tiles_resident
-        self._check_hybrid(a)
-        n, x = self._nao_ao, self._orthozer
-        fu, fd = self._factor_of(dm.u), self._factor_of(dm.d)
-        one = fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1
-        side = self._coulomb_side(dm.u.device, own=True)
-        tiles = self._tiles
-
-        def jk():
+        def coulomb():  # (the AO-basis densities and their J, K: nothing the grid pass waits for)
+            if kfrac is None:
+                dt = (fu[0][0] @ fu[0][1] + fd[0][0] @ fd[0][1])[:n, :n].contiguous() if one else self._unconvert_dm(dm.u + dm.d)
+                return None, self._jk_ao(dt, False)[0], None
             if one:
                 ds = torch.stack([(fu[0][0] @ fu[0][1])[:n, :n], (fd[0][0] @ fd[0][1])[:n, :n]])
             else:
                 ds = self._unconvert_dm(torch.stack([dm.u, dm.d]))
                 ds = (ds + ds.transpose(-2, -1)) * 0.5
-            return (ds,) + lib.jk_multi(tiles, (ds[0] + ds[1]).unsqueeze(0), ds, self._multi_work(1, 2))
+            j, k = lib.jk_multi(tiles, (ds[0] + ds[1]).unsqueeze(0), ds, self._multi_work(1, 2))
+            return ds, j[0], k
 
-        ds, jao, kao = self._beside(side, jk)
+        if fused:
+            self._prep(work, None, [(torch.cat([fu[0][0], fd[0][0]], dim=1),)], False)
+            self._beside(side, lambda: lib.jk_stream_prepared(tiles, n, work, False))
+            outs = ()
+        else:
+            outs = ds, jao, kao = self._beside(side, coulomb)
         potinfo = self.xc.get_vxc(self._dm2densinfo_pol(dm))
         vu = self._vxc_ao_from_potinfo(potinfo.u)
         vd = self._vxc_ao_from_potinfo(potinfo.d)
-        for t in (ds, jao, kao):
-            self._rejoin(side, t)
-        # the exchange energy of this pair falls out of the build: E_K = -a / 2 sum_s tr D_s K[D_s]  (remembered per pair)
-        self._hybpol_memo.put(-0.5 * a * (ds * kao).sum(), dm.u, dm.d)
-        mat = x.transpose(-2, -1) @ torch.stack([jao[0] - a * kao[0] + vu[:n, :n], jao[0] - a * kao[1] + vd[:n, :n]]) @ x
+        self._rejoin(side, *outs)
+        if fused:  # (the two finishes share the scratch regions of the work buffer: stream order keeps them apart)
+            return torch.stack([lib.fock_finish(work, x, n, False, vxc_ao=v, core=core)[0] for v in (vu, vd)])
+        if kfrac is None:
+            mat = torch.stack([jao + vu[:n, :n], jao + vd[:n, :n]])
+        else:  # E_K = -a / 2 sum_s tr D_s K[D_s] of this pair falls out of the build
+            self._energy_memo.put(_Energies(ka=-0.5 * kfrac * (ds * kao).sum()), dm.u, dm.d)
+            mat = torch.stack([jao - kfrac * kao[0] + vu[:n, :n], jao - kfrac * kao[1] + vd[:n, :n]])
+        mat = x.transpose(-2, -1) @ mat @ x
         mat = (mat + mat.transpose(-2, -1)) * 0.5
         return mat if core is None else core + mat
+
+    # the public names of the builds (plain tensors in the orthogonalised basis; the operators' own sums up to round-off)
+    def get_elrep_plus_vxc(self, dm, core=None):
+        """J[D] + Vxc[D] of one restricted density matrix: get_elrep(dm) + get_vxc(dm) (ks.py:176-187)"""
+        return self._fock2e(dm, None, True, core)
+
+    def get_elrep_plus_exchange(self, dm, core=None):
+        """J[D] - K[D] / 2 of one restricted density matrix: get_elrep(dm) + get_exchange(dm) (hf.py:198-199)"""
+        return self._fock2e(dm, 1.0, False, core)
+
+    def get_elrep_plus_exchange_plus_vxc(self, dm, core=None):
+        """J[D] - a K[D] / 2 + Vxc[D] of one restricted density matrix, a = the exact-exchange fraction of the functional given to
+        setup_grid: get_elrep(dm) + a get_exchange(dm) + get_vxc(dm)"""
+        return self._fock2e(dm, self.exx_fraction, True, core)
+
+    def get_elrep_plus_vxc_pol(self, dm: SpinParam, core=None):
+        """stacked (2, nao, nao) J[D_u + D_d] + Vxc_s[D_u, D_d] of an unrestricted pair: get_elrep(dm.u + dm.d) + get_vxc(dm)"""
+        return self._fock2e_pol(dm, None, core)
+
+    def get_elrep_plus_exchange_plus_vxc_pol(self, dm: SpinParam, core=None):
+        """stacked (2, nao, nao) J[D_u + D_d] - a K[D_s] + Vxc_s[D_u, D_d] of an unrestricted pair"""
+        return self._fock2e_pol(dm, self.exx_fraction, core)
+
+    def _memo_energy(self, dm, field):
+        """E_J, E_xc, E_K or a E_K (`field` "j", "xc", "k", "ka") of `dm` (a pair: keyed on its two matrices) when the last build
+        formed it, else None"""
+        e = self._energy_memo.get(*((dm.u, dm.d) if isinstance(dm, SpinParam) else (dm,)))
+        return None if e is None else getattr(e, field)
 
     def get_e_exchange_hybrid(self, dm):
         """a E_K: the exact-exchange energy of a hybrid functional, get_e_exchange(dm) scaled by the functional's fraction (a by-product
         of the last hybrid build of `dm` when there was one)"""
-        a = self.exx_fraction
-        if isinstance(dm, SpinParam):
-            e = self._hybpol_memo.get(dm.u, dm.d)
-            return e if e is not None else a * self.get_e_exchange(dm)
         e = self._memo_energy(dm, "ka")
-        return e if e is not None else a * self.get_e_exchange(dm)
+        return e if e is not None else self.exx_fraction * self.get_e_exchange(dm)
 
     def timed_fock_kernels(self, dm, core):
         """measurement aid (bench.py): the restricted KS Fock build `core + get_elrep_plus_vxc(dm)` -- its own body, on this stream --
@@ -1154,7 +1099,7 @@ class HamiltonMI355(_Base):
             ev.append(torch.cuda.Event(enable_timing=True))
             ev[-1].record(torch.cuda.current_stream(self.device))
 
-        self._elrep_plus_vxc(dm, core.contiguous(), mark)
+        self._fock2e(dm, None, True, core.contiguous(), mark)
         return ["orth_transforms", "jk_tiles", "grid_density", "xc_eval", "grid_vxc", "fock_assemble"], ev
 
     def getparamnames(self, methodname: str, prefix: str = "") -> List[str]:

@@ -590,15 +590,29 @@ def jk_stream_prepared(tiles, nao, work, with_k):
                "dqc_jk_from_tiles" if with_k else "dqc_jk_from_tiles[J only]")
 
 
-def fock_finish(work, x, nao, with_k, vxc_ao=None, core=None, want_j=False):
-    """-> fock (north, north) = sym(X^T (J - K / 2 + V) X) + core, energies (2,) = [tr D J / 2, -tr D K / 4], J_ao or None"""
-    north = x.shape[1]
+def fock_finish(work, x, nao, with_k, vxc_ao=None, core=None, want_j=False, vscale=None, kfrac=None, exc=None):
+    """the closing launch of a fused Fock build -> fock (north, north) = sym(X^T (J - kfrac K / 2 + V) X) + core, energies, J_ao or None.
+    `vxc_ao`: a symmetric AO-basis matrix or, with their `vscale`, the raw sums of grid_vxc_raw.  Which entry point closes the build:
+    dqc_fock_finish_hybrid when a fraction `kfrac` and a Vxc are given -- energies (3,) = [tr D J / 2, -kfrac tr D K / 4, E_xc handed
+    through from the (1,) tensor `exc`]; dqc_fock_finish_vraw for raw sums without exchange; else dqc_fock_finish (K as a whole when
+    `with_k`, J_ao on request) -- energies (2,) = [tr D J / 2, -tr D K / 4]"""
+    north, nv = x.shape[1], 0 if vxc_ao is None else int(vxc_ao.shape[-1])
+    hybrid, raw = kfrac is not None and vxc_ao is not None, vscale is not None
+    assert (hybrid or kfrac is None) and not (want_j and (hybrid or raw)) and not (raw and with_k and not hybrid)
     fock = torch.empty((north, north), dtype=torch.float64, device=work.device)
-    en = torch.empty(2, dtype=torch.float64, device=work.device)
+    en = torch.empty(3 if hybrid else 2, dtype=torch.float64, device=work.device)
     jao = torch.empty((nao, nao), dtype=torch.float64, device=work.device) if want_j else None
     with _on(work.device) as st_:
-        _check(load().dqc_fock_finish(_ptr(fock), _ptr(en), _ptr(jao), _ptr(work), _ptr(vxc_ao), 0 if vxc_ao is None else vxc_ao.shape[-1],
-                                      _ptr(core), _ptr(x), int(nao), int(north), 1 if with_k else 0, st_), "dqc_fock_finish")
+        if hybrid:
+            _check(load().dqc_fock_finish_hybrid(_ptr(fock), _ptr(en), _ptr(work), _ptr(vxc_ao), nv, 1 if raw else 0,
+                                                 float(vscale) if raw else 0.0, float(kfrac), _ptr(exc), _ptr(core), _ptr(x),
+                                                 int(nao), int(north), st_), "dqc_fock_finish_hybrid")
+        elif raw:
+            _check(load().dqc_fock_finish_vraw(_ptr(fock), _ptr(en), _ptr(work), _ptr(vxc_ao), nv, float(vscale), _ptr(core),
+                                               _ptr(x), int(nao), int(north), st_), "dqc_fock_finish")
+        else:
+            _check(load().dqc_fock_finish(_ptr(fock), _ptr(en), _ptr(jao), _ptr(work), _ptr(vxc_ao), nv, _ptr(core), _ptr(x),
+                                          int(nao), int(north), 1 if with_k else 0, st_), "dqc_fock_finish")
     return fock, en, jao
 
 
@@ -1086,7 +1100,7 @@ def device_cu_count(device=None):
 
 def grid_vxc_raw(ao, nao, w, vrho, vgrad):
     """dqc_grid_vxc without the closing symmetrisation launch -> (raw (ld, ld) cross-block sums, their fixed-point scale or 0.0);
-    for fock_finish_vraw"""
+    for fock_finish"""
     ncomp = 1 if ao.dim() == 2 else ao.shape[0]
     ngrid = ao.shape[-2]
     ld = padded_nao(nao)
@@ -1096,31 +1110,6 @@ def grid_vxc_raw(ao, nao, w, vrho, vgrad):
         _check(load().dqc_grid_vxc_raw(_ptr(vm), _ptr(ao), ncomp, ngrid, nao, _ptr(w), _ptr(vrho), _ptr(vgrad), ctypes.byref(sc), st_),
                "dqc_grid_vxc" if vgrad is not None else "dqc_grid_vxc[no gradient term]")
     return vm, float(sc.value)
-
-
-def fock_finish_vraw(work, x, nao, vxc_raw, vscale, core=None):
-    """the Kohn-Sham finish on the raw sums of grid_vxc_raw -> fock (north, north), energies (2,)"""
-    north = x.shape[1]
-    fock = torch.empty((north, north), dtype=torch.float64, device=work.device)
-    en = torch.empty(2, dtype=torch.float64, device=work.device)
-    with _on(work.device) as st_:
-        _check(load().dqc_fock_finish_vraw(_ptr(fock), _ptr(en), _ptr(work), _ptr(vxc_raw), int(vxc_raw.shape[-1]), float(vscale), _ptr(core),
-                                           _ptr(x), int(nao), int(north), st_), "dqc_fock_finish")
-    return fock, en
-
-
-def fock_finish_hybrid(work, x, nao, kfrac, vxc, vscale=None, exc=None, core=None):
-    """the finish of a hybrid Kohn-Sham build -> fock (north, north) = sym(X^T (J - kfrac K / 2 + V) X) + core, energies (3,) =
-    [tr D J / 2, -kfrac tr D K / 4, E_xc handed through from the (1,) tensor `exc`].  `vxc`: the raw sums of grid_vxc_raw with their
-    `vscale`, or (vscale None) a symmetric AO-basis matrix"""
-    north = x.shape[1]
-    fock = torch.empty((north, north), dtype=torch.float64, device=work.device)
-    en = torch.empty(3, dtype=torch.float64, device=work.device)
-    with _on(work.device) as st_:
-        _check(load().dqc_fock_finish_hybrid(_ptr(fock), _ptr(en), _ptr(work), _ptr(vxc), int(vxc.shape[-1]), 0 if vscale is None else 1,
-                                             0.0 if vscale is None else float(vscale), float(kfrac), _ptr(exc), _ptr(core), _ptr(x),
-                                             int(nao), int(north), st_), "dqc_fock_finish_hybrid")
-    return fock, en
 
 
 def resp_kappa2dm(kappa, cv, co, scale):

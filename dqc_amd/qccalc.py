@@ -86,51 +86,37 @@ class _Engine:
 
     # Fock build -- THE hot path (hf.py:182-201, ks.py:176-187)
     def dm2scp(self, dm):
-        if self.exx != 0.0:
-            return self._dm2scp_hybrid(dm)
+        """F = h + J + Vxc[D] (Kohn-Sham), h + J + get_exchange(D) (Hartree-Fock) or h + J + a get_exchange(D) + Vxc[D] (a hybrid,
+        a = self.exx).  One (nao, nao) density or pair: one build of the Hamiltonian (hamilton.py: _fock2e, _fock2e_pol), the core
+        Hamiltonian added in its last launch; batched densities, and what the builds do not cover, through the operators' own sum"""
+        h, a = self.hamilton, self.exx
         if self.polarized:  # scp = stacked (F_u, F_d)  (hf.py:93-103)
             if not isinstance(dm, SpinParam):
                 dm = SpinParam(u=dm[0], d=dm[1])
-            h = self.hamilton
-            if not self.is_ks and h.df is None and hasattr(h, "get_elrep_exchange_pol") and dm.u.dim() == 2:
+            if dm.u.dim() == 2 and a != 0.0:
+                return h.get_elrep_plus_exchange_plus_vxc_pol(dm, core=self._core_matrix())
+            if dm.u.dim() == 2 and self.is_ks and h.tiles_resident:
+                return h.get_elrep_plus_vxc_pol(dm, core=self._core_matrix())
+            if dm.u.dim() == 2 and not self.is_ks and h.df is None:
                 # J[D_u + D_d], -K[2 D_u]/2, -K[2 D_d]/2 from ONE pass over the ERI tiles instead of three
                 J, kx = h.get_elrep_exchange_pol(dm)
-                core = self.knvext.fullmatrix() + J
-                return torch.stack([core + kx.u, core + kx.d])
-            if self.is_ks and dm.u.dim() == 2 and hasattr(h, "get_elrep_plus_vxc_pol") and h.tiles_resident:
-                # J + Vxc_s with one batched AO -> orthogonal conversion, the Coulomb stream beside the grid pass (hamilton.py)
-                return h.get_elrep_plus_vxc_pol(dm, core=self._core_matrix())
-            core = self.knvext + h.get_elrep(dm.u + dm.d)
+                hj = self.knvext.fullmatrix() + J
+                return torch.stack([hj + kx.u, hj + kx.d])
+            hj = self.knvext + h.get_elrep(dm.u + dm.d)
             v = h.get_vxc(dm) if self.is_ks else h.get_exchange(dm)
-            return torch.stack([(core + v.u).fullmatrix(), (core + v.d).fullmatrix()])
-        if self.is_ks and dm.dim() == 2 and hasattr(self.hamilton, "get_elrep_plus_vxc"):
-            # J + Vxc with one AO -> orthogonal conversion (the operators' own sum, ks.py:176-187, converts each)
-            return self.hamilton.get_elrep_plus_vxc(dm, core=self._core_matrix())
-        if not self.is_ks and dm.dim() == 2 and self.hamilton.df is None and hasattr(self.hamilton, "get_elrep_plus_exchange"):
-            # J - K / 2 with one AO -> orthogonal conversion (hf.py:198-199 converts each operator)
-            return self.hamilton.get_elrep_plus_exchange(dm, core=self._core_matrix())
-        elrep = self.hamilton.get_elrep(dm)
-        if self.is_ks:
-            fock = self.knvext + elrep + self.hamilton.get_vxc(dm)
-        else:
-            fock = self.knvext + elrep + self.hamilton.get_exchange(dm)
-        return fock.fullmatrix()
-
-    def _dm2scp_hybrid(self, dm):
-        """F = h + J + a get_exchange(D) + Vxc[D], a = self.exx: one fused build (hamilton.py: get_elrep_plus_exchange_plus_vxc and its
-        unrestricted form); batched densities through the operators' own sum"""
-        h, a = self.hamilton, self.exx
-        if self.polarized:
-            if not isinstance(dm, SpinParam):
-                dm = SpinParam(u=dm[0], d=dm[1])
-            if dm.u.dim() == 2:
-                return h.get_elrep_plus_exchange_plus_vxc_pol(dm, core=self._core_matrix())
-            core = self.knvext + h.get_elrep(dm.u + dm.d)
-            v, k = h.get_vxc(dm), h.get_exchange(dm)
-            return torch.stack([(core + v.u).fullmatrix() + a * k.u.fullmatrix(), (core + v.d).fullmatrix() + a * k.d.fullmatrix()])
-        if dm.dim() == 2:
+            fock = [(hj + v.u).fullmatrix(), (hj + v.d).fullmatrix()]
+            if a != 0.0:
+                k = h.get_exchange(dm)
+                fock = [fock[0] + a * k.u.fullmatrix(), fock[1] + a * k.d.fullmatrix()]
+            return torch.stack(fock)
+        if dm.dim() == 2 and a != 0.0:
             return h.get_elrep_plus_exchange_plus_vxc(dm, core=self._core_matrix())
-        return (self.knvext + h.get_elrep(dm) + h.get_vxc(dm)).fullmatrix() + a * h.get_exchange(dm).fullmatrix()
+        if dm.dim() == 2 and self.is_ks:
+            return h.get_elrep_plus_vxc(dm, core=self._core_matrix())
+        if dm.dim() == 2 and h.df is None:
+            return h.get_elrep_plus_exchange(dm, core=self._core_matrix())
+        fock = (self.knvext + h.get_elrep(dm) + (h.get_vxc(dm) if self.is_ks else h.get_exchange(dm))).fullmatrix()
+        return fock if a == 0.0 else fock + a * h.get_exchange(dm).fullmatrix()
 
     def scp2dm(self, scp):
         if self.polarized:
@@ -150,21 +136,15 @@ class _Engine:
 
     def dm2energy(self, dm):
         h = self.hamilton
-        if self.polarized:  # hf.py:166-172 / ks.py:157-166 with dmtot = dm.u + dm.d
-            tot = dm.u + dm.d
-            e = h.get_e_hcore(tot) + h.get_e_elrep(tot) + (h.get_e_xc(dm) if self.is_ks else h.get_e_exchange(dm))
-            if self.exx != 0.0:
-                e = e + h.get_e_exchange_hybrid(dm)
-            return e + self._enuc
-        e = h.get_e_hcore(dm) + h.get_e_elrep(dm)
-        e = e + (h.get_e_xc(dm) if self.is_ks else h.get_e_exchange(dm))
+        tot = SpinParam.sum(dm)  # hf.py:166-172 / ks.py:157-166: core and Coulomb terms see the total density
+        e = h.get_e_hcore(tot) + h.get_e_elrep(tot) + (h.get_e_xc(dm) if self.is_ks else h.get_e_exchange(dm))
         if self.exx != 0.0:  # a E_K of the hybrid functional (a by-product of the build of this density)
             e = e + h.get_e_exchange_hybrid(dm)
         return e + self._enuc
 
     def energy_parts(self, dm):
         h = self.hamilton
-        tot = SpinParam.sum(dm)  # hf.py:166-172: core and Coulomb terms see the total density
+        tot = SpinParam.sum(dm)
         p = {"e_core": float(h.get_e_hcore(tot)), "e_elrep": float(h.get_e_elrep(tot)),
              "e_nuc": float(self._system.get_nuclei_energy())}
         p["e_xc" if self.is_ks else "e_exch"] = float(h.get_e_xc(dm) if self.is_ks else h.get_e_exchange(dm))
