@@ -155,7 +155,20 @@ def set_generic_eri(on=True):
 def set_deterministic(on=True):
     """bit-reproducible Fock builds: the cross-block sums (J / K accumulators, split-K Vxc, purification trace) use fixed-point
     integer atomics instead of fp64 atomics (include/dqc_amd.h: dqc_set_deterministic).  Returns the previous setting.
-    Environment: DQC_AMD_DETERMINISTIC=1."""
+    Environment: DQC_AMD_DETERMINISTIC=1.
+
+    Fixed point is exact in any order but only as fine as its scale, and each of the three users sets the scale its own way
+    (tests/test_gpu_deterministic_kernels.py pins each against a host reference across input magnitudes):
+      J / K from tiles   per call, 2^k with 2 gmax max_q sum|D_q| 2^k < 2^61: any magnitude of D.  ONE scale for all densities of a
+                         jk_multi pass: every slot is exact to the largest slot's resolution (see jk_multi).
+      Vxc                `grid_vxc`, `grid_vxc_pair`: the potential is divided by a power of two c taken on the device from the
+                         call's own arrays -- 2^14 c >= B = sum_g A_g^2 |w_g| (|v_g| + 2 sum_d |vgrad_dg|) >= every partial sum, A_g
+                         the largest |AO value| at the point (one pass over an AO array, remembered with it) -- summed on the constant
+                         scale 2^47, and the result multiplied by c: any magnitude, no state shared between calls or streams.
+                         `grid_vxc_raw` (the fused Fock build's form) and the C entry points sum on 2^47 as they are: right
+                         for sums of order one (v_xc on normalised AOs); each addition rounds to 2^-47 ABSOLUTE and a sum beyond
+                         2^16 wraps.
+      purification       traces on the constant 2^46: spectra mapped to [0, 1], traces below 2^15 -- always the case."""
     return bool(load().dqc_set_deterministic(1 if on else 0))
 
 
@@ -735,7 +748,12 @@ def jk_multi(tiles, dms_j, dms_k, work=None, k_antisym=None):
     """ONE pass over the tiles for several density matrices: dms_j (nj, nao, nao) -> J (nj, nao, nao), dms_k (nk, nao, nao)
     -> K (nk, nao, nao) (plain K, not -K/2); either may be None.  AO basis, symmetrised.
     k_antisym: a sequence of nk flags; a flagged exchange density is ANTISYMMETRISED instead, (D - D^T) / 2, and its K[D]_pq =
-    (pr|qs) D_rs is antisymmetric (dqc_jk_from_tiles_multi_asym; two exchange densities of either kind share a pass)."""
+    (pr|qs) D_rs is antisymmetric (dqc_jk_from_tiles_multi_asym; two exchange densities of either kind share a pass).
+    Deterministic mode, the contract of the shared scale: the densities of one pass (all of dms_j and the first two of dms_k; then two of
+    dms_k per pass) are summed on ONE fixed-point scale, set by the largest sum_ij |D_ij| among them.  Every J and K of the pass is
+    therefore exact to 1e-12 of the LARGEST result of the pass, not of its own: a density 2^-27 times smaller than its partner keeps
+    about eight digits less.  The scale depends on the largest density alone, so its results are bit for bit those it has beside any
+    smaller partner.  Densities of very different size that each need full relative accuracy go in separate calls."""
     ref = dms_j if dms_j is not None else dms_k
     nao, dev = ref.shape[-1], ref.device
     nj = 0 if dms_j is None else dms_j.shape[0]
@@ -1034,21 +1052,75 @@ def grid_vxc_pair(ao_a, ao_b, nao, w, v, what="dqc_grid_vxc_pair"):
     """sym( sum_g w_g v_g a_ga b_gb ) -> (ld, ld)   (`what`: the name this call is listed under by call_trace)"""
     ngrid, ld = ao_a.shape[0], padded_nao(nao)
     vm = torch.empty((ld, ld), dtype=torch.float64, device=ao_a.device)
+    unit = None if not load().dqc_get_deterministic() else _vxc_det_unit(w, v, None, _ao_envelope(ao_a), _ao_envelope(ao_b))
+    if unit is not None:
+        v = v * unit[1]
     with _on(ao_a.device) as st_:
         _check(load().dqc_grid_vxc_pair(_ptr(vm), _ptr(ao_a), _ptr(ao_b), ngrid, nao, _ptr(w), _ptr(v), st_), what)
-    return vm
+    return vm if unit is None else vm.mul_(unit[0])
+
+
+def _ao_envelope(ao):
+    """(ngrid,) max |a| over the AO axis of an (ngrid, lda) array, over the components as well of a (ncomp, ngrid, lda) one.  One
+    pass over the array, made once: the result is kept on the tensor that owns the storage (the views a caller slices off a resident
+    AO array share it), per view, per stream and per version of the storage (an in-place write makes a new one).  Not kept while a
+    graph is being captured (the memory would belong to the graph)."""
+    owner = ao._base if ao._base is not None else ao
+    key = (ao.data_ptr(), tuple(ao.shape), tuple(ao.stride()), ao._version, torch.cuda.current_stream(ao.device).cuda_stream if ao.is_cuda else 0)
+    memo = owner.__dict__.setdefault("_dqc_envelope", {})
+    env = memo.get(key)
+    if env is None:
+        env = torch.linalg.vector_norm(ao, float("inf"), dim=-1)
+        env = env if env.dim() == 1 else env.amax(0)
+        if not (ao.is_cuda and torch.cuda.is_current_stream_capturing()):
+            if len(memo) >= 16:
+                memo.clear()
+            memo[key] = env
+    return env
+
+
+def _pow2(e):
+    """2^e as a float64 tensor from the integer tensor e (|e| <= 1000), put together from the exponent bits: exact"""
+    return ((e.to(torch.int64).clamp(-1000, 1000) + 1023) << 52).view(torch.float64)
+
+
+def _vxc_det_unit(w, vrho, vgrad, env_a, env_b):
+    """deterministic mode: (c, 1 / c) as 0-dim device tensors, c a power of two that follows THIS call's arrays -- the split-K sums of
+    the Vxc kernels are fixed-point integers on the CONSTANT scale 2^47 (csrc/grid_vxc.hip), which fits sums below 2^16; the wrappers
+    hand the kernels v / c and return c V[v / c] = V[v], both exact.  c comes from the bound
+        |sum_g a_gi w_g (v_g b_gj + 2 sum_d vg_dg d_d b_gj)| <= B = sum_g A_g B_g |w_g| (|v_g| + 2 sum_d |vg_dg|),
+    A_g, B_g the envelopes max_i |a_gi|, max_j,comp |b_gj| of the two AO operands (_ao_envelope: no pass over the AO arrays per
+    call), which holds for every partial sum too: c = 2^-14 times a power of two >= B, so |V[v / c]| <= 2^14 and one addition rounds
+    to 2^-61 B -- the rule of the J / K accumulators (jk_det_scale_kernel).  B is summed EXACTLY: the terms are rounded up to
+    30-bit integers relative to the largest and added as int64, so c does not depend on the order of a reduction and repeats bit for
+    bit; nothing is read back to the host (the call can be captured in a graph) and nothing outlives the call.  None with the
+    mode off (the kernels then run on the caller's arrays as they are) and for an empty grid."""
+    if w.numel() == 0 or not load().dqc_get_deterministic():
+        return None
+    t = vrho.abs() if vgrad is None else vrho.abs() + 2.0 * vgrad.abs().sum(0)
+    t = t * w.abs() * env_a * env_b
+    e = torch.frexp(t.max())[1].clamp(-1000, 1000)            # every term < 2^e (frexp(0) = (0, 0))
+    total = torch.ceil(t * _pow2(30 - e)).to(torch.int64).sum()   # terms <= 2^30 each: B <= total 2^(e - 30), exact below 2^33 points
+    ec = torch.frexp(total.to(torch.float64))[1] + e - 44      # total <= 2^frexp: B 2^-14 <= 2^ec
+    return _pow2(ec), _pow2(-ec)
 
 
 def grid_vxc(ao, nao, w, vrho, vgrad):
-    """-> (ld, ld) symmetric AO-basis Vxc matrix (zero padded)"""
+    """-> (ld, ld) symmetric AO-basis Vxc matrix (zero padded).  Deterministic mode: any magnitude of the potential (_vxc_det_unit)"""
     ncomp = 1 if ao.dim() == 2 else ao.shape[0]
     ngrid = ao.shape[-2]
     ld = padded_nao(nao)
     vm = torch.empty((ld, ld), dtype=torch.float64, device=ao.device)
+    unit = None
+    if load().dqc_get_deterministic():
+        env = _ao_envelope(ao if ao.dim() == 2 else (ao[0] if vgrad is None else ao[:4]))
+        unit = _vxc_det_unit(w, vrho, vgrad, env, env)
+    if unit is not None:
+        vrho, vgrad = vrho * unit[1], None if vgrad is None else vgrad * unit[1]
     with _on(ao.device) as st_:
         _check(load().dqc_grid_vxc(_ptr(vm), _ptr(ao), ncomp, ngrid, nao, _ptr(w), _ptr(vrho), _ptr(vgrad), st_),
                "dqc_grid_vxc" if vgrad is not None else "dqc_grid_vxc[no gradient term]")
-    return vm
+    return vm if unit is None else vm.mul_(unit[0])
 
 
 class PartitionStream:
@@ -1100,7 +1172,8 @@ def device_cu_count(device=None):
 
 def grid_vxc_raw(ao, nao, w, vrho, vgrad):
     """dqc_grid_vxc without the closing symmetrisation launch -> (raw (ld, ld) cross-block sums, their fixed-point scale or 0.0);
-    for fock_finish"""
+    for fock_finish.  Deterministic mode: the scale is the constant 2^47 and the potential is summed as it is -- right for matrices
+    with elements of order one (v_xc on normalised AOs), not for arbitrary magnitudes: those go through grid_vxc (set_deterministic)"""
     ncomp = 1 if ao.dim() == 2 else ao.shape[0]
     ngrid = ao.shape[-2]
     ld = padded_nao(nao)

@@ -424,7 +424,8 @@ int dqc_grid_vxc_pair(double *d_vmat, const double *d_ao_a, const double *d_ao_b
                       const double *d_w, const double *d_v, void *stream);
 
 /* dqc_grid_vxc without its closing symmetrisation: d_vmat (ld, ld) <- the raw sums M; V = (M + M^T) / 2 on the first nao rows / columns
- * (fixed-point integers of scale *h_scale in deterministic mode, *h_scale = 0 otherwise) -- consumed by dqc_fock_finish_vraw */
+ * (fixed-point integers of scale *h_scale in deterministic mode, *h_scale = 0 otherwise) -- consumed by dqc_fock_finish_vraw.
+ * *h_scale is the constant 2^47: see dqc_set_deterministic for the magnitudes of the potential this is meant for */
 int dqc_grid_vxc_raw(double *d_vmat, const double *d_ao, int ncomp, int ngrid, int nao, const double *d_w, const double *d_vrho,
                      const double *d_vgrad, double *h_scale, void *stream);
 
@@ -486,7 +487,19 @@ int dqc_direct_destroy(void *ctx);
  * iterate): the order of the additions, hence the last bits of the result, vary from run to run, while the reference's CPU
  * path is deterministic.  dqc_set_deterministic(1) switches those sums to fixed-point 64-bit INTEGER atomics (associative:
  * bit-identical results whatever the order; contributions are rounded to 2^-k with k chosen per call from a rigorous bound
- * of the sum: 2 max(ii|ii) sum|D_ij| for J / K, 2^14 for V).  Process-wide, returns the previous setting. */
+ * of the sum: 2 max(ii|ii) sum|D_ij| for J / K, 2^14 for V).  Process-wide, returns the previous setting.
+ * Valid magnitudes of the inputs in this mode:
+ *   dqc_jk_from_tiles*, dqc_fock_finish*    any: the scale follows sum|D_ij| of the call.  The densities of one pass of
+ *                                           dqc_jk_from_tiles_multi share ONE scale, set by the largest: each result is exact to
+ *                                           ~1e-12 of the largest result of the pass, not of its own.
+ *   dqc_grid_vxc, _raw, _pair               the CONSTANT scale 2^47, whatever the potential: every addition rounds to 2^-47 = 7e-15
+ *                                           ABSOLUTE and a sum beyond 2^16 wraps silently.  Meant for matrices with elements of
+ *                                           order one, as V_xc on normalised AOs.  A caller with potentials of another size
+ *                                           hands over v / c, c a power of two chosen so that no sum of the call exceeds 2^14
+ *                                           (e.g. from sum_g max_i |phi_gi|^2 |w_g v_g|), and multiplies the result by c -- both
+ *                                           exact; the Python entry points lib.grid_vxc / lib.grid_vxc_pair do so on the device.
+ *   dqc_purify_tc2*, dqc_projector_tc2      the constant 2^46 for traces of iterates with spectrum in [0, 1] (below 2^15: n <= 32768)
+ *                                           and, in dqc_projector_tc2, for the Gershgorin row sums of the Fock matrix (below 2^17). */
 int dqc_set_deterministic(int on);
 int dqc_get_deterministic(void);
 

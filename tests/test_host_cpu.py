@@ -621,3 +621,38 @@ def test_eri_pair_tables_host_logic_without_a_gpu(name, basis):
         assert lib.eri_pair_stats(tab, True)["groups"] == 84 and lib.eri_pair_stats(tab, True)["primitive_quartets"] < 0.32 * lib.eri_pair_stats(tab, False)["primitive_quartets"]
     if basis == "sto-3g":  # s and p share exponents but not the angular momentum: nothing to merge
         assert lib.eri_pair_stats(tab, True) == lib.eri_pair_stats(tab, False)
+
+
+def test_vxc_deterministic_unit_bounds_the_sums_and_is_a_power_of_two():
+    """the per-call normalisation of lib.grid_vxc / grid_vxc_pair in deterministic mode (lib._vxc_det_unit), on host tensors: c is a
+    power of two with c / c^-1 exact, 2^14 c bounds every element of the matrix by at most a factor 2 above the bound B it is built
+    from, it follows the potential exactly (v 2^k -> c 2^k), a zero potential gives a finite c, and the AO envelope of a view of a
+    resident array is computed once (tests/test_gpu_deterministic_kernels.py holds the kernels to it on the GPU)"""
+    import math
+    from dqc_amd import lib
+    gen = torch.Generator().manual_seed(5)
+    ngrid, nao = 1031, 19
+    flat = torch.randn(4 * ngrid * nao + 64, dtype=torch.float64, generator=gen)
+    ao = flat[:4 * ngrid * nao].view(4, ngrid, nao)
+    w = torch.rand(ngrid, dtype=torch.float64, generator=gen) * torch.exp2(-20.0 * torch.rand(ngrid, dtype=torch.float64, generator=gen))
+    v, vg = torch.randn(ngrid, dtype=torch.float64, generator=gen), torch.randn((3, ngrid), dtype=torch.float64, generator=gen)
+    env = lib._ao_envelope(ao)
+    assert torch.equal(env, ao.abs().amax(dim=(0, 2))) and lib._ao_envelope(flat[:4 * ngrid * nao].view(4, ngrid, nao)) is env
+    assert lib._ao_envelope(ao[0]) is lib._ao_envelope(ao[0]) and torch.equal(lib._ao_envelope(ao[0]), ao[0].abs().amax(dim=1))
+    prev = lib.set_deterministic(False)
+    try:
+        assert lib._vxc_det_unit(w, v, vg, env, env) is None
+        lib.set_deterministic(True)
+        assert lib._vxc_det_unit(w[:0], v[:0], vg[:, :0], env[:0], env[:0]) is None
+        bound = float((env * env * w * (v.abs() + 2.0 * vg.abs().sum(0))).sum())
+        psi = (w * v)[:, None] * ao[0] + 2 * (w[None, :, None] * vg[:, :, None] * ao[1:]).sum(0)
+        top = float((ao[0].T @ psi).abs().max())
+        for k in (-40, 0, 20):
+            c, cinv = lib._vxc_det_unit(w, v * 2.0 ** k, vg * 2.0 ** k, env, env)
+            c, cinv = float(c) / 2.0 ** k, float(cinv) * 2.0 ** k
+            assert c * cinv == 1.0 and math.frexp(c)[0] == 0.5
+            assert bound <= 2.0 ** 14 * c <= 2.0 * bound * (1.0 + 2.0 ** -20) and top <= 2.0 ** 14 * c
+        c, cinv = lib._vxc_det_unit(w, v * 0.0, vg * 0.0, env, env)
+        assert math.isfinite(float(c)) and float(c) * float(cinv) == 1.0
+    finally:
+        lib.set_deterministic(prev)
