@@ -744,7 +744,6 @@ int dqc_direct_jk_part(void *ctx, double *d_J, double *d_K, const double *d_dm, 
     og.kacc = d_K ? c.d_b : nullptr;
     og.part = part;
     og.nparts = nparts;
-    if (const char *e = getenv("DQC_ERI_DBG")) og.dbg = atoi(e);  // timing experiments (eri_core.hpp)
     if (const char *e = getenv("DQC_ERI_SPLIT_PER")) c.split_per = atoi(e) > 0 ? atoi(e) : 1 << 30;
     og.split_per = c.split_per;
     if (const char *e = getenv("DQC_ERI_FLIP1")) c.flip1 = atoi(e) != 0;
@@ -838,7 +837,6 @@ int dqc_eri_fill_tiles_part(double *d_tiles_part, const int *atm, int natm, cons
     og.st_lo = lo;
     og.st_hi = hi;
     og.st_nao = b.nao;
-    if (const char *e = getenv("DQC_ERI_DBG")) og.dbg = atoi(e);
     // depth-binned wave maps of the one-lane classes (DQC_ERI_WMAP=0: the plain wave-transposed map, A/B runs)
     static const bool wmap_env = [] { const char *e = getenv("DQC_ERI_WMAP"); return !(e && e[0] == '0'); }();
     WaveMaps wm;

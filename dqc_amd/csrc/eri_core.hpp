@@ -260,7 +260,6 @@ struct EriOut {
     int wbin[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int flip1 = 0;      // screened maps of the one-lane classes with a larger bra than ket block: bra-uniform entries (see FLIP1)
     int split_per = 16; // screened maps of the multi-lane classes: primitive quartets per lane group below which a quartet is not spread further
-    int dbg = 0;  // timing experiments (DQC_ERI_DBG): 1 = skip the primitive loops, 2 = skip the output phase, 4 = skip the tile stores only, 8 = skip the Coulomb atomics of the direct modes
     // ---- one molecule sharded over GPUs (dqc_direct_jk_part): this launch is part `part` of `nparts` interleaved block sets
     int part = 0, nparts = 1;
     // ---- TILES mode: slice [st_lo, st_hi) (double offsets) of the store this launch fills (dqc_eri_fill_tiles_part)
@@ -531,8 +530,7 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
     }
     const int pb0 = prs.pp_off[ib], nbp = prs.pp_off[ib + 1] - pb0;
     const int pk0 = prk.pp_off[ik], nkp = prk.pp_off[ik + 1] - pk0;
-    const bool loops_on = active && !(og.dbg & 1);
-    const int nq = loops_on ? nbp * nkp : 0;
+    const int nq = active ? nbp * nkp : 0;
 
     int maxq = nq;  // groups inside a wave: the wave simply runs until its longest quartet is done (`on` masks the others)
     if (TPQ > 64) {  // the group is the block: block-uniform trip count so that the barriers below are legal
@@ -565,7 +563,7 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
         int psk = 1;
         while (psk < psl && psk < nkp) psk <<= 1;
         const int psb = psl / psk, jb = psj / psk, jk = psj % psk;
-        for (int ipb = jb; ipb < (loops_on ? nbp : 0); ipb += psb) {
+        for (int ipb = jb; ipb < (active ? nbp : 0); ipb += psb) {
             const double *pb = prs.pp + (size_t)(pb0 + ipb) * prs.stride;
             // NE == 1: the coefficient rides in the prefactor; grouped: the primitive integral is formed without coefficients,
             // summed over the ket primitives per ket slot (tk) and spread over the bra slots once per bra primitive pair
@@ -854,7 +852,6 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
         }
         return;
     }
-    if (og.dbg & 2) return;
     // ---------------- phase C: Cartesian -> solid harmonics (LDS), scatter to tiles ----------------
     // once per member combination of a grouped quartet (NE == 1: the shell quartet itself).  Members: bra slot eb = 2 xa + xb
     // ((s s| pairs; xb alone for (l s|), ket alike; a combination is an ordinary shell quartet with its own AO offsets.  Of the
@@ -931,7 +928,7 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                 // elements.  ONE of the two is written (its images cover both positions): the store is bitwise reproducible
                 const bool twin = (ai == aj && mb > ma) || (ak == al && md > mc) ||
                                   (ai == ak && aj == al && mc * Cfg::SD + md > ma * Cfg::SB + mb);
-                if (!twin && (!(og.dbg & 4) || v == 12345.678)) tile_put_all(tiles, i, j, k, l, v, og.st_lo, og.st_hi, og.st_nao);
+                if (!twin) tile_put_all(tiles, i, j, k, l, v, og.st_lo, og.st_hi, og.st_nao);
             } else if (MODE == ERI_OUT_3C) {
                 const size_t io = i - og.ao0, jo = j - og.ao0, kx = k - og.aux0;
                 tiles[(io * og.nao + jo) * og.naux + kx] = v;
@@ -984,8 +981,8 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                 }
                 if (share_ab) {
                     for (int o = TPQ; o < 64; o <<= 1) a_ += __shfl_xor(a_, o);
-                    if (grp0 && a_ != 0.0 && (!(og.dbg & 8) || a_ == 12345.678)) atomicAdd(og.jacc + (size_t)(ai0 + ab / Cfg::SB) * n + aj0 + ab % Cfg::SB, a_);
-                } else if (act && (!(og.dbg & 8) || a_ == 12345.678)) {
+                    if (grp0 && a_ != 0.0) atomicAdd(og.jacc + (size_t)(ai0 + ab / Cfg::SB) * n + aj0 + ab % Cfg::SB, a_);
+                } else if (act) {
                     atomicAdd(og.jacc + (size_t)(ai + ab / Cfg::SB) * n + aj + ab % Cfg::SB, a_);
                 }
             }
@@ -1001,8 +998,8 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                 }
                 if (share_cd) {
                     for (int o = 1; o < 64; o <<= 1) a_ += __shfl_xor(a_, o);
-                    if ((tid & 63) == 0 && a_ != 0.0 && (!(og.dbg & 8) || a_ == 12345.678)) atomicAdd(og.jacc + (size_t)(ak0 + cd / Cfg::SD) * n + al0 + cd % Cfg::SD, a_);
-                } else if (act && (!(og.dbg & 8) || a_ == 12345.678)) {
+                    if ((tid & 63) == 0 && a_ != 0.0) atomicAdd(og.jacc + (size_t)(ak0 + cd / Cfg::SD) * n + al0 + cd % Cfg::SD, a_);
+                } else if (act) {
                     atomicAdd(og.jacc + (size_t)(ak + cd / Cfg::SD) * n + al + cd % Cfg::SD, a_);
                 }
             }

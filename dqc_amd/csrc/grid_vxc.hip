@@ -1,16 +1,26 @@
-// grid_vxc.hip -- the Vxc matrix M = Phi^T Psi: the second GEMM-shaped pass over the cached AO matrix
-// AO matrix (reference: HamiltonCGTO._dm2densinfo hcgto.py:371-443 and _get_vxc_from_potinfo
-// hcgto.py:445-495, which run them as chunked torch.matmul + einsum on the CPU).
+// grid_vxc.hip -- the Vxc matrix V = (M + M^T) / 2, M = Phi^T Psi, from the cached AO matrix on the grid
+// (reference: HamiltonCGTO._get_vxc_from_potinfo, hcgto.py:445-495, which runs it as chunked torch.matmul + einsum on the
+// CPU).  The density pass over the same AO matrix lives in grid_density.hip.
 //
-// Both kernels are fp64 MFMA (v_mfma_f64_16x16x4_f64) GEMMs whose operands stream from HBM exactly
-// once per pass; the element-wise parts of the reference (row dots, v*phi, symmetrisation) are
-// fused into the prologue/epilogue so nothing of size (ngrid, nao) is ever written back.
+//   Psi = w (vrho Phi + sum_d 2 vgrad_d dPhi_d)      GGA: four AO components (dqc_grid_vxc, dqc_grid_vxc_raw)
+//   Psi = w v Phi_b                                  one component; Phi_b == Phi: LDA Vxc, the tau terms of a meta-GGA
+//                                                    (symmetric M), Phi_b != Phi: the "pair" form (dqc_grid_vxc_pair)
 //
-//   density:  A = Phi[32 pts x n] . D[n x n] per wave, accumulators stay in registers, epilogue
-//             rho_g = sum_j A_gj Phi_gj , grad rho_g = 2 sum_j A_gj dPhi_gj   (16-lane DPP reduce)
-//   vxc:      M = Phi^T . Psi,  Psi = w (vrho Phi + sum_d 2 vgrad_d dPhi_d), split-K over point slabs,
-//             16-point chunks staged once in LDS (Psi is formed on the way in), every wave owns an equal
-//             share of the 16x16 output tiles, partial sums reduced with fp64 atomics; V = (M + M^T)/2.
+// Every kernel here is an fp64 MFMA (v_mfma_f64_16x16x4_f64) GEMM, split-K over slabs of grid points, whose operands stream
+// from HBM once per block: 16-point chunks of (Phi, Psi) are staged in double-buffered LDS -- Psi is formed on the way in, so
+// nothing of size (ngrid, nao) is ever written back -- by PRODUCER waves while CONSUMER waves do nothing but fragment reads
+// and MFMAs; the blocks' partial sums meet in fp64 atomics (deterministic mode: fixed point) and symmetrize_kernel closes.
+// Four kernel families, chosen by the number T of 16 x 16 tile rows and the form (grid_vxc_impl at the end of the file):
+//   vxc_ws_kernel    T <= 9 (GGA), T <= 13 (pair), T <= 9 and T = 14, 15 (one operand): linear tile split over 1-2 blocks per slab
+//   vxc_wsu_kernel   10 <= T <= 13, one operand, no gradient term:       one block per slab, upper-triangular tiles
+//   vxc_wsd_kernel   10 <= T <= 13, GGA:                                 the same, two MFMAs per off-diagonal tile
+//   vxc_ws2_kernel   everything larger:                                  rectangles of <= 9 x 12 tiles per block
+//
+// Shared by all of them:
+//   ld  = 16 T: rows / columns of the output matrix and the tile-padded width of an AO row that is staged;
+//   lda = row stride of the AO arrays in HBM (dqc_ao_stride).  Where lda < ld, columns lda .. ld - 1 of a staged row are the
+//         first doubles of the next row: finite values that only reach rows / columns of M that symmetrize_kernel zeroes;
+//   LS  = LDS row stride of a staged chunk, == 16 (mod 32) so that the ds_read_b64 fragment reads are conflict-free.
 //
 // f64 MFMA fragment layout (gfx950): A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15],
 // C[row = (lane>>4) + 4*reg][col = lane&15].
@@ -23,175 +33,24 @@ int vxc_cus_cap();  // host.hip: dqc_set_vxc_cus / DQC_VXC_CUS
 // fixed-point scale of the split-K accumulation into V in deterministic mode (0: fp64 atomics); common.hpp: acc_add
 __device__ double g_vxc_det_scale = 0.0;
 
-// ---------------------------------------------------------------------------------------------
-// Vxc:  M = Phi^T . Psi, split-K over point slabs.  16-point chunks of Phi and Psi live in double-buffered
-// LDS; the next chunk's four AO components are prefetched into registers while the MFMAs run, combined into
-// Psi and stored to the other buffer afterwards.  The 16x16 output tiles are dealt evenly to the 8 waves of
-// NSPLIT co-scheduled blocks (same XCD, so the slab is fetched from HBM once).
-// ---------------------------------------------------------------------------------------------
-constexpr int VXC_KC = 16;      // points per LDS chunk
-constexpr int VXC_WAVES = 8;    // waves per block
-
-template <int MAXT, int NL, int KCH, bool GGA>
-__global__ __launch_bounds__(512, 2) void vxc_kernel(double *__restrict__ vmat, const double *__restrict__ ao,
-                                                     int ngrid, int ld, const double *__restrict__ w,
-                                                     const double *__restrict__ vrho, const double *__restrict__ vgrad,
-                                                     int slab, int nsplit, int tiles_per_split,
-                                                     const double *__restrict__ aob, int lda, int LS) {
-    // aob: LDA mode only -- array the Psi operand is built from (== ao except for the "pair" form ao^T diag(w v) aob)
-    // lda: row stride of the AO arrays in HBM (dqc_ao_stride); ld = 16 T: the tile-padded width that is staged (columns
-    // lda .. ld - 1 of a row are the first doubles of the next row: finite values that only reach discarded rows / columns
-    // of M); LS: LDS row stride, == 16 (mod 32) so that the fragment reads are conflict-free
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int BUF = 2 * KCH * LS;  // phi + psi
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int lr = lane & 15, lk = lane >> 4;
-    const int T = ld >> 4, ttot = T * T;
-    const size_t cs = (size_t)ngrid * lda;
-
-    // XCD-aware decode: the nsplit blocks that share a slab get ids 8 apart -> same XCD, dispatched together
-    const int id = blockIdx.x;
-    const int grp = id / (8 * nsplit), rem = id - grp * 8 * nsplit;
-    const int split = rem / 8, sl = grp * 8 + (rem & 7);
-    const int gs = sl * slab, ge = min(gs + slab, ngrid);
-    if (gs >= ngrid) return;
-    const int tc0 = split * tiles_per_split;
-    const int tc1 = min(tc0 + tiles_per_split, ttot);
-    const int per_wave = (tc1 - tc0 + VXC_WAVES - 1) / VXC_WAVES;
-    const int t0 = tc0 + wave * per_wave;
-    const int nt = max(0, min(per_wave, tc1 - t0));
-
-    v4d acc[MAXT];
-    unsigned offab[MAXT];  // LDS offsets of the A (low 16 bits) and B (high 16 bits) fragments
-#pragma unroll
-    for (int t = 0; t < MAXT; t++) {
-        acc[t] = v4d{0, 0, 0, 0};
-        const int tid2 = min(t0 + t, ttot - 1);
-        offab[t] = (unsigned)(lk * LS + (tid2 / T) * 16 + lr) | ((unsigned)(KCH * LS + lk * LS + (tid2 % T) * 16 + lr) << 16);
-    }
-
-    // staging roles: a thread serves ONE row of the chunk (row = tid / TPR) and up to NL double2 columns of it, so
-    // its four Psi coefficients are loaded once; the raw AO loads stay in flight during the MFMA phase and are
-    // only combined into Psi when they are written to LDS afterwards.
-    constexpr int TPR = 512 / KCH;       // threads per row
-    const int prow = tid / TPR, pcol = tid % TPR;
-    double2 raw[NL][GGA ? 4 : 2];  // LDA mode: [0] = phi (A operand), [1] = the array Psi is built from
-    double cf[GGA ? 4 : 1], wg = 0.0;  // RAW loads here; the products are formed in stage() so that prefetch() never
-    bool rowok = false;                // waits on memory (a wait here idles the matrix pipe at every chunk start)
-    // the next chunk's loads are issued in KCH/4 slices BETWEEN the MFMA groups of the current chunk: waves issue in
-    // order, and a wave that first has to push its whole 16 KB prefetch through the CU's address pipe (128 KB per chunk
-    // for the 8 waves) starts its MFMAs thousands of cycles late
-    const double *src = ao;
-    const double *srcb = aob;
-    auto prefetch_meta = [&](int gc) {
-        const int g = gc + prow;
-        rowok = g < ge;
-        const int gg = rowok ? g : gs;
-        wg = w[gg];
-        cf[0] = vrho[gg];
-        if (GGA) {
-#pragma unroll
-            for (int d = 0; d < 3; d++) cf[d + 1] = vgrad[(size_t)d * ngrid + gg];
-        }
-        src = ao + (size_t)gg * lda;
-        srcb = aob + (size_t)gg * lda;
-    };
-    auto prefetch_cols = [&](int part) {
-#pragma unroll
-        for (int i = 0; i < NL; i++) {
-            if (i % (KCH / 4) != part) continue;
-            const int c2 = (pcol + i * TPR) * 2;
-            const int cc = c2 < ld ? c2 : 0;
-#pragma unroll
-            for (int d = 0; d < (GGA ? 4 : 1); d++)
-#ifndef ABL_VXC_NO_LOAD
-                raw[i][d] = *reinterpret_cast<const double2 *>(src + d * cs + cc);
-#else
-                raw[i][d] = make_double2(1e-3 * cc, 2e-3 * d);
-#endif
-            if (!GGA) raw[i][1] = *reinterpret_cast<const double2 *>(srcb + cc);
-        }
-    };
-    auto stage = [&](int buf) {
-        const double ww = rowok ? wg : 0.0;
-        cf[0] *= ww;
-        if (GGA) {
-#pragma unroll
-            for (int d = 1; d < 4; d++) cf[d] *= 2.0 * ww;
-        }
-#pragma unroll
-        for (int i = 0; i < NL; i++) {
-            const int c2 = (pcol + i * TPR) * 2;
-            if (c2 < ld) {
-                double2 ph = raw[i][0];
-                const double2 pb = GGA ? ph : raw[i][1];
-                double2 ps = make_double2(cf[0] * pb.x, cf[0] * pb.y);
-                if (GGA) {
-#pragma unroll
-                    for (int d = 1; d < 4; d++) { ps.x += cf[d] * raw[i][d].x; ps.y += cf[d] * raw[i][d].y; }
-                }
-                if (!rowok) ph = make_double2(0.0, 0.0);
-                *reinterpret_cast<double2 *>(lds + buf * BUF + prow * LS + c2) = ph;
-                *reinterpret_cast<double2 *>(lds + buf * BUF + KCH * LS + prow * LS + c2) = ps;
-            }
-        }
-    };
-
-    prefetch_meta(gs);
-#pragma unroll
-    for (int part = 0; part < KCH / 4; part++) prefetch_cols(part);
-    stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int gc = gs; gc < ge; gc += KCH) {
-        const bool more = gc + KCH < ge;
-        if (more) prefetch_meta(gc + KCH);
-        const double *base = lds + buf * BUF;
-#pragma unroll
-        for (int kk = 0; kk < KCH / 4; kk++) {
-            if (more) prefetch_cols(kk);
-            const int ko = kk * 4 * LS;
-#pragma unroll
-            for (int t = 0; t < MAXT; t++) {  // straight-line: tiles past nt are clamped duplicates, discarded later
-                const double a = base[ko + (offab[t] & 0xffffu)];
-                const double b = base[ko + (offab[t] >> 16)];
-#ifndef ABL_VXC_NO_MFMA
-                acc[t] = mfma_f64(a, b, acc[t]);
-#else
-                acc[t][0] += a * b;
-#endif
-            }
-        }
-        if (more) stage(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-#pragma unroll
-    for (int t = 0; t < MAXT; t++) {
-        if (t < nt) {
-            const int tl = t0 + t;
-            const int ia = (tl / T) * 16 + lk, ib = (tl % T) * 16 + lr;
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-#ifdef ABL_VXC_NO_ATOMIC
-                if (acc[t][r] == 12345.678)
-#endif
-                    acc_add(&vmat[(size_t)(ia + 4 * r) * ld + ib], acc[t][r], g_vxc_det_scale);
-        }
-    }
-}
+constexpr int VXC_WAVES = 8;    // consumer (MFMA) waves per block
 
 // ---------------------------------------------------------------------------------------------
-// Vxc, wave-specialised variant (the default).  Measured on MI355X: a SIMD reaches the fp64 MFMA peak (one
+// Vxc, wave-specialised, linear tile split (small bases).  Measured on MI355X: a SIMD reaches the fp64 MFMA peak (one
 // 16x16x4 per 64.6 cycles, 78 TF chip-wide) only while TWO of its waves are issuing MFMAs; a single issuing wave
-// gets one per 140 cycles (36 TF).  In vxc_kernel every wave alternates MFMA work with loads, the Psi combination
-// and LDS writes, so for part of every chunk fewer than two waves per SIMD feed the matrix pipe.  Here a block is
+// gets one per 140 cycles (36 TF).  A kernel whose waves all alternate MFMA work with loads, the Psi combination and LDS
+// writes leaves fewer than two waves per SIMD feeding the matrix pipe for part of every chunk.  Here a block is
 // 16 waves: waves 0-7 (two per SIMD) are CONSUMERS that do nothing but fragment reads + MFMAs; waves 8-15 (two per
 // SIMD) are PRODUCERS that fetch the next chunk's four AO components (buffer loads: no VALU address arithmetic), form
 // Psi and write the (Phi, Psi) chunk to the other LDS buffer.  An fp64 MFMA occupies the SIMD's vector ALU, so the
 // producers' VALU work cannot overlap the MFMAs: it runs in a window between two s_barriers per chunk during which the
-// consumers wait; the loads fly during the MFMA phase (see the comments in the kernel and DESIGN.md, section 3).  Tile
-// ownership, split-K over slabs, the XCD-aware block decode and the atomic epilogue are those of vxc_kernel.
+// consumers wait; the loads fly during the MFMA phase (see the comments in the kernel and DESIGN.md, section 3).
+//
+// Work split: the grid points are cut into slabs (split-K); the T x T output tiles (sym: the upper triangle) are cut into
+// `nsplit` runs of `tiles_per_split` consecutive tiles, one block per (slab, run), and a run is dealt evenly to the block's 8
+// consumer waves (ws_deal).  XCD-aware block decode: blocks are dispatched round-robin over the 8 XCDs, so the nsplit blocks
+// that share a slab get ids 8 apart -- same XCD, dispatched together, and the slab is fetched from HBM once.  Epilogue: every
+// wave adds its accumulator tiles to M with fp64 atomics (acc_add; fixed point in deterministic mode).
 // ---------------------------------------------------------------------------------------------
 #ifndef VWS_PROD_THREADS
 #define VWS_PROD_THREADS 512
@@ -215,7 +74,7 @@ __device__ long long g_vxc_trace[256 * 2 * (VXC_TRACE_MAXC + 2)];
 // offset:kk*VWS_GS*8  with one per-tile address register that does not change within a chunk: no VALU instruction at
 // all between the MFMAs.  (With the natural stride 4 * ld, a run-time value, every read needs a v_add first; those two
 // VALU instructions per MFMA cost 16 % of the MFMA rate -- tools/ubench/barrier_cost.hip: 60.6 vs 72.2 TF.)
-constexpr int VWS_LSMAX = 256;                    // ld <= 208 reaches this kernel (larger bases: vxc_ws2_kernel)
+constexpr int VWS_LSMAX = 256;                    // LS <= 256, i.e. ld <= 240 (T <= 15), reaches this layout (wider: vxc_ws2_kernel)
 constexpr int VWS_GS = 4 * VWS_LSMAX;             // doubles between k-groups
 constexpr int VWS_XS = (16 / 4) * VWS_GS;         // doubles between Phi and Psi (16-point chunks)
 constexpr int VWS_BUF = 2 * VWS_XS;               // doubles per buffer: 64 KB; two buffers = 128 KB of the 160 KB
@@ -330,7 +189,7 @@ __global__ __launch_bounds__(VWS_NT, VWS_NT / 256) void vxc_ws_kernel(double *__
                                                           int tiles_per_split, const double *__restrict__ aob, int sym, int lda, int LS) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     static_assert(KCH == 16, "the fixed-stride chunk layout is laid out for 16-point chunks");
-    constexpr int BUF = VWS_BUF;  // (lda / ld / LS: see vxc_kernel)
+    constexpr int BUF = VWS_BUF;  // (lda / ld / LS: see the head of the file)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const size_t cs = (size_t)ngrid * lda;
     const int id = blockIdx.x;
@@ -590,12 +449,14 @@ __global__ __launch_bounds__(VWS2_NT, 3) void vxc_ws2_kernel(double *__restrict_
 // Vxc, ONE block per slab (bases with 10 <= T <= 13 tile rows, i.e. 145 <= nao <= 208: the 20-atom cc-pVDZ molecules).
 // vxc_ws_kernel needs two blocks per slab there (T^2 = 169 tiles > 8 waves x 11), so every chunk travels L2 -> CU twice
 // and the chunk period is set by the producers' loads (2.7 us), not by the MFMAs (2.5 us).  Here the block owns the
-// UPPER-TRIANGULAR tiles only (T (T + 1) / 2 = 91 <= 8 x 12) and accumulates the symmetrised matrix directly:
-//     acc_ij = Phi_i^T Psi_j + Psi_i^T Phi_j = M_ij + (M_ji)^T = 2 V_ij         (two MFMAs per tile and k-group; GGA)
-//     acc_ij = Phi_i^T Psi_j                 = M_ij = V_ij                      (one operand, no gradient term: M symmetric)
-// -- 182 instead of 169 MFMAs per k-group (+8 %), but half the L2 -> CU traffic, half the producers (4 waves: one per
-// SIMD, 12 waves per block => 168 VGPRs per wave for the 12 accumulator tiles) and one combine window per 2 x the MFMA
-// work.  Chunk layout, buffer loads, the two-barrier combine window and the hand-pipelined fragment reads are those of
+// UPPER-TRIANGULAR tiles only (T (T + 1) / 2 = 91 <= 8 x 12) and accumulates the symmetrised matrix directly.  Two kernels
+// share the scheme, the producer (vwu_producer) and the block shape (8 consumer + 4 producer waves, one producer per SIMD):
+//     vxc_wsu_kernel (here):   one operand, no gradient term -- M is symmetric:   acc_ij = Phi_i^T Psi_j = M_ij = V_ij,
+//                              one MFMA per tile and k-group, T (T + 1) / 2 of them instead of T^2
+//     vxc_wsd_kernel (below):  GGA:   acc_ij = Phi_i^T Psi_j + Psi_i^T Phi_j = M_ij + (M_ji)^T = 2 V_ij  on the off-diagonal tiles
+//                              (its figures: the comment above that kernel)
+// Against two blocks per slab: half the L2 -> CU traffic, half the producers and one combine window per 2 x the MFMA work.
+// Chunk layout, buffer loads, the two-barrier combine window and the hand-pipelined fragment reads are those of
 // vxc_ws_kernel; the fragment of tile row i is  Phi: pi[t] + kk GS 8,  Psi: pi[t] + (XS + kk GS) 8  (immediates).
 // ---------------------------------------------------------------------------------------------
 constexpr int VWU_PROD = 256, VWU_NT = 512 + VWU_PROD;
@@ -609,45 +470,42 @@ __device__ long long g_vwu_trace[2 * VWU_TRACE_N];
 #define VWU_STAMP(role, slot)
 #endif
 
-template <int MAXT, int NTL, bool TWO, int D = 2, int KG0 = 0, int NKG = 4, int GS = VWS_GS, int XS = VWS_XS>
+template <int MAXT, int NTL, int D = 2>
 __device__ __forceinline__ void wsu_chunk(const unsigned (&pi)[MAXT], const unsigned (&pj)[MAXT], v4d (&acc)[MAXT]) {
-    // NTL <= MAXT: tiles actually looped over (waves that own one tile fewer skip the dummy MFMAs);
-    // k-groups KG0 .. KG0 + NKG - 1 of the 16-point chunk (the fused kernel runs a chunk in two halves)
-    constexpr int H = TWO ? 2 : 1, NS = NKG * NTL * H;
+    // NTL <= MAXT: tiles actually looped over (waves that own one tile fewer skip the dummy MFMAs); step s: k-group s / NTL of
+    // the 16-point chunk, tile s % NTL:  A = Phi_i, B = Psi_j
+    constexpr int NS = 4 * NTL;
     double fa[D + 1], fb[D + 1];
     auto rd = [&](int s) {
-        const int kk = KG0 + s / (NTL * H), t = (s % (NTL * H)) / H, h = s % H;
-        // h = 0: A = Phi_i, B = Psi_j;   h = 1: A = Psi_i, B = Phi_j
-        fa[s % (D + 1)] = *(lds_cdouble_t *)(pi[t] + (kk * GS + (h ? XS : 0)) * 8);
-        fb[s % (D + 1)] = *(lds_cdouble_t *)(pj[t] + (kk * GS + (h ? 0 : XS)) * 8);
+        fa[s % (D + 1)] = *(lds_cdouble_t *)(pi[s % NTL] + (s / NTL) * VWS_GS * 8);
+        fb[s % (D + 1)] = *(lds_cdouble_t *)(pj[s % NTL] + ((s / NTL) * VWS_GS + VWS_XS) * 8);
     };
 #pragma unroll
     for (int s = 0; s < D && s < NS; s++) rd(s);
 #pragma unroll
-    for (int s = 0; s < NS; s++) {  // tiles past the wave's count are clamped duplicates, discarded later
+    for (int s = 0; s < NS; s++) {
         if (s + D < NS) rd(s + D);
         __builtin_amdgcn_sched_barrier(0);
-        const int t = (s % (NTL * H)) / H;
-        acc[t] = mfma_f64(fa[s % (D + 1)], fb[s % (D + 1)], acc[t]);
+        acc[s % NTL] = mfma_f64(fa[s % (D + 1)], fb[s % (D + 1)], acc[s % NTL]);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
 
 // the same with a (wave-uniform) run-time tile count in [0, MAXT]: one straight-line body per count, no dummy MFMAs
-template <int MAXT, bool TWO, int N = MAXT>
+template <int MAXT, int N = MAXT>
 __device__ __forceinline__ void wsu_chunk_n(int nt, const unsigned (&pi)[MAXT], const unsigned (&pj)[MAXT], v4d (&acc)[MAXT]) {
     if constexpr (N == 0) return;
-    else if (nt == N) wsu_chunk<MAXT, N, TWO>(pi, pj, acc);
-    else wsu_chunk_n<MAXT, TWO, N - 1>(nt, pi, pj, acc);
+    else if (nt == N) wsu_chunk<MAXT, N>(pi, pj, acc);
+    else wsu_chunk_n<MAXT, N - 1>(nt, pi, pj, acc);
 }
 
-// the 4 producer waves of vxc_wsu_kernel / vxc_wsb_kernel (threads 512 .. 767): chunk c + 2 travels HBM -> registers while the
+// the 4 producer waves of vxc_wsu_kernel / vxc_wsd_kernel (threads 512 .. 767): chunk c + 2 travels HBM -> registers while the
 // consumers run the MFMAs of chunk c; chunk c + 1 is combined into (Phi, Psi) and written to LDS in the window between chunks
 template <int NLP, bool GGA>
 DQC_DEV void vwu_producer(double *lds, const double *__restrict__ ao, int ngrid, int ld, const double *__restrict__ w,
                           const double *__restrict__ vrho, const double *__restrict__ vgrad, int gs, int ge, int nchunk,
                           int lda, int LS) {
-    // lda: row stride of the AO arrays in HBM; ld = 16 T: staged width; LS: LDS row stride (see vxc_kernel)
+    // lda: row stride of the AO arrays in HBM; ld = 16 T: staged width; LS: LDS row stride (see the head of the file)
     constexpr int KCH = 16;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     (void)wave; (void)lane;
@@ -744,10 +602,11 @@ DQC_DEV void vwu_producer(double *lds, const double *__restrict__ ao, int ngrid,
 #endif
 }
 
-template <int MAXT, int NLP, bool GGA>
+template <int MAXT, int NLP>
 __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsu_kernel(double *__restrict__ vmat, const double *__restrict__ ao, int ngrid,
                                                            int ld, const double *__restrict__ w, const double *__restrict__ vrho,
                                                            const double *__restrict__ vgrad, int slab, int lda, int LS) {
+    // (vgrad: not read -- no gradient term in this form; the launcher passes it through for a uniform argument list)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     constexpr int KCH = 16;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -756,7 +615,7 @@ __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsu_kernel(double *__restrict__
     const int nchunk = (ge - gs + KCH - 1) / KCH;
 
     if (wave >= VXC_WAVES) {
-        vwu_producer<NLP, GGA>(lds, ao, ngrid, ld, w, vrho, vgrad, gs, ge, nchunk, lda, LS);
+        vwu_producer<NLP, false>(lds, ao, ngrid, ld, w, vrho, vgrad, gs, ge, nchunk, lda, LS);
         return;
     }
 
@@ -796,7 +655,7 @@ __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsu_kernel(double *__restrict__
         VWU_STAMP(0, 4 * c + 1);
 #endif
 #ifndef VWU_EXP_NOMFMA
-        wsu_chunk_n<MAXT, GGA>(nt, pi, pj, acc);
+        wsu_chunk_n<MAXT>(nt, pi, pj, acc);
 #endif
         const unsigned delta = (c & 1) ? (unsigned)(-VWS_BUF * 8) : (unsigned)(VWS_BUF * 8);
 #pragma unroll
@@ -809,9 +668,8 @@ __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsu_kernel(double *__restrict__
             tile_ij(t0 + t, ti, tj);
             const int ia = ti * 16 + lk, ib = tj * 16 + lr;
             // symmetrize_kernel forms (m_ij + m_ji) / 2 over the whole matrix and the lower tiles stay zero:
-            //   GGA: acc = 2 V -> off-diagonal tiles store acc (-> acc / 2 = V), diagonal tiles acc / 2 (already symmetric)
-            //   one operand: acc = V -> off-diagonal tiles 2 acc, diagonal tiles acc
-            const double sc = (GGA ? 1.0 : 2.0) * (ti != tj ? 1.0 : 0.5);
+            // acc = V -> off-diagonal tiles store 2 acc, diagonal tiles acc
+            const double sc = ti != tj ? 2.0 : 1.0;
 #ifdef VWU_EXP_NOEPI
             if (acc[t][0] != 1.2345e300) continue;
 #endif
@@ -822,15 +680,17 @@ __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsu_kernel(double *__restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// Vxc, one block per slab, GGA, T = 11 or 13 tile rows: vxc_wsu_kernel with ONE MFMA on the diagonal tiles.
-// vxc_wsu_kernel is 90 % MFMA-busy in cycles, but the chip sits at its power limit there (tools/gpu_vxc_trace.py: the shader
-// clock is 1.96 GHz with the MFMAs and the HBM stream both running, 2.35 GHz with the MFMAs alone, 2.41 GHz with the stream
-// alone), so what is left is the number of MFMAs.  A diagonal tile needs only M_ii = Phi_i^T Psi_i: symmetrize_kernel forms
-// (M_ii + M_ii^T) / 2 = V_ii anyway.  T^2 = 169 MFMAs per k-group instead of T (T + 1) = 182 (-7 %).  Every wave owns NO
-// off-diagonal tiles (two MFMAs each) followed by ND diagonal tiles (one each); the deal is fixed at compile time so that the
-// SIMDs (waves w and w + 4) carry 42, 42, 42, 43 MFMAs per k-group for T = 13 and no wave more than 12 accumulator tiles.
-// Measured (C5 shape, random data): 0.691 ms against 0.725 ms.  Not pursued: sharing fragment reads between the tiles of a
-// row -- a build that issues a quarter of the ds_read_b64 (wrong results, timing only) is just 3-5 % faster.
+// Vxc, one block per slab, GGA, 10 <= T <= 13 tile rows: the upper-triangular scheme with two MFMAs on the off-diagonal tiles
+// and ONE on the diagonal tiles.  With two on every tile the kernel is 90 % MFMA-busy in cycles, but the chip sits at its
+// power limit there (tools/gpu_vxc_trace.py: the shader clock is 1.96 GHz with the MFMAs and the HBM stream both running,
+// 2.35 GHz with the MFMAs alone, 2.41 GHz with the stream alone), so what is left is the number of MFMAs.  A diagonal tile
+// needs only M_ii = Phi_i^T Psi_i: symmetrize_kernel forms (M_ii + M_ii^T) / 2 = V_ii anyway.  T^2 = 169 MFMAs per k-group
+// instead of T (T + 1) = 182 (-7 %) -- as many as the two-block vxc_ws_kernel form issues.  12 waves per block => 168 VGPRs
+// per wave for the 12 accumulator tiles.  Every wave owns NO off-diagonal tiles (two MFMAs each) followed by ND diagonal
+// tiles (one each); the deal is fixed at compile time so that the SIMDs (waves w and w + 4) carry 42, 42, 42, 43 MFMAs per
+// k-group for T = 13 and no wave more than 12 accumulator tiles.  Measured (C5 shape, random data): 0.691 ms against 0.725 ms.
+// Not pursued: sharing fragment reads between the tiles of a row -- a build that issues a quarter of the ds_read_b64 (wrong
+// results, timing only) is just 3-5 % faster.
 // ---------------------------------------------------------------------------------------------
 constexpr int wsd_ls(int T) { return ((16 * T) & 31) == 16 ? 16 * T : 16 * T + 16; }
 
@@ -987,16 +847,6 @@ static int sync_vxc_det_scale() {
     return 0;
 }
 
-template <int MAXT, int NL, int KCH, bool GGA>
-static void launch_vxc_inst(dim3 grid, size_t shmem, hipStream_t st, double *vmat, const double *ao, int ngrid, int ld,
-                            const double *w, const double *vrho, const double *vgrad, int slab, int nsplit, int tps,
-                            const double *aob, int lda, int LS) {
-    (void)hipFuncSetAttribute((const void *)vxc_kernel<MAXT, NL, KCH, GGA>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shmem);
-    hipLaunchKernelGGL((vxc_kernel<MAXT, NL, KCH, GGA>), grid, dim3(512), shmem, st, vmat, ao, ngrid, ld, w, vrho, vgrad, slab,
-                       nsplit, tps, aob, lda, LS);
-}
-
 template <int MAXT, int NLP, int KCH, bool GGA>
 static void launch_vxc_ws_inst(dim3 grid, size_t shmem, hipStream_t st, double *vmat, const double *ao, int ngrid, int ld,
                                const double *w, const double *vrho, const double *vgrad, int slab, int nsplit, int tps,
@@ -1007,11 +857,11 @@ static void launch_vxc_ws_inst(dim3 grid, size_t shmem, hipStream_t st, double *
 }
 
 template <bool GGA>
-static int launch_vxc_ws(int maxt, int nlp, int kch, dim3 grid, size_t shmem, hipStream_t st, double *vmat,
+static int launch_vxc_ws(int maxt, int nlp, dim3 grid, size_t shmem, hipStream_t st, double *vmat,
                          const double *ao, int ngrid, int ld, const double *w, const double *vrho, const double *vgrad,
                          int slab, int nsplit, int tps, const double *aob, int sym, int lda, int LS) {
 #define DQC_VWS_CASE(N, L)                                                                                          \
-    if (maxt == N && nlp == L && kch == 16) {                                                                       \
+    if (maxt == N && nlp == L) {                                                                                    \
         launch_vxc_ws_inst<N, L, 16, GGA>(grid, shmem, st, vmat, ao, ngrid, ld, w, vrho, vgrad, slab, nsplit, tps, aob, sym, lda, LS); \
         return 0;                                                                                                   \
     }
@@ -1023,10 +873,10 @@ static int launch_vxc_ws(int maxt, int nlp, int kch, dim3 grid, size_t shmem, hi
     return DQC_EINVAL;
 }
 
-template <int MAXT, int NLP, bool GGA>
-static void launch_vxc_wsu_inst(dim3 grid, size_t shmem, hipStream_t st, double *vmat, const double *ao, int ngrid, int ld,
+template <int MAXT>
+static void launch_vxc_wsu(dim3 grid, size_t shmem, hipStream_t st, double *vmat, const double *ao, int ngrid, int ld,
                                 const double *w, const double *vrho, const double *vgrad, int slab, int lda, int LS) {
-    auto kern = vxc_wsu_kernel<MAXT, NLP, GGA>;
+    auto kern = vxc_wsu_kernel<MAXT, 7>;
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     hipLaunchKernelGGL(kern, grid, dim3(VWU_NT), shmem, st, vmat, ao, ngrid, ld, w, vrho, vgrad, slab, lda, LS);
 }
@@ -1037,14 +887,6 @@ static void launch_vxc_wsd(dim3 grid, size_t shmem, hipStream_t st, double *vmat
     auto kern = vxc_wsd_kernel<T, 7>;
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     hipLaunchKernelGGL(kern, grid, dim3(VWU_NT), shmem, st, vmat, ao, ngrid, w, vrho, vgrad, slab, lda);
-}
-
-template <bool GGA>
-static int launch_vxc_wsu(int maxt, dim3 grid, size_t shmem, hipStream_t st, double *vmat, const double *ao, int ngrid, int ld,
-                          const double *w, const double *vrho, const double *vgrad, int slab, int lda, int LS) {
-    if (maxt <= 9) launch_vxc_wsu_inst<9, 7, GGA>(grid, shmem, st, vmat, ao, ngrid, ld, w, vrho, vgrad, slab, lda, LS);
-    else launch_vxc_wsu_inst<12, 7, GGA>(grid, shmem, st, vmat, ao, ngrid, ld, w, vrho, vgrad, slab, lda, LS);
-    return 0;
 }
 
 template <int MAXT, int NLA, int NLB, bool GGA>
@@ -1072,27 +914,6 @@ static int launch_vxc_ws2(int maxt, int nla, int nlb, dim3 grid, size_t shmem, h
     return DQC_EINVAL;
 }
 
-template <bool GGA>
-static int launch_vxc(int maxt, int nl, int kch, dim3 grid, size_t shmem, hipStream_t st, double *vmat, const double *ao,
-                      int ngrid, int ld, const double *w, const double *vrho, const double *vgrad, int slab, int nsplit,
-                      int tps, const double *aob, int lda, int LS) {
-#define DQC_VXC_CASE(N, L)                                                                                        \
-    if (maxt == N && nl == L && kch == 16) {                                                                      \
-        launch_vxc_inst<N, L, 16, GGA>(grid, shmem, st, vmat, ao, ngrid, ld, w, vrho, vgrad, slab, nsplit, tps, aob, lda, LS);  \
-        return 0;                                                                                                 \
-    }                                                                                                             \
-    if (maxt == N && nl == L && kch == 8) {                                                                       \
-        launch_vxc_inst<N, L, 8, GGA>(grid, shmem, st, vmat, ao, ngrid, ld, w, vrho, vgrad, slab, nsplit, tps, aob, lda, LS);   \
-        return 0;                                                                                                 \
-    }
-    DQC_VXC_CASE(2, 1) DQC_VXC_CASE(4, 1) DQC_VXC_CASE(8, 1) DQC_VXC_CASE(11, 1)
-    DQC_VXC_CASE(2, 2) DQC_VXC_CASE(4, 2) DQC_VXC_CASE(8, 2) DQC_VXC_CASE(11, 2)
-    DQC_VXC_CASE(2, 4) DQC_VXC_CASE(4, 4) DQC_VXC_CASE(8, 4) DQC_VXC_CASE(11, 4)
-#undef DQC_VXC_CASE  // (this kernel only sees ld <= 256: wider bases take vxc_ws2_kernel)
-    set_error("vxc: internal dispatch error");
-    return DQC_EINVAL;
-}
-
 }  // namespace dqc
 
 extern "C" {
@@ -1105,134 +926,105 @@ static int grid_vxc_impl(double *d_vmat, const double *d_ao, const double *d_aob
     hipStream_t st = (hipStream_t)stream;
     const bool gga = d_vgrad != nullptr;
     if (gga && ncomp < 4) { set_error("dqc_grid_vxc: vgrad given but ao has < 4 components"); return DQC_EINVAL; }
-    // ld = 16 T: rows / columns of the output matrix and the width the kernels stage; lda: row stride of the AO arrays;
-    // LS: LDS row stride of a staged chunk, == 16 (mod 32) so that the ds_read_b64 fragment reads are conflict-free
-    const int ld = dqc_padded_nao(nao), lda = dqc_ao_stride(nao), T = ld / 16, ttot = T * T;
+    // ld, lda, LS: see the head of the file
+    const int ld = dqc_padded_nao(nao), lda = dqc_ao_stride(nao), T = ld / 16;
     auto pad16 = [](int w_) { return (w_ & 31) == 16 ? w_ : w_ + 16; };
     const int LS = pad16(ld);
     if (sync_vxc_det_scale()) return DQC_EHIP;
     DQC_HIP(hipMemsetAsync(d_vmat, 0, sizeof(double) * (size_t)ld * ld, st));
-    if (ngrid > 0) {
-        static const char *impl_env = getenv("DQC_VXC_IMPL");  // "reg": the unspecialised vxc_kernel (A/B runs)
-        // one-operand forms without a gradient term (LDA Vxc, the tau terms of a meta-GGA) are symmetric matrices: the
-        // wave-specialised kernel then computes the upper-triangular tiles only
-        const bool ws_shape = LS <= VWS_LSMAX && !(impl_env && impl_env[0] == 'r');
-        const bool sym = ws_shape && !gga && d_aob == d_ao;
-        const int ttot_w = sym ? T * (T + 1) / 2 : ttot;
-        if (ttot_w > 2 * 11 * VXC_WAVES && !(impl_env && impl_env[0] == 'r')) {
-            // larger bases: rectangular ownership (vxc_ws2_kernel), rectangles of at most 9 x 12 tiles
-            // rectangle shape: a block stages nr Phi tile columns (one component) and 4 nc AO-component tile columns for its
-            // nr x nc tiles -- (nr + 4 nc) / (nr nc) operand tile columns per MFMA: rows are cheap, columns dear.  The tallest
-            // rectangle the layout allows (9 rows: LSA <= 144), then the widest that keeps <= 11 accumulator tiles per wave:
-            // T = 26 (naphthalene / cc-pVTZ): 9 x 9 tiles, 9 blocks per slab (round 2: 7 x 9, 12 blocks); T = 17: 9 x 9 (6 x 9).
-            // DQC_WS2_NR / DQC_WS2_NC override the block counts (A/B runs).
-            int NR = (T + 8) / 9, NC = 1;
-            {
-                const int nrm = (T + NR - 1) / NR;
-                while ((T + NC - 1) / NC > 12 || nrm * ((T + NC - 1) / NC) > 11 * VXC_WAVES) NC++;
-                const char *e1 = getenv("DQC_WS2_NR"), *e2 = getenv("DQC_WS2_NC");
-                if (e1 && atoi(e1) > 0) NR = atoi(e1);
-                if (e2 && atoi(e2) > 0) NC = atoi(e2);
-            }
-            const int nrmax = (T + NR - 1) / NR, ncmax = (T + NC - 1) / NC;
-            if (nrmax > 9 || ncmax > 12 || nrmax * ncmax > 11 * VXC_WAVES) { set_error("vxc_ws2: rectangle outside the kernel's limits"); return DQC_EINVAL; }
-            const int need2 = (nrmax * ncmax + VXC_WAVES - 1) / VXC_WAVES;
-            const int maxt2 = need2 <= 8 ? 8 : 11;
-            const int LSA = pad16(nrmax * 16), LSB = pad16(ncmax * 16);
-            const int nla = nrmax <= 8 ? 4 : 5, nlb = (ncmax * 8 + 15) / 16 <= 4 ? 4 : 6;  // b128 loads per producer thread and row
-            const int nsplit2 = NR * NC;
-            // two blocks per CU: the nine (NR x NC) blocks of a slab start together and stay in step (see the consumers), so the slab
-            // is fetched from HBM about once; many small blocks (DQC_VXC_BLOCKS=3072: ~12 per CU) even out the tail but start
-            // at different times -- same launch time, FETCH_SIZE x 2 (profiles/r04q_c4_blocks.txt)
-            static const int target_blocks2 = [] { const char *e = getenv("DQC_VXC_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();
-            int nslab = std::max(8, std::min(target_blocks2 / nsplit2, std::max(ngrid / 1024, 512 / nsplit2)) / 8 * 8);
-            int slab = (ngrid + nslab - 1) / nslab;
-            slab = (slab + 15) / 16 * 16;
-            nslab = ((ngrid + slab - 1) / slab + 7) / 8 * 8;
-            const size_t shmem2 = sizeof(double) * 2 * WS2_BUF;  // fixed-stride chunk layout, two buffers
-            if (LSA > 144 || LSB > 208) { set_error("vxc_ws2: internal layout error"); return DQC_EINVAL; }
-            dim3 grid2(nslab * nsplit2);
-            int rc = gga ? launch_vxc_ws2<true>(maxt2, nla, nlb, grid2, shmem2, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, NR, NC, LSA, LSB, d_aob, lda)
-                         : launch_vxc_ws2<false>(maxt2, nla, nlb, grid2, shmem2, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, NR, NC, LSA, LSB, d_aob, lda);
-            if (rc) return rc;
-            DQC_CHECK_LAUNCH();
-            if (!raw) hipLaunchKernelGGL(symmetrize_kernel, dim3((ld + 15) / 16, (ld + 15) / 16), dim3(16, 16), 0, st, d_vmat, ld, nao);
-            DQC_CHECK_LAUNCH();
-            return DQC_OK;
+    if (ngrid <= 0) return DQC_OK;
+    // ws_shape: a whole staged row fits the fixed-stride chunk layout of vxc_ws / vxc_wsu / vxc_wsd (T <= 15)
+    const bool ws_shape = LS <= VWS_LSMAX, one_operand = d_aob == d_ao;
+    // one-operand forms without a gradient term (LDA Vxc, the tau terms of a meta-GGA) are symmetric matrices: vxc_ws_kernel
+    // then computes the upper-triangular tiles only
+    const bool sym = ws_shape && !gga && one_operand;
+    const int ttot = sym ? T * (T + 1) / 2 : T * T;  // tiles to compute
+    auto slabs = [&](int nslab, int mult, int &slab) {  // `nslab` slabs of a multiple of 16 points; -> slab count, a multiple of `mult`
+        slab = (ngrid + nslab - 1) / nslab;
+        slab = (slab + 15) / 16 * 16;
+        return ((ngrid + slab - 1) / slab + mult - 1) / mult * mult;
+    };
+    int rc = 0, slab = 0;
+    if (ttot > 2 * 11 * VXC_WAVES) {
+        // ---- vxc_ws2_kernel (larger bases): rectangular ownership, rectangles of at most 9 x 12 tiles.
+        // Rectangle shape: a block stages nr Phi tile columns (one component) and 4 nc AO-component tile columns for its
+        // nr x nc tiles -- (nr + 4 nc) / (nr nc) operand tile columns per MFMA: rows are cheap, columns dear.  The tallest
+        // rectangle the layout allows (9 rows: LSA <= 144), then the widest that keeps <= 11 accumulator tiles per wave:
+        // T = 26 (naphthalene / cc-pVTZ): 9 x 9 tiles, 9 blocks per slab (round 2: 7 x 9, 12 blocks); T = 17: 9 x 9 (6 x 9).
+        // DQC_WS2_NR / DQC_WS2_NC override the block counts (A/B runs).
+        int NR = (T + 8) / 9, NC = 1;
+        {
+            const int nrm = (T + NR - 1) / NR;
+            while ((T + NC - 1) / NC > 12 || nrm * ((T + NC - 1) / NC) > 11 * VXC_WAVES) NC++;
+            const char *e1 = getenv("DQC_WS2_NR"), *e2 = getenv("DQC_WS2_NC");
+            if (e1 && atoi(e1) > 0) NR = atoi(e1);
+            if (e2 && atoi(e2) > 0) NC = atoi(e2);
         }
-        // 145 <= nao <= 208 (10 <= T <= 13): one block per slab over the upper-triangular tiles (vxc_wsu_kernel) instead of two
-        // blocks that each stage the whole slab.  One operand, symmetric result; DQC_VXC_IMPL=split keeps the two-block form.
-        if (ws_shape && T >= 10 && T * (T + 1) / 2 <= 12 * VXC_WAVES && d_aob == d_ao && !(impl_env && impl_env[0] == 's')) {
-            int ncu = stream_cus(st);  // one block per CU of the stream's partition (all 256 on an ordinary stream)
-            if (vxc_cus_cap() > 0) ncu = std::max(8, std::min(ncu, vxc_cus_cap()));  // (leave CUs to other streams' kernels: host.hip)
-            int nslab = ncu;
-            int slab = (ngrid + nslab - 1) / nslab;
-            slab = (slab + 15) / 16 * 16;
-            nslab = (ngrid + slab - 1) / slab;
-            const int need = (T * (T + 1) / 2 + VXC_WAVES - 1) / VXC_WAVES;
-            const size_t shmem_u = sizeof(double) * 2 * VWS_BUF;
-            int rc = 0;
-            // GGA: one MFMA on the diagonal tiles (vxc_wsd_kernel); DQC_VXC_IMPL=upper keeps two on every tile (A/B runs)
-            if (gga && !(impl_env && impl_env[0] == 'u')) {
-                if (T == 13) launch_vxc_wsd<13>(dim3(nslab), shmem_u, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
-                else if (T == 12) launch_vxc_wsd<12>(dim3(nslab), shmem_u, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
-                else if (T == 11) launch_vxc_wsd<11>(dim3(nslab), shmem_u, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
-                else launch_vxc_wsd<10>(dim3(nslab), shmem_u, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
-            } else {
-                rc = gga ? launch_vxc_wsu<true>(need, dim3(nslab), shmem_u, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, lda, LS)
-                         : launch_vxc_wsu<false>(need, dim3(nslab), shmem_u, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, lda, LS);
-            }
-            if (rc) return rc;
-            DQC_CHECK_LAUNCH();
-            if (!raw) hipLaunchKernelGGL(symmetrize_kernel, dim3((ld + 15) / 16, (ld + 15) / 16), dim3(16, 16), 0, st, d_vmat, ld, nao);
-            DQC_CHECK_LAUNCH();
-            return DQC_OK;
+        const int nrmax = (T + NR - 1) / NR, ncmax = (T + NC - 1) / NC;
+        if (nrmax > 9 || ncmax > 12 || nrmax * ncmax > 11 * VXC_WAVES) { set_error("vxc_ws2: rectangle outside the kernel's limits"); return DQC_EINVAL; }
+        const int need = (nrmax * ncmax + VXC_WAVES - 1) / VXC_WAVES;
+        const int maxt = need <= 8 ? 8 : 11;
+        const int LSA = pad16(nrmax * 16), LSB = pad16(ncmax * 16);
+        if (LSA > 144 || LSB > 208) { set_error("vxc_ws2: internal layout error"); return DQC_EINVAL; }
+        const int nla = nrmax <= 8 ? 4 : 5, nlb = (ncmax * 8 + 15) / 16 <= 4 ? 4 : 6;  // b128 loads per producer thread and row
+        const int nsplit = NR * NC;
+        // two blocks per CU: the nine (NR x NC) blocks of a slab start together and stay in step (see the consumers), so the slab
+        // is fetched from HBM about once; many small blocks (DQC_VXC_BLOCKS=3072: ~12 per CU) even out the tail but start
+        // at different times -- same launch time, FETCH_SIZE x 2 (profiles/r04q_c4_blocks.txt)
+        static const int target_blocks = [] { const char *e = getenv("DQC_VXC_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();
+        // slabs in multiples of 8 so that the XCD-aware decode is exact
+        const int nslab = slabs(std::max(8, std::min(target_blocks / nsplit, std::max(ngrid / 1024, 512 / nsplit)) / 8 * 8), 8, slab);
+        const size_t shmem = sizeof(double) * 2 * WS2_BUF;  // fixed-stride chunk layout, two buffers
+        const dim3 grid(nslab * nsplit);
+        rc = gga ? launch_vxc_ws2<true>(maxt, nla, nlb, grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, NR, NC, LSA, LSB, d_aob, lda)
+                 : launch_vxc_ws2<false>(maxt, nla, nlb, grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, NR, NC, LSA, LSB, d_aob, lda);
+    } else if (ws_shape && T >= 10 && T * (T + 1) / 2 <= 12 * VXC_WAVES && one_operand) {
+        // ---- vxc_wsu_kernel / vxc_wsd_kernel: 145 <= nao <= 208 (10 <= T <= 13), one operand: one block per slab over the
+        // upper-triangular tiles instead of two blocks that each stage the whole slab
+        int ncu = stream_cus(st);  // one block per CU of the stream's partition (all 256 on an ordinary stream)
+        if (vxc_cus_cap() > 0) ncu = std::max(8, std::min(ncu, vxc_cus_cap()));  // (leave CUs to other streams' kernels: host.hip)
+        const dim3 grid(slabs(ncu, 1, slab));
+        const size_t shmem = sizeof(double) * 2 * VWS_BUF;
+        if (gga) {  // one MFMA on the diagonal tiles, two on the others
+            if (T == 13) launch_vxc_wsd<13>(grid, shmem, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
+            else if (T == 12) launch_vxc_wsd<12>(grid, shmem, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
+            else if (T == 11) launch_vxc_wsd<11>(grid, shmem, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
+            else launch_vxc_wsd<10>(grid, shmem, st, d_vmat, d_ao, ngrid, d_w, d_vrho, d_vgrad, slab, lda);
+        } else if ((T * (T + 1) / 2 + VXC_WAVES - 1) / VXC_WAVES <= 9) {  // accumulator tiles per wave
+            launch_vxc_wsu<9>(grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, lda, LS);
+        } else {
+            launch_vxc_wsu<12>(grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, lda, LS);
         }
-        // tiles per block are capped at 11 per wave so that accumulators + prefetch registers fit 256 VGPRs
-        static const int sizes_ws[] = {2, 4, 6, 8, 11}, sizes_reg[] = {2, 4, 8, 11, 11};
-        const int *sizes_p = ws_shape ? sizes_ws : sizes_reg;
+    } else if (ws_shape) {
+        // ---- vxc_ws_kernel (8 MFMA waves + 8 producer waves): the tiles are split linearly over 1 or 2 blocks per slab; tiles
+        // per block are capped at 11 per wave so that accumulators + prefetch registers fit 256 VGPRs
+        static const int sizes_ws[] = {2, 4, 6, 8, 11};
         const int cap = 11 * VXC_WAVES;
-        const int nsplit = (ttot_w + cap - 1) / cap;
-        const int tps = (ttot_w + nsplit - 1) / nsplit;
+        const int nsplit = (ttot + cap - 1) / cap;
+        const int tps = (ttot + nsplit - 1) / nsplit;
         const int need = (tps + VXC_WAVES - 1) / VXC_WAVES;
         int maxt = 11;
         for (int q = 0; q < 5; q++)
-            if (sizes_p[q] >= need) { maxt = sizes_p[q]; break; }
-        // chunk depth: 16 points while the double-buffered (phi, psi) chunk fits LDS, else 8
-        const int kch = (sizeof(double) * 2 * 2 * 16 * (size_t)LS <= 150 * 1024) ? 16 : 8;
-        const int tpr = 512 / kch;  // threads per chunk row
-        const int nlneed = (ld / 2 + tpr - 1) / tpr;  // double2 columns per thread
-        const int nl = nlneed <= 1 ? 1 : (nlneed <= 2 ? 2 : (nlneed <= 4 ? 4 : 8));
-        if (nlneed > 8) { set_error("dqc_grid_vxc: nao above 1008 is not supported by this build"); return DQC_EINVAL; }
-        // one 8-wave block per CU; slabs in multiples of 8 so that the XCD-aware decode is exact
-        int nslab = std::max(8, (stream_cus(st) / nsplit) / 8 * 8);
-        int slab = (ngrid + nslab - 1) / nslab;
-        slab = (slab + kch - 1) / kch * kch;
-        nslab = ((ngrid + slab - 1) / slab + 7) / 8 * 8;
-        const size_t shmem = sizeof(double) * 2 * 2 * kch * LS;
-        dim3 grid(nslab * nsplit);
-        // default: wave-specialised kernel (8 MFMA waves + 8 producer waves); the producers hold a whole chunk in
-        // registers, which bounds ld; DQC_VXC_IMPL=reg selects the unspecialised kernel
-        const int tprp = VWS_PROD / kch;
+            if (sizes_ws[q] >= need) { maxt = sizes_ws[q]; break; }
+        // the producers hold a whole chunk in registers: b128 pieces per thread and row (ws_shape: ld <= 240, at most 4)
+        const int tprp = VWS_PROD / 16;
         const int nlpneed = (ld / 2 + tprp - 1) / tprp;
-        const int nlp = nlpneed <= 1 ? 1 : (nlpneed <= 2 ? 2 : (nlpneed <= 4 ? 4 : (nlpneed <= 7 ? 7 : 8)));
-        if (nlpneed <= 4 && kch == 16 && ws_shape) {
-            const size_t shmem_ws = sizeof(double) * 2 * VWS_BUF;  // fixed-stride chunk layout, two buffers
-            int rc = gga ? launch_vxc_ws<true>(maxt, nlp, kch, grid, shmem_ws, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, nsplit, tps, d_aob, 0, lda, LS)
-                         : launch_vxc_ws<false>(maxt, nlp, kch, grid, shmem_ws, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, nsplit, tps, d_aob, sym ? 1 : 0, lda, LS);
-            if (rc) return rc;
-            DQC_CHECK_LAUNCH();
-            if (!raw) hipLaunchKernelGGL(symmetrize_kernel, dim3((ld + 15) / 16, (ld + 15) / 16), dim3(16, 16), 0, st, d_vmat, ld, nao);
-            DQC_CHECK_LAUNCH();
-            return DQC_OK;
-        }
-        int rc = gga ? launch_vxc<true>(maxt, nl, kch, grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, nsplit, tps, d_aob, lda, LS)
-                     : launch_vxc<false>(maxt, nl, kch, grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, nsplit, tps, d_aob, lda, LS);
-        if (rc) return rc;
-        DQC_CHECK_LAUNCH();
-        if (!raw) hipLaunchKernelGGL(symmetrize_kernel, dim3((ld + 15) / 16, (ld + 15) / 16), dim3(16, 16), 0, st, d_vmat, ld, nao);
-        DQC_CHECK_LAUNCH();
+        const int nlp = nlpneed <= 1 ? 1 : (nlpneed <= 2 ? 2 : 4);
+        // one block per CU; slabs in multiples of 8 so that the XCD-aware decode is exact
+        const int nslab = slabs(std::max(8, (stream_cus(st) / nsplit) / 8 * 8), 8, slab);
+        const size_t shmem = sizeof(double) * 2 * VWS_BUF;  // fixed-stride chunk layout, two buffers
+        const dim3 grid(nslab * nsplit);
+        rc = gga ? launch_vxc_ws<true>(maxt, nlp, grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, nsplit, tps, d_aob, 0, lda, LS)
+                 : launch_vxc_ws<false>(maxt, nlp, grid, shmem, st, d_vmat, d_ao, ngrid, ld, d_w, d_vrho, d_vgrad, slab, nsplit, tps, d_aob, sym ? 1 : 0, lda, LS);
+    } else {
+        // (not reached: without ws_shape T >= 16 and ttot = T^2 takes the first branch)
+        set_error("dqc_grid_vxc: internal dispatch error (no kernel family for this shape)");
+        return DQC_EINVAL;
     }
+    if (rc) return rc;
+    DQC_CHECK_LAUNCH();
+    if (!raw) hipLaunchKernelGGL(symmetrize_kernel, dim3((ld + 15) / 16, (ld + 15) / 16), dim3(16, 16), 0, st, d_vmat, ld, nao);
+    DQC_CHECK_LAUNCH();
     return DQC_OK;
 }
 

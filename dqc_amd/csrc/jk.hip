@@ -11,10 +11,12 @@
 //   Kacc[I,K] +=  f g.D[J,L]       Kacc[J,K] +=  f g.D[I,L]
 // and finally J = Jacc + Jacc^T, K = Kacc + Kacc^T (the 8 index permutations of every unique integral).
 //
-// Mapping: one 256-thread workgroup per tile, viewed as a 64x64 matrix M[(ij)][(kl)]; thread t owns the
-// 4x4 patch rows 4(t/16).., cols 4(t%16).. (16-byte loads, 512-byte rows per 16 lanes).  J needs row sums
-// (16-lane DPP reduce) and column sums (2 shuffles + a 4-wave LDS combine).  For K the patch is parked in
-// LDS (row stride 65) and the four contractions re-read it with output-major lane mappings.
+// Mapping: a 256-thread workgroup streams a CONTIGUOUS range of tiles (j_stream_kernel, jk_stream_kernel,
+// jk_multi_stream_kernel; more than one Coulomb density: the grid-stride jk_multi_kernel).  A tile is viewed as a 64x64
+// matrix M[(ij)][(kl)]; thread t owns the 4x4 patch rows 4(t/16).., cols 4(t%16).. (16-byte loads, 512-byte rows per
+// 16 lanes).  J needs row sums (kept in registers while the bra pair IJ lasts, then a 16-lane reduce) and column sums
+// (2 shuffles + a 4-wave LDS combine per tile).  For K the patch is parked in LDS (row stride 68) and the four
+// contractions re-read it with output-major lane mappings (bank analysis: jk_stream_kernel).
 #include <cstdlib>
 
 #include "common.hpp"
@@ -142,134 +144,6 @@ __global__ __launch_bounds__(256) void jk_det_scale_kernel(double *__restrict__ 
     }
 }
 
-template <bool WITH_K>
-__global__ __launch_bounds__(256, WITH_K ? 4 : 1) void jk_tiles_kernel(const double *__restrict__ dscp, const double *__restrict__ tiles,
-                                                       double *__restrict__ work, int npad, long long ntiles, int nao) {
-    const TileLay ly(nao);
-    const double dsc = dscp ? *dscp : 0.0;  // deterministic mode: fixed-point scale of the accumulators (common.hpp: acc_add)
-    constexpr int LDT = 68;  // row stride of the tile parked in LDS: 16-byte aligned rows, bank = 4 row + col (mod 32)
-    __shared__ double s_col[4][64];
-    __shared__ __attribute__((aligned(16))) double s_g[WITH_K ? 64 * LDT : 2];
-    // D[J,K], D[I,K] | D[J,L], D[I,L]; element (a, v) of a block at a * 9 + v, the two blocks of a pair interleaved so that
-    // one ds_read_b128 fetches both (the exchange part is LDS-read-bound)
-    __shared__ __attribute__((aligned(16))) double s_d[WITH_K ? 2 : 1][72][2];
-    const size_t n2 = (size_t)npad * npad;
-    const double *Dp = work;
-    double *Jacc = work + n2, *Kacc = work + 2 * n2;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r0 = 4 * (t >> 4), c0 = 4 * (t & 15);
-
-    for (long long T = blockIdx.x; T < ntiles; T += gridDim.x) {
-        int IJ, KL, I, J, K, L;
-        decode_tri(T, IJ, KL);
-        decode_tri(IJ, I, J);
-        decode_tri(KL, K, L);
-        const double f = (I == J ? 0.5 : 1.0) * (K == L ? 0.5 : 1.0) * (IJ == KL ? 0.5 : 1.0);
-        // D[K,L](k,l) for the 4 columns, D[I,J](i,j) for the 4 rows of this thread's patch
-        const int kk = c0 >> 3, l0 = c0 & 7, ii = r0 >> 3, j0 = r0 & 7;
-        const double *dklp = Dp + (size_t)(K * 8 + kk) * npad + L * 8 + l0;
-        const double *dijp = Dp + (size_t)(I * 8 + ii) * npad + J * 8 + j0;
-        double dkl[4], dij[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) { dkl[q] = dklp[q]; dij[q] = dijp[q]; }
-        double rs[4] = {0, 0, 0, 0}, cs[4] = {0, 0, 0, 0};
-        double g[4][4];
-        {
-            double2 ta0, tb0, ta1, tb1, ta2, tb2, ta3, tb3;
-            tile_load_patch(tiles, IJ, KL, I, J, K, L, r0, c0, ta0, tb0, ta1, tb1, ta2, tb2, ta3, tb3, ly);
-            g[0][0] = ta0.x; g[0][1] = ta0.y; g[0][2] = tb0.x; g[0][3] = tb0.y;
-            g[1][0] = ta1.x; g[1][1] = ta1.y; g[1][2] = tb1.x; g[1][3] = tb1.y;
-            g[2][0] = ta2.x; g[2][1] = ta2.y; g[2][2] = tb2.x; g[2][3] = tb2.y;
-            g[3][0] = ta3.x; g[3][1] = ta3.y; g[3][2] = tb3.x; g[3][3] = tb3.y;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                rs[r] += g[r][c] * dkl[c];
-                cs[c] += g[r][c] * dij[r];
-            }
-        if (WITH_K) {
-            // (the barrier at the end of the previous iteration has retired that tile's LDS readers)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                *reinterpret_cast<double2 *>(&s_g[(r0 + r) * LDT + c0]) = make_double2(g[r][0], g[r][1]);
-                *reinterpret_cast<double2 *>(&s_g[(r0 + r) * LDT + c0 + 2]) = make_double2(g[r][2], g[r][3]);
-            }
-            // D blocks: thread t loads element (t&63) of block (t>>6)
-            {
-                const int blk = t >> 6, e = t & 63, x = e >> 3, y = e & 7;
-                const int R = (blk & 1) ? I : J, Cb = (blk & 2) ? L : K;
-                s_d[blk >> 1][x * 9 + y][blk & 1] = Dp[(size_t)(R * 8 + x) * npad + Cb * 8 + y];
-            }
-        }
-        // ---- J: row sums over the 16 lanes of a row group, column sums over the 16 row groups ----
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            double v = rs[r];
-            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-            rs[r] = v;
-        }
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            double v = cs[c];
-            v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-            cs[c] = v;
-        }
-        if ((lane & 15) == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-                acc_add(&Jacc[(size_t)(I * 8 + ii) * npad + J * 8 + j0 + r], 2.0 * f * rs[r], dsc);
-        }
-        if (lane < 16) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) s_col[wave][c0 + c] = cs[c];
-        }
-        __syncthreads();
-        if (t < 64) {
-            const double v = s_col[0][t] + s_col[1][t] + s_col[2][t] + s_col[3][t];
-            acc_add(&Jacc[(size_t)(K * 8 + (t >> 3)) * npad + L * 8 + (t & 7)], 2.0 * f * v, dsc);
-        }
-        if (WITH_K) {
-            // four contractions; thread = output o (64) x partial group pg (4), 16 of the 64 terms each.  Which 16 is chosen
-            // per contraction so that the 32 lanes of a half-wave (x fixed, y = 0..7, pg = 0..3) hit 32 different LDS banks at
-            // every step (row stride 68: bank = 4 row + col mod 32; yh = y >> 2):
-            //   K1  row = 8x + a, col = 8v + y : v = pg + 4u, all a               -> bank = 8 pg + y + const
-            //   K2  row = 8a + x, col = 8v + y : v = pg + 4u, all a               -> bank = 8 pg + y + const
-            //   K3  row = 8x + a, col = 8y + v : v = pg + 4 (u ^ yh), all a       -> 8 (y & 3) + pg + 4 (u ^ yh) + const
-            //   K4  row = 8a + x, col = 8y + v : v = pg + 4 (u ^ yh), all a       -> same
-            // (with the straightforward split every read had 3- to 4-way conflicts and the K part cost as much as the stream)
-            const int o = t >> 2, pg = t & 3, x = o >> 3, y = o & 7, yh = y >> 2;
-            double k1 = 0, k2 = 0, k3 = 0, k4 = 0;
-#pragma unroll 1
-            for (int u = 0; u < 2; u++) {  // rolled: fully unrolled, the hoisted LDS reads spill (128-VGPR budget)
-                const int q = pg + 4 * u, q4 = pg + 4 * (u ^ yh);
-#pragma unroll
-                for (int a = 0; a < 8; a++) {
-                    typedef double vd2_ __attribute__((ext_vector_type(2)));
-                    const vd2_ d12 = *reinterpret_cast<const vd2_ *>(&s_d[0][a * 9 + q][0]);
-                    const vd2_ d34 = *reinterpret_cast<const vd2_ *>(&s_d[1][a * 9 + q4][0]);
-                    k1 += s_g[(x * 8 + a) * LDT + q * 8 + y] * d12.x;    // g[x][a][v=q][y]  D[J,K](a,v)
-                    k2 += s_g[(a * 8 + x) * LDT + q * 8 + y] * d12.y;    // g[a][x][v=q][y]  D[I,K](a,v)
-                    k3 += s_g[(x * 8 + a) * LDT + y * 8 + q4] * d34.x;   // g[x][a][y][v=q4] D[J,L](a,v)
-                    k4 += s_g[(a * 8 + x) * LDT + y * 8 + q4] * d34.y;   // g[a][x][y][v=q4] D[I,L](a,v)
-                }
-            }
-            k1 += __shfl_xor(k1, 1); k1 += __shfl_xor(k1, 2);
-            k2 += __shfl_xor(k2, 1); k2 += __shfl_xor(k2, 2);
-            k3 += __shfl_xor(k3, 1); k3 += __shfl_xor(k3, 2);
-            k4 += __shfl_xor(k4, 1); k4 += __shfl_xor(k4, 2);
-            if (pg == 0) {
-                acc_add(&Kacc[(size_t)(I * 8 + x) * npad + L * 8 + y], f * k1, dsc);
-                acc_add(&Kacc[(size_t)(J * 8 + x) * npad + L * 8 + y], f * k2, dsc);
-                acc_add(&Kacc[(size_t)(I * 8 + x) * npad + K * 8 + y], f * k3, dsc);
-                acc_add(&Kacc[(size_t)(J * 8 + x) * npad + K * 8 + y], f * k4, dsc);
-            }
-        }
-        __syncthreads();  // s_col / s_g reuse
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Several right-hand sides in ONE pass over the tiles.  The reference's callers ask for J and K of different density
 // matrices back to back -- unrestricted Hartree-Fock: J[D_u + D_d], K[2 D_u], K[2 D_d] (hcgto.py:238-241, hf.py:93-103,
@@ -376,7 +250,7 @@ __global__ __launch_bounds__(256, NK ? 3 : 1) void jk_multi_kernel(const double 
         }
         if (NK) {
             if (nj == 0) __syncthreads();
-            // the four exchange contractions (lane mapping and bank analysis: jk_tiles_kernel), NK densities per tile read
+            // the four exchange contractions (lane mapping and bank analysis: jk_stream_kernel), NK densities per tile read
             const int o = t >> 2, pg = t & 3, x = o >> 3, y = o & 7, yh = y >> 2;
             double k1[NKD], k2[NKD], k3[NKD], k4[NKD];
 #pragma unroll
@@ -477,7 +351,7 @@ __global__ void jk_multi_finish_kernel(double *__restrict__ J, int nj, double *_
 // of the kernel's fp64 atomics (7.9 M per 20-atom molecule, device scope: each one is a trip to the memory side) and the
 // same-address contention of concurrently running neighbouring blocks (grid-stride order made them all hit J[I,J] at once)
 // disappear; D[I,J] is reloaded only when IJ changes.  The column sums J[K,L] += g . D[I,J] change target every tile and
-// keep the 2-shuffle + 4-wave LDS combine of jk_tiles_kernel.
+// take 2 shuffles + a 4-wave LDS combine per tile.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256, 1) void j_stream_kernel(const double *__restrict__ dscp, const double *__restrict__ tiles,
                                                          double *__restrict__ work, int npad, long long ntiles, long long per_block,
@@ -564,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void j_stream_kernel(const double *__restri
 
 // ---------------------------------------------------------------------------------------------
 // Coulomb AND exchange of one density (restricted Hartree-Fock, hf.py:198-199) over CONTIGUOUS tile ranges: j_stream_kernel's
-// scheme -- row sums J[I,J] in registers until IJ changes -- plus the four exchange contractions of jk_tiles_kernel on the
+// scheme -- row sums J[I,J] in registers until IJ changes -- plus the four exchange contractions on the
 // tile parked in LDS.  Consecutive tiles of a range share (I, J) and, for K + 1 tiles in a row, K: the exchange blocks
 // K[I,K] and K[J,K] keep accumulating in registers until K (or IJ) changes, the other two, K[I,L] and K[J,L], change every
 // tile.  Per tile 64 + 128 fp64 atomics instead of 128 + 256 (ablation of the grid-stride kernel on a 20-atom molecule: the J
@@ -574,10 +448,12 @@ __global__ __launch_bounds__(256, 4) void jk_stream_kernel(const double *__restr
                                                           double *__restrict__ work, int npad, long long ntiles, long long per_block,
                                                           long long tbeg, int nao) {
     const TileLay ly(nao);
-    const double dsc = dscp ? *dscp : 0.0;
-    constexpr int LDT = 68;
+    const double dsc = dscp ? *dscp : 0.0;  // deterministic mode: fixed-point scale of the accumulators (common.hpp: acc_add)
+    constexpr int LDT = 68;  // row stride of the tile parked in LDS: 16-byte aligned rows, bank = 4 row + col (mod 32)
     __shared__ double s_col[4][64];  // (single buffer: two barriers per tile separate its writers and readers anyway)
     __shared__ __attribute__((aligned(16))) double s_g[64 * LDT];
+    // D[J,K], D[I,K] | D[J,L], D[I,L]; element (a, v) of a block at a * 9 + v, the two blocks of a pair interleaved so that
+    // one ds_read_b128 fetches both (the exchange part is LDS-read-bound)
     __shared__ __attribute__((aligned(16))) double s_d[2][72][2];
     const size_t n2 = (size_t)npad * npad;
     const double *Dp = work;
@@ -659,10 +535,18 @@ __global__ __launch_bounds__(256, 4) void jk_stream_kernel(const double *__restr
             const double v = s_col[0][t] + s_col[1][t] + s_col[2][t] + s_col[3][t];
             acc_add(&Jacc[(size_t)(K * 8 + (t >> 3)) * npad + L * 8 + (t & 7)], 2.0 * (I == J ? 0.5 : 1.0) * fk * v, dsc);
         }
-        {   // exchange: lane mapping and bank analysis as in jk_tiles_kernel
+        {
+            // four contractions; thread = output o (64) x partial group pg (4), 16 of the 64 terms each.  Which 16 is chosen
+            // per contraction so that the 32 lanes of a half-wave (x fixed, y = 0..7, pg = 0..3) hit 32 different LDS banks at
+            // every step (row stride 68: bank = 4 row + col mod 32; yh = y >> 2):
+            //   K1  row = 8x + a, col = 8v + y : v = pg + 4u, all a               -> bank = 8 pg + y + const
+            //   K2  row = 8a + x, col = 8v + y : v = pg + 4u, all a               -> bank = 8 pg + y + const
+            //   K3  row = 8x + a, col = 8y + v : v = pg + 4 (u ^ yh), all a       -> 8 (y & 3) + pg + 4 (u ^ yh) + const
+            //   K4  row = 8a + x, col = 8y + v : v = pg + 4 (u ^ yh), all a       -> same
+            // (with the straightforward split every read had 3- to 4-way conflicts and the K part cost as much as the stream)
             double k1 = 0, k2 = 0, k3 = 0, k4 = 0;
 #pragma unroll 1
-            for (int u = 0; u < 2; u++) {
+            for (int u = 0; u < 2; u++) {  // rolled: fully unrolled, the hoisted LDS reads spill (128-VGPR budget)
                 const int q = pg + 4 * u, q4 = pg + 4 * (u ^ yh);
 #pragma unroll
                 for (int a = 0; a < 8; a++) {
@@ -813,7 +697,7 @@ __global__ __launch_bounds__(256, 3) void jk_multi_stream_kernel(const double *_
             const double v = s_col[0][t] + s_col[1][t] + s_col[2][t] + s_col[3][t];
             acc_add(&Jacc[(size_t)(K * 8 + (t >> 3)) * npad + L * 8 + (t & 7)], 2.0 * (I == J ? 0.5 : 1.0) * fk * v, dsc);
         }
-        {   // exchange: lane mapping and bank analysis as in jk_tiles_kernel; the tile reads are shared by the NK densities
+        {   // exchange: lane mapping and bank analysis as in jk_stream_kernel; the tile reads are shared by the NK densities
             double k1[NK], k2[NK], k3[NK], k4[NK];
 #pragma unroll
             for (int q = 0; q < NK; q++) k1[q] = k2[q] = k3[q] = k4[q] = 0.0;
@@ -952,25 +836,15 @@ static int jk_from_tiles_impl(double *d_J, double *d_K, const double *d_tiles_pa
         hipLaunchKernelGGL(jk_det_scale_kernel, dim3(1), dim3(256), 0, st, dscp, d_work, 1, (size_t)npad * npad, d_tiles, nao);
         DQC_CHECK_LAUNCH();
     }
-    const unsigned grid = (unsigned)std::min<long long>(ntiles, 256 * 16);
-    static const char *jimpl = getenv("DQC_J_IMPL");  // "stride": the grid-stride kernel of round 1 (A/B runs)
     if (nrun == 0) {
         // (an empty slice: nothing to add)
-    } else if (!whole && jimpl && jimpl[0] == 's') {
-        set_error("dqc_jk_from_tiles_part: DQC_J_IMPL=stride streams the whole store only");
-        return DQC_EINVAL;
-    } else
-    if (with_k && !(jimpl && jimpl[0] == 's')) {
+    } else if (with_k) {
         // contiguous tile ranges of >= 8 tiles, 1024 ... 6144 blocks (4 resident per CU; sweep 1024 ... 8192 on benzene, 20-atom
         // cc-pVDZ and naphthalene / cc-pVTZ: flat within 3 % inside this window)
         static const long long jk_nblk_env = [] { const char *e = getenv("DQC_JK_NBLK"); return e ? atoll(e) : 0LL; }();
         const long long nblk = jk_nblk_env > 0 ? std::min<long long>(nrun, jk_nblk_env) : std::min<long long>(nrun, std::max<long long>(1024, std::min<long long>(6144, nrun / 8)));
         const long long per = (nrun + nblk - 1) / nblk;
         hipLaunchKernelGGL(jk_stream_kernel, dim3((unsigned)((nrun + per - 1) / per)), dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, per, tbeg, nao);
-    } else if (with_k) {
-        hipLaunchKernelGGL(jk_tiles_kernel<true>, dim3(grid), dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, nao);
-    } else if (jimpl && jimpl[0] == 's') {
-        hipLaunchKernelGGL(jk_tiles_kernel<false>, dim3(grid), dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, nao);
     } else {
         // contiguous tile ranges, ~6 resident blocks per CU x 2 rounds.  (Tried: 8 x 4 tile rectangles with the column sums in
         // LDS, 24 atomics per tile and no barrier -- 0.396 ms against 0.37 ms for this form: shorter contiguous runs.)
@@ -1040,8 +914,7 @@ static int jk_from_tiles_multi_impl(double *d_J, const double *d_dmJ, int nj, do
         const long long nblk_s = std::min<long long>(ntiles, std::max<long long>(1024, std::min<long long>(6144, ntiles / 8)));
         const long long per_s = (ntiles + nblk_s - 1) / nblk_s;
         const dim3 grid_s((unsigned)((ntiles + per_s - 1) / per_s));
-        static const char *mimpl = getenv("DQC_JK_MULTI_IMPL");  // "grid": the grid-stride kernel (A/B runs)
-        const bool stream_ok = njp <= 1 && nkp >= 1 && !(mimpl && mimpl[0] == 'g');
+        const bool stream_ok = njp <= 1 && nkp >= 1;
         if (stream_ok && njp == 1 && nkp == 2) hipLaunchKernelGGL((jk_multi_stream_kernel<1, 2>), grid_s, dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, per_s, nao);
         else if (stream_ok && njp == 1 && nkp == 1) hipLaunchKernelGGL((jk_multi_stream_kernel<1, 1>), grid_s, dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, per_s, nao);
         else if (stream_ok && njp == 0 && nkp == 2) hipLaunchKernelGGL((jk_multi_stream_kernel<0, 2>), grid_s, dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, per_s, nao);

@@ -19,7 +19,7 @@ from tests import molecules as M
 
 pytestmark = pytest.mark.gpu
 
-VXC_NAO = [7, 48, 170, 240]  # vxc_kernel / vxc_ws_kernel on one panel, the two-block shape, vxc_wsu / vxc_wsd (145 ... 208), vxc_ws2 (> 208)
+VXC_NAO = [7, 48, 170, 240]  # vxc_ws_kernel on one panel and with several tiles per wave, vxc_wsu / vxc_wsd (145 ... 208), vxc_ws2 (> 208)
 VXC_NGRID = [17, 4099]
 VXC_MAGS = [-40, -20, 0, 20]  # the potentials are scaled by 2^k
 

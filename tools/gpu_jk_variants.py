@@ -1,4 +1,4 @@
-"""RHF J + K of one density: jk_tiles_kernel<true> (dqc_jk_from_tiles) against jk_multi_kernel<1> (dqc_jk_from_tiles_multi, nj = nk = 1)"""
+"""RHF J + K of one density: jk_stream_kernel (dqc_jk_from_tiles) against jk_multi_stream_kernel<1, 1> (dqc_jk_from_tiles_multi, nj = nk = 1)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, dqc_amd
@@ -22,6 +22,6 @@ for name, geo, basis in (("C5", M.c5_molecule(0), "cc-pvdz"), ("C4", M.naphthale
     t2 = min(ev(lambda: lib.jk_multi(tiles, D1, D1)) for _ in range(3))
     J1, K1 = lib.jk(tiles, D, work, True)
     J2, K2 = lib.jk_multi(tiles, D1, D1)
-    print("%-8s J+K: jk_tiles<true> %.3f ms | jk_multi<1> %.3f ms | max rel diff J %.1e K %.1e" % (
+    print("%-8s J+K: jk_stream %.3f ms | jk_multi %.3f ms | max rel diff J %.1e K %.1e" % (
         name, t1, t2, float((J1 - J2[0]).abs().max() / J1.abs().max()), float((K1 - K2[0]).abs().max() / K1.abs().max())))
     del tiles

@@ -17,7 +17,7 @@ __global__ void naive(const v2d *__restrict__ buf, size_t n2, double *out) {
 
 template <int U, bool NT>
 __global__ __launch_bounds__(256) void tile(const v2d *__restrict__ buf, long long ntile, double *out) {
-    // a tile = 2048 v2d; thread t loads 8 v2d of a tile: rows of 64 doubles, 4 x (2 v2d) like jk_tiles_kernel
+    // a tile = 2048 v2d; thread t loads 8 v2d of a tile: rows of 64 doubles, 4 x (2 v2d) like the J / K stream kernels (tile_load_patch)
     double s = 0;
     const int t = threadIdx.x;
     for (long long T = (long long)blockIdx.x * U; T < ntile; T += (long long)gridDim.x * U) {
