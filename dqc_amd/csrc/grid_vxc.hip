@@ -24,6 +24,8 @@
 //
 // f64 MFMA fragment layout (gfx950): A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15],
 // C[row = (lane>>4) + 4*reg][col = lane&15].
+#include <utility>
+
 #include "grid_common.hpp"
 
 namespace dqc {
@@ -686,108 +688,243 @@ __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsu_kernel(double *__restrict__
 // 2.35 GHz with the MFMAs alone, 2.41 GHz with the stream alone), so what is left is the number of MFMAs.  A diagonal tile
 // needs only M_ii = Phi_i^T Psi_i: symmetrize_kernel forms (M_ii + M_ii^T) / 2 = V_ii anyway.  T^2 = 169 MFMAs per k-group
 // instead of T (T + 1) = 182 (-7 %) -- as many as the two-block vxc_ws_kernel form issues.  12 waves per block => 168 VGPRs
-// per wave for the 12 accumulator tiles.  Every wave owns NO off-diagonal tiles (two MFMAs each) followed by ND diagonal
-// tiles (one each); the deal is fixed at compile time so that the SIMDs (waves w and w + 4) carry 42, 42, 42, 43 MFMAs per
-// k-group for T = 13 and no wave more than 12 accumulator tiles.  Measured (C5 shape, random data): 0.691 ms against 0.725 ms.
-// Not pursued: sharing fragment reads between the tiles of a row -- a build that issues a quarter of the ds_read_b64 (wrong
-// results, timing only) is just 3-5 % faster.
+// per wave for the 12 accumulator tiles.  Measured (C5 shape, random data): 0.691 ms against 0.725 ms.
+//
+// Fragment reuse.  The A fragment of tile row t and the B fragment of tile column t are the same 64 doubles in the same
+// lanes (LDS doubles lk LS + 16 t + lr of the component), so a fragment is named by (Phi or Psi, tile index t, k-group)
+// alone and a wave that owns the tile set S needs, per k-group, the 2 |U| fragments of the tile indices U that occur in S
+// as a row or as a column -- however many MFMAs use them.  The ownership (WSD_OWNER, found by tools/wsd_deal_search.py) is
+// therefore a compile-time table that gives every wave a compact set of tiles with |U| <= 7 instead of a run of the
+// row-major triangle: T = 13 reads 2 x 48 fragments per k-group and block where a read pair per MFMA took 2 x 169.  A wave
+// keeps TWO fragment sets in registers: the MFMAs of k-group kk run from one while the reads of k-group kk + 1 fill the
+// other, spread evenly between those MFMAs (sched_barriers pin the places).  All addresses are ONE base register plus
+// immediates (tile index, k-group and component are compile-time), so there is still no VALU instruction between MFMAs.
+// Per output tile the MFMA sequence over (chunk, k-group, h) is unchanged -- h = 0: Phi_i^T Psi_j, then h = 1: Psi_i^T Phi_j --
+// so every block's partial sums are bit-identical to those of the linear deal; only the order among a wave's tiles differs
+// (all h = 0 products of a k-group, then all h = 1, then the diagonal tiles: no MFMA waits for the one before it).
+// Measured inside the bench (T = 13, docs/LOG_r14.md): 0.510 ms per launch against 0.529 ms with a read pair per MFMA.
 // ---------------------------------------------------------------------------------------------
 constexpr int wsd_ls(int T) { return ((16 * T) & 31) == 16 ? 16 * T : 16 * T + 16; }
 
+constexpr int WSD_TMIN = 10, WSD_TMAX = 13, WSD_NTRI = WSD_TMAX * (WSD_TMAX + 1) / 2;
+constexpr int WSD_MAXTILES = 12;  // accumulator tiles per wave: 96 VGPRs
+constexpr int WSD_MAXU = 7;       // tile indices per wave: two fragment sets of 4 |U| VGPRs
+// owner wave of every upper-triangle tile (row-major, diagonal included), one row per T = 10 ... 13; under each row its
+// triangle.  Constraints of the search: <= 12 tiles per wave, |U| <= 7, the MFMAs per k-group of the SIMDs (waves w and
+// w + 4) differ by at most one and those of the two waves of a SIMD by at most two; minimised: sum of |U| over the waves
+constexpr signed char WSD_OWNER[WSD_TMAX - WSD_TMIN + 1][WSD_NTRI] = {
+    // T = 10: tiles 6 7 7 7 7 7 7 7, MFMAs 12 12 13 12 13 13 12 13, SIMDs 25 25 25 25, sum |U| = 37
+    {7, 0, 3, 3, 2, 2, 7, 2, 0, 0, 4, 0, 1, 4, 1, 4, 2, 0, 4, 3, 3, 3, 5, 5, 7, 0, 7, 1, 3, 1, 6, 6, 6, 1, 3, 5, 4, 2, 5, 4, 2, 5, 2, 5, 1, 6, 7, 6, 7, 6, 6, 7, 5, 4, 1},
+    //   7 0 3 3 2 2 7 2 0 0
+    //     4 0 1 4 1 4 2 0 4
+    //       3 3 3 5 5 7 0 7
+    //         1 3 1 6 6 6 1
+    //           3 5 4 2 5 4
+    //             2 5 2 5 1
+    //               6 7 6 7
+    //                 6 6 7
+    //                   5 4
+    //                     1
+    // T = 11: tiles 9 9 8 9 7 9 8 7, MFMAs 16 16 16 16 14 14 15 14, SIMDs 30 30 31 30, sum |U| = 39
+    {5, 0, 6, 0, 5, 3, 6, 0, 5, 5, 3, 0, 7, 7, 4, 2, 2, 0, 4, 7, 2, 6, 7, 6, 3, 6, 3, 6, 7, 3, 1, 1, 1, 0, 0, 1, 7, 1, 5, 1, 6, 4, 4, 5, 1, 1, 2, 3, 1, 2, 3, 0, 0, 6, 2, 2, 3, 4, 7, 4, 5, 5, 4, 5, 2, 3},
+    //   5 0 6 0 5 3 6 0 5 5 3
+    //     0 7 7 4 2 2 0 4 7 2
+    //       6 7 6 3 6 3 6 7 3
+    //         1 1 1 0 0 1 7 1
+    //           5 1 6 4 4 5 1
+    //             1 2 3 1 2 3
+    //               0 0 6 2 2
+    //                 3 4 7 4
+    //                   5 5 4
+    //                     5 2
+    //                       3
+    // T = 12: tiles 9 9 11 10 10 11 9 9, MFMAs 18 17 18 19 18 19 18 17, SIMDs 36 36 36 36, sum |U| = 46
+    {4, 0, 0, 4, 7, 4, 7, 0, 1, 1, 0, 1, 3, 0, 6, 6, 6, 2, 0, 3, 2, 2, 3, 2, 5, 5, 0, 5, 5, 1, 1, 2, 1, 5, 6, 4, 5, 4, 6, 5, 4, 4, 5, 7, 3, 6, 3, 7, 3, 3, 7, 7, 6, 6, 7, 0, 4, 2, 5, 3, 2, 2, 7, 5, 6, 5, 0, 4, 1, 1, 3, 1, 2, 2, 7, 2, 3, 4},
+    //   4 0 0 4 7 4 7 0 1 1 0 1
+    //     3 0 6 6 6 2 0 3 2 2 3
+    //       2 5 5 0 5 5 1 1 2 1
+    //         5 6 4 5 4 6 5 4 4
+    //           5 7 3 6 3 7 3 3
+    //             7 7 6 6 7 0 4
+    //               2 5 3 2 2 7
+    //                 5 6 5 0 4
+    //                   1 1 3 1
+    //                     2 2 7
+    //                       2 3
+    //                         4
+    // T = 13: tiles 12 11 11 12 11 11 12 11, MFMAs 22 21 21 21 20 21 22 21, SIMDs 42 42 43 42, sum |U| = 48
+    {0, 2, 0, 0, 1, 1, 2, 2, 6, 0, 6, 2, 6, 4, 3, 3, 4, 5, 5, 2, 3, 4, 4, 4, 2, 6, 7, 3, 7, 3, 7, 3, 0, 6, 7, 7, 0, 4, 7, 3, 7, 0, 0, 4, 0, 7, 3, 1, 3, 1, 3, 1, 4, 4, 1, 5, 5, 1, 5, 5, 5, 7, 1, 3, 2, 5, 5, 5, 2, 2, 7, 6, 1, 6, 7, 6, 3, 0, 6, 0, 6, 1, 5, 0, 1, 4, 4, 6, 2, 2, 6},
+    //   0 2 0 0 1 1 2 2 6 0 6 2 6
+    //     4 3 3 4 5 5 2 3 4 4 4 2
+    //       6 7 3 7 3 7 3 0 6 7 7
+    //         0 4 7 3 7 0 0 4 0 7
+    //           3 1 3 1 3 1 4 4 1
+    //             5 5 1 5 5 5 7 1
+    //               3 2 5 5 5 2 2
+    //                 7 6 1 6 7 6
+    //                   3 0 6 0 6
+    //                     1 5 0 1
+    //                       4 4 6
+    //                         2 2
+    //                           6
+};
+// |U| of every wave as the search states it (static_assert below)
+constexpr int WSD_NU[WSD_TMAX - WSD_TMIN + 1][VXC_WAVES] = {
+    {5, 4, 5, 4, 5, 5, 4, 5}, {5, 5, 5, 5, 5, 4, 5, 5}, {6, 5, 5, 6, 6, 6, 6, 6}, {6, 6, 6, 6, 6, 6, 6, 6}};
+
+// the deal of T tile rows, derived from WSD_OWNER[T - 10]: per wave its tiles (the NO off-diagonal ones first, then the ND
+// diagonal ones), the sorted tile indices U it needs and, per tile, the slots of its row and column index in U
 template <int T>
 struct WsdDeal {
-    int no[VXC_WAVES], nd[VXC_WAVES], o0[VXC_WAVES], d0[VXC_WAVES];
-    constexpr WsdDeal() : no{}, nd{}, o0{}, d0{} {
-        const int noff = T * (T - 1) / 2;
-        int cost[4] = {0, 0, 0, 0};
+    int nt[VXC_WAVES], no[VXC_WAVES], nu[VXC_WAVES], nm[VXC_WAVES];  // tiles, off-diagonal tiles, |U|, MFMAs per k-group
+    int ti[VXC_WAVES][WSD_NTRI], tj[VXC_WAVES][WSD_NTRI];            // tile coordinates, ti <= tj
+    int si[VXC_WAVES][WSD_NTRI], sj[VXC_WAVES][WSD_NTRI];            // slots of ti and tj in u
+    int u[VXC_WAVES][WSD_TMAX];
+    int owned;  // tiles of the triangle whose table entry names a wave (every tile has one entry: owned exactly once)
+    constexpr WsdDeal() : nt{}, no{}, nu{}, nm{}, ti{}, tj{}, si{}, sj{}, u{}, owned(0) {
+        for (int pass = 0; pass < 2; pass++)  // pass 0: off-diagonal tiles, pass 1: diagonal tiles
+            for (int i = 0, k = 0; i < T; i++)
+                for (int j = i; j < T; j++, k++) {
+                    const int w = WSD_OWNER[T - WSD_TMIN][k];
+                    if (w < 0 || w >= VXC_WAVES || (i == j) != (pass == 1)) continue;
+                    ti[w][nt[w]] = i;
+                    tj[w][nt[w]] = j;
+                    nt[w]++;
+                    no[w] += i != j;
+                    nm[w] += i != j ? 2 : 1;
+                    owned++;
+                }
         for (int w = 0; w < VXC_WAVES; w++) {
-            no[w] = noff / VXC_WAVES + (w < noff % VXC_WAVES ? 1 : 0);
-            cost[w & 3] += 2 * no[w];
-        }
-        for (int d = 0; d < T; d++) {  // greedy: the next diagonal tile goes to the lightest SIMD, there to the wave with fewer tiles
-            int q = 0;
-            for (int r = 1; r < 4; r++)
-                if (cost[r] < cost[q]) q = r;
-            const int w = no[q] + nd[q] <= no[q + 4] + nd[q + 4] ? q : q + 4;
-            nd[w]++;
-            cost[q]++;
-        }
-        for (int w = 1; w < VXC_WAVES; w++) {
-            o0[w] = o0[w - 1] + no[w - 1];
-            d0[w] = d0[w - 1] + nd[w - 1];
+            for (int x = 0; x < T; x++) {
+                bool used = false;
+                for (int t = 0; t < nt[w]; t++) used = used || ti[w][t] == x || tj[w][t] == x;
+                if (used) u[w][nu[w]++] = x;
+            }
+            for (int t = 0; t < nt[w]; t++)
+                for (int s = 0; s < nu[w]; s++) {
+                    if (u[w][s] == ti[w][t]) si[w][t] = s;
+                    if (u[w][s] == tj[w][t]) sj[w][t] = s;
+                }
         }
     }
     constexpr int max_tiles() const {
         int m = 0;
-        for (int w = 0; w < VXC_WAVES; w++) m = no[w] + nd[w] > m ? no[w] + nd[w] : m;
+        for (int w = 0; w < VXC_WAVES; w++) m = nt[w] > m ? nt[w] : m;
         return m;
+    }
+    constexpr int simd_spread() const {  // waves w and w + 4 share a SIMD: largest minus smallest MFMA count per k-group
+        int lo = nm[0] + nm[4], hi = lo;
+        for (int q = 1; q < 4; q++) {
+            const int c = nm[q] + nm[q + 4];
+            lo = c < lo ? c : lo;
+            hi = c > hi ? c : hi;
+        }
+        return hi - lo;
+    }
+    constexpr int mfmas() const {
+        int m = 0;
+        for (int w = 0; w < VXC_WAVES; w++) m += nm[w];
+        return m;
+    }
+    constexpr bool nu_as_stated() const {
+        for (int w = 0; w < VXC_WAVES; w++)
+            if (nu[w] != WSD_NU[T - WSD_TMIN][w] || nu[w] > WSD_MAXU) return false;
+        return true;
+    }
+};
+template <int T>
+struct WsdDealOf {
+    static constexpr WsdDeal<T> v{};
+    static_assert(v.owned == T * (T + 1) / 2, "an upper-triangle tile without an owner wave");
+    static_assert(v.mfmas() == T * T, "T^2 MFMAs per k-group");
+    static_assert(v.max_tiles() <= WSD_MAXTILES, "more than 12 accumulator tiles per wave");
+    static_assert(v.simd_spread() <= 1, "the SIMDs' MFMA counts differ by more than one");
+    static_assert(v.nu_as_stated(), "per-wave fragment count |U| is not the stated one (or above 7)");
+};
+
+// LDS byte offset (from the wave's base: lk LS + lr of the current buffer) of the fragment in slot S of wave W's set,
+// component X (0: Phi, 1: Psi), k-group KK
+template <int T, int W, int S, int X, int KK>
+constexpr int wsd_frag_off() { return (WsdDealOf<T>::v.u[W][S] * 16 + KK * VWS_GS + X * VWS_XS) * 8; }
+
+// one chunk of consumer wave W: f[b][2 s + X] holds fragment (slot s, component X) of the k-groups with kk % 2 == b
+template <int T, int W>
+struct WsdChunk {
+    static constexpr int NT = WsdDealOf<T>::v.nt[W], NO = WsdDealOf<T>::v.no[W], NU = WsdDealOf<T>::v.nu[W];
+    static constexpr int NM = WsdDealOf<T>::v.nm[W], NR = 2 * NU;  // MFMAs and fragment reads per k-group
+    typedef double Frags[2][2 * WSD_MAXU];
+
+    template <int KK, int R>
+    static DQC_DEV void read(unsigned base, Frags &f) {
+        f[KK & 1][R] = *(lds_cdouble_t *)(base + wsd_frag_off<T, W, R / 2, R % 2, KK>());
+    }
+    template <int KK, int... R>
+    static DQC_DEV void read_all(unsigned base, Frags &f, std::integer_sequence<int, R...>) {
+        (read<KK, R>(base, f), ...);
+    }
+    // the reads of k-group KK that go in front of MFMA M of k-group KK - 1: reads [M NR / NMR, (M + 1) NR / NMR), M < NMR.
+    // The last two MFMAs of a k-group carry none: every fragment is requested at least three MFMAs before its first use
+    static constexpr int NMR = NM > 2 ? NM - 2 : 1;
+    template <int KK, int M, int R = M * NR / NMR>
+    static DQC_DEV void read_slice(unsigned base, Frags &f) {
+        if constexpr (M < NMR && R < (M + 1) * NR / NMR) {
+            read<KK, R>(base, f);
+            read_slice<KK, M, R + 1>(base, f);
+        }
+    }
+    // MFMA M of k-group KK: M < NO: tile M, h = 0 (Phi_i^T Psi_j); M < 2 NO: tile M - NO, h = 1 (Psi_i^T Phi_j); then the
+    // diagonal tiles (Phi_i^T Psi_i)
+    template <int KK, int M>
+    static DQC_DEV void step(unsigned base, Frags &f, v4d (&acc)[NT]) {
+        constexpr int t = M < NO ? M : M - NO, h = M >= NO && M < 2 * NO ? 1 : 0;
+        constexpr int a = 2 * WsdDealOf<T>::v.si[W][t] + h, b = 2 * WsdDealOf<T>::v.sj[W][t] + (1 - h);
+        if constexpr (KK < 3) read_slice<KK + 1, M>(base, f);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[t] = mfma_f64(f[KK & 1][a], f[KK & 1][b], acc[t]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    template <int KK, int... M>
+    static DQC_DEV void kgroup(unsigned base, Frags &f, v4d (&acc)[NT], std::integer_sequence<int, M...>) {
+        (step<KK, M>(base, f, acc), ...);
+    }
+    static DQC_DEV void run(unsigned base, v4d (&acc)[NT]) {
+        Frags f;
+        read_all<0>(base, f, std::make_integer_sequence<int, NR>{});
+        kgroup<0>(base, f, acc, std::make_integer_sequence<int, NM>{});
+        kgroup<1>(base, f, acc, std::make_integer_sequence<int, NM>{});
+        kgroup<2>(base, f, acc, std::make_integer_sequence<int, NM>{});
+        kgroup<3>(base, f, acc, std::make_integer_sequence<int, NM>{});
+    }
+    // off-diagonal tiles hold 2 V_ij (symmetrize_kernel halves them against the zero lower tiles), diagonal tiles M_ii
+    template <int... TL>
+    static DQC_DEV void store(double *__restrict__ vmat, const v4d (&acc)[NT], int lr, int lk, std::integer_sequence<int, TL...>) {
+        auto one = [&](int t, int ti, int tj) {
+            const int ia = ti * 16 + lk, ib = tj * 16 + lr;
+#pragma unroll
+            for (int r = 0; r < 4; r++) acc_add(&vmat[(size_t)(ia + 4 * r) * (16 * T) + ib], acc[t][r], g_vxc_det_scale);
+        };
+        (one(TL, WsdDealOf<T>::v.ti[W][TL], WsdDealOf<T>::v.tj[W][TL]), ...);
     }
 };
 
-template <int NO, int ND, int D = 2>
-DQC_DEV void wsd_chunk(const unsigned (&pi)[NO + ND], const unsigned (&pj)[NO + ND], v4d (&acc)[NO + ND]) {
-    // step s of a k-group: s < 2 NO: tile s / 2, h = s % 2 (h = 0: Phi_i^T Psi_j, h = 1: Psi_i^T Phi_j); then the diagonal tiles, h = 0
-    constexpr int PER = 2 * NO + ND, NS = 4 * PER;
-    double fa[D + 1], fb[D + 1];
-    auto rd = [&](int s) {
-        const int kk = s / PER, u = s % PER;
-        const int t = u < 2 * NO ? u / 2 : NO + (u - 2 * NO), h = u < 2 * NO ? u % 2 : 0;
-        fa[s % (D + 1)] = *(lds_cdouble_t *)(pi[t] + (kk * VWS_GS + (h ? VWS_XS : 0)) * 8);
-        fb[s % (D + 1)] = *(lds_cdouble_t *)(pj[t] + (kk * VWS_GS + (h ? 0 : VWS_XS)) * 8);
-    };
-#pragma unroll
-    for (int s = 0; s < D && s < NS; s++) rd(s);
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        if (s + D < NS) rd(s + D);
-        __builtin_amdgcn_sched_barrier(0);
-        const int u = s % PER;
-        const int t = u < 2 * NO ? u / 2 : NO + (u - 2 * NO);
-        acc[t] = mfma_f64(fa[s % (D + 1)], fb[s % (D + 1)], acc[t]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-template <int T, int NO, int ND>
-DQC_DEV void wsd_consumer(double *lds, double *__restrict__ vmat, int nchunk, int o0, int d0) {
-    constexpr int NT = NO + ND, LS = wsd_ls(T);  // rows of the output matrix: 16 T; LDS rows: == 16 (mod 32)
+template <int T, int W>
+DQC_DEV void wsd_consumer(double *lds, double *__restrict__ vmat, int nchunk) {
+    typedef WsdChunk<T, W> CH;
+    constexpr int LS = wsd_ls(T);  // rows of the output matrix: 16 T; LDS rows: == 16 (mod 32)
     const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
-    auto tile_ij = [&](int t, int &ti, int &tj) {
-        if (t >= NO) { ti = tj = d0 + (t - NO); return; }
-        int i = 0, rem = o0 + t;
-        while (rem >= T - 1 - i) { rem -= T - 1 - i; i++; }  // row i of the strict upper triangle holds T - 1 - i tiles
-        ti = i;
-        tj = i + 1 + rem;
-    };
-    v4d acc[NT];
-    unsigned pi[NT], pj[NT];  // LDS byte addresses of the row / column fragments in the Phi part (k-group 0, current buffer)
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double *)lds;
+    v4d acc[CH::NT];
 #pragma unroll
-    for (int t = 0; t < NT; t++) {
-        acc[t] = v4d{0, 0, 0, 0};
-        int ti, tj;
-        tile_ij(t, ti, tj);
-        pi[t] = lds0 + 8u * (unsigned)(lk * LS + ti * 16 + lr);
-        pj[t] = lds0 + 8u * (unsigned)(lk * LS + tj * 16 + lr);
-    }
+    for (int t = 0; t < CH::NT; t++) acc[t] = v4d{0, 0, 0, 0};
+    // LDS byte address of tile index 0's fragment in the Phi part (k-group 0, current buffer)
+    unsigned base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double *)lds + 8u * (unsigned)(lk * LS + lr);
     __syncthreads();
     for (int c = 0; c < nchunk; c++) {
         __syncthreads();  // chunk c - 1 done: the producers' combine window opens ...
         __syncthreads();  // ... and closes
-        wsd_chunk<NO, ND>(pi, pj, acc);
-        const unsigned delta = (c & 1) ? (unsigned)(-VWS_BUF * 8) : (unsigned)(VWS_BUF * 8);
-#pragma unroll
-        for (int t = 0; t < NT; t++) { pi[t] += delta; pj[t] += delta; }
+        CH::run(base, acc);
+        base += (c & 1) ? (unsigned)(-VWS_BUF * 8) : (unsigned)(VWS_BUF * 8);
     }
-    // off-diagonal tiles hold 2 V_ij (symmetrize_kernel halves them against the zero lower tiles), diagonal tiles M_ii
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-        int ti, tj;
-        tile_ij(t, ti, tj);
-        const int ia = ti * 16 + lk, ib = tj * 16 + lr;
-#pragma unroll
-        for (int r = 0; r < 4; r++) acc_add(&vmat[(size_t)(ia + 4 * r) * (16 * T) + ib], acc[t][r], g_vxc_det_scale);
-    }
+    CH::store(vmat, acc, lr, lk, std::make_integer_sequence<int, CH::NT>{});
 }
 
 template <int T, int NLP>
@@ -796,8 +933,7 @@ __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsd_kernel(double *__restrict__
                                                            const double *__restrict__ vgrad, int slab, int lda) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     constexpr int KCH = 16, ld = 16 * T;
-    constexpr WsdDeal<T> DL{};
-    static_assert(DL.max_tiles() <= 12, "more than 12 accumulator tiles per wave");
+    static_assert(T >= WSD_TMIN && T <= WSD_TMAX, "no ownership table for this T");
     const int wave = threadIdx.x >> 6;
     const int gs = blockIdx.x * slab, ge = min(gs + slab, ngrid);
     if (gs >= ngrid) return;
@@ -806,15 +942,13 @@ __global__ __launch_bounds__(VWU_NT, 3) void vxc_wsd_kernel(double *__restrict__
         vwu_producer<NLP, true>(lds, ao, ngrid, ld, w, vrho, vgrad, gs, ge, nchunk, lda, wsd_ls(T));
         return;
     }
-#define DQC_WSD_CASE(W) case W: wsd_consumer<T, DL.no[W], DL.nd[W]>(lds, vmat, nchunk, DL.o0[W], DL.d0[W]); break;
-    switch (wave) {  // wave-uniform; equal (NO, ND) pairs share one instantiation
+#define DQC_WSD_CASE(W) case W: wsd_consumer<T, W>(lds, vmat, nchunk); break;
+    switch (wave) {  // wave-uniform; every wave has its own straight-line body (its tile indices are immediates)
         DQC_WSD_CASE(0) DQC_WSD_CASE(1) DQC_WSD_CASE(2) DQC_WSD_CASE(3)
         DQC_WSD_CASE(4) DQC_WSD_CASE(5) DQC_WSD_CASE(6) DQC_WSD_CASE(7)
     }
 #undef DQC_WSD_CASE
 }
-
-
 
 // V = (M + M^T) / 2 on the (ld, ld) matrix (deterministic mode: M arrives as fixed-point integers).  Rows / columns nao .. ld - 1
 // are ZEROED: the kernels stage 16 T columns per AO row, and where the row stride of the AO arrays is below that
