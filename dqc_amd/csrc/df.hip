@@ -7,6 +7,7 @@
 // solid-harmonic factor) is appended to the shell table, the ket "pair" list is (auxiliary shell, unit), and the
 // Rys shell-quartet kernel of eri_core.hpp runs unchanged in its 3C / 2C output modes: <LA,LB,LC,0> and <LA,0,LC,0>.
 #include "eri_generic.hpp"
+#include "grid_common.hpp"
 
 namespace dqc {
 
@@ -221,6 +222,125 @@ __global__ __launch_bounds__(256) void df_j_kernel(double *__restrict__ jmat, co
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// density-fitted exchange (RI-K) from the Cholesky-whitened three-index tensor B[P, mu, nu] = sum_Q (L^-1)[P, Q] (mu nu|Q):
+//     Y[P, mu, i] = sum_lam B[P, mu, lam] Lf[lam, i],     K[mu, nu] = sum_P sum_i Y[P, mu, i] Y[P, nu, i],     D = Lf Lf^T
+//
+// Stage 1, df_k_half_kernel: the tall-skinny GEMM (naux nao) x nao x rp on the fp64 matrix cores.  One wave owns two 16-row
+// tiles of one or two slabs B_P and all rp / 16 column tiles; B streams from HBM straight into the MFMA operand registers -- lane
+// (j, q) loads the four consecutive doubles B[P, mu0 + j, k0 + 4 q .. + 3] (32 contiguous bytes per lane, 128 per row) and feeds
+// them to four MFMAs whose k index it defines as k0 + 4 q + s; the factor operand is read from LDS under the same map, so the
+// permutation of k inside a 16-block cancels and B is never staged or read twice.  Lf is staged in LDS in chunks of DFK_LDS_DOUBLES
+// (row stride rp + 4 == 4 (mod 8): the two k rows a 32-lane half reads sit 32 banks apart, ds_read_b64 conflict-free), each element
+// once per block.  The product is formed TRANSPOSED -- Lf^T as the A operand, B_P^T as the B operand -- so that the accumulator has
+// mu on the lane (C[row = i][col = mu]) and Y is written as the matrix stage 2 wants:  Yt[(P, i), mu], row stride lda =
+// dqc_ao_stride(nao), 128 contiguous bytes per 16 lanes.  No cross-block sums: bit-reproducible as it stands.
+//
+// Stage 2, K = Yt^T Yt, is the split-K symmetric rank update of the Vxc pass with (P, i) in the role of the grid points and unit
+// weights -- dqc_grid_vxc's one-operand form as it is (grid_vxc.hip: producer / consumer waves, upper-triangular tiles for nao <= 240,
+// fp64 atomics or, in deterministic mode, fixed point on 2^47, the closing symmetrisation that also zeroes the padding).
+// ---------------------------------------------------------------------------------------------
+constexpr int DFK_LDS_DOUBLES = 8192;  // 64 KB of factor rows per chunk: two blocks per CU, i.e. two MFMA-issuing waves per SIMD
+
+DQC_DEV void dfk_load4(double (&a)[4], const double *row, int k, int nao, bool ok, bool even) {
+    // row[k .. k + 3], zero past the end of the row (and for a row that does not exist)
+    if (ok && even && k + 3 < nao) {  // (even nao: every row starts on 16 bytes)
+        const double2 v0 = *reinterpret_cast<const double2 *>(row + k), v1 = *reinterpret_cast<const double2 *>(row + k + 2);
+        a[0] = v0.x; a[1] = v0.y; a[2] = v1.x; a[3] = v1.y;
+    } else {
+#pragma unroll
+        for (int s = 0; s < 4; s++) a[s] = ok && k + s < nao ? row[k + s] : 0.0;
+    }
+}
+
+template <int NT>  // NT = rp / 16 column tiles of the factor
+__global__ __launch_bounds__(256, 2) void df_k_half_kernel(double *__restrict__ yt, const double *__restrict__ b,
+                                                           const double *__restrict__ orb, int nao, int naux, int ld, int lda, int kc) {
+    extern __shared__ __align__(16) double s_lf[];  // [kc][rp + 4]
+    constexpr int RP = 16 * NT, LS = RP + 4;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+    const int T = ld >> 4;
+    const long long ntile = (long long)naux * T;
+    const bool even = (nao & 1) == 0;
+    const double *row[2];
+    bool ok[2];
+    long long tile[2];
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        tile[u] = ((long long)blockIdx.x * 4 + wave) * 2 + u;
+        const long long tt = tile[u] < ntile ? tile[u] : 0;
+        const int p = (int)(tt / T), mu = (int)(tt - (long long)p * T) * 16 + j;
+        ok[u] = tile[u] < ntile && mu < nao;
+        row[u] = b + ((size_t)p * nao + (ok[u] ? mu : 0)) * nao;
+    }
+    v4d acc[2][NT];
+#pragma unroll
+    for (int u = 0; u < 2; u++)
+#pragma unroll
+        for (int t = 0; t < NT; t++) acc[u][t] = v4d{0.0, 0.0, 0.0, 0.0};
+    for (int c0 = 0; c0 < ld; c0 += kc) {
+        const int cn = min(kc, ld - c0);  // (multiples of 16; rows nao .. ld - 1 of the padded factor are zero)
+        __syncthreads();
+        for (int e = threadIdx.x * 2; e < cn * RP; e += 512) {
+            const int k = e / RP, i = e - k * RP;
+            const double2 v = *reinterpret_cast<const double2 *>(orb + (size_t)(c0 + k) * RP + i);
+            *reinterpret_cast<double2 *>(&s_lf[k * LS + i]) = v;
+        }
+        __syncthreads();
+        double a[2][4];
+        dfk_load4(a[0], row[0], c0 + 4 * q, nao, ok[0], even);
+        dfk_load4(a[1], row[1], c0 + 4 * q, nao, ok[1], even);
+        for (int k0 = 0; k0 < cn; k0 += 16) {
+            double an[2][4];  // the next k-block's rows are asked for before this block's MFMAs
+            const int kn = c0 + k0 + 16 + 4 * q;
+            const bool more = k0 + 16 < cn;
+            dfk_load4(an[0], row[0], kn, nao, ok[0] && more, even);
+            dfk_load4(an[1], row[1], kn, nao, ok[1] && more, even);
+            const double *lf = s_lf + (k0 + 4 * q) * LS + j;
+#pragma unroll
+            for (int s = 0; s < 4; s++)
+#pragma unroll
+                for (int t = 0; t < NT; t++) {
+                    const double f = lf[s * LS + 16 * t];
+                    acc[0][t] = mfma_f64(f, a[0][s], acc[0][t]);
+                    acc[1][t] = mfma_f64(f, a[1][s], acc[1][t]);
+                }
+#pragma unroll
+            for (int s = 0; s < 4; s++) { a[0][s] = an[0][s]; a[1][s] = an[1][s]; }
+        }
+    }
+    // C[row = q + 4 reg][col = j]: factor column i = 16 t + q + 4 reg, AO mu = 16 tmu + j
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        if (tile[u] >= ntile) continue;
+        const int p = (int)(tile[u] / T), mu = (int)(tile[u] - (long long)p * T) * 16 + j;
+        if (mu >= lda) continue;  // (columns nao .. lda - 1 receive the zeros of the rows that do not exist)
+        double *out = yt + (size_t)p * RP * lda + mu;
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) out[(size_t)(16 * t + q + 4 * r) * lda] = acc[u][t][r];
+    }
+}
+
+// the unit weights of stage 2 and the slack behind Yt that the Vxc kernels' 16-column tile reads reach
+__global__ void df_k_fill_kernel(double *__restrict__ slack, int nslack, double *__restrict__ ones, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ones[i] = 1.0;
+    if (i < nslack) slack[i] = 0.0;
+}
+
+template <int NT>
+static void launch_df_k_half(double *yt, const double *b, const double *orb, int nao, int naux, int ld, int lda, hipStream_t st) {
+    const int rp = 16 * NT;
+    const int kc = std::min(ld, DFK_LDS_DOUBLES / (rp + 4) / 16 * 16);
+    const size_t shmem = sizeof(double) * (size_t)kc * (rp + 4);
+    const long long ntile = (long long)naux * (ld / 16);
+    auto kern = df_k_half_kernel<NT>;
+    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((ntile + 7) / 8)), dim3(256), shmem, st, yt, b, orb, nao, naux, ld, lda, kc);
+}
+
 }  // namespace dqc
 
 extern "C" {
@@ -275,6 +395,43 @@ int dqc_df_coulomb(double *d_j, const double *d_j3c, const double *d_inv_j2c, co
     hipLaunchKernelGGL(df_j_kernel, dim3((unsigned)((npair + 3) / 4)), dim3(256), 0, st, d_j, d_j3c, c, nao, naux, npair);
     DQC_CHECK_LAUNCH();
     return DQC_OK;
+}
+
+size_t dqc_df_exchange_work_doubles(int nao, int naux, int rp) {
+    // Yt (naux rp rows of dqc_ao_stride(nao) doubles) | 16 doubles of slack | naux rp unit weights
+    if (nao <= 0 || naux <= 0 || rp <= 0) return 0;
+    return (size_t)naux * rp * dqc_ao_stride(nao) + 16 + (size_t)naux * rp;
+}
+
+int dqc_df_exchange(double *d_k, const double *d_b, const double *d_orb, const double *d_orbt, int nao, int naux, int rp,
+                    double *d_work, void *stream) {
+    // d_k (ld, ld), ld = dqc_padded_nao(nao), is overwritten (symmetric, zero padding).  Enqueues only.
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    (void)d_orbt;  // (the transposed half of the factor pair: this kernel stages the factor from d_orb alone)
+    if (nao < 0 || naux < 0) { set_error("dqc_df_exchange: negative nao or naux"); return DQC_EINVAL; }
+    if (rp <= 0 || dqc_padded_norb(rp) != rp) { set_error("dqc_df_exchange: rp is not a padded factor width (dqc_padded_norb)"); return DQC_EINVAL; }
+    if (nao == 0) return DQC_OK;
+    if (!d_k) { set_error("dqc_df_exchange: null output"); return DQC_EINVAL; }
+    const int ld = dqc_padded_nao(nao), lda = dqc_ao_stride(nao);
+    if (naux == 0) { DQC_HIP(hipMemsetAsync(d_k, 0, sizeof(double) * (size_t)ld * ld, st)); return DQC_OK; }
+    if (!d_b || !d_orb || !d_work) { set_error("dqc_df_exchange: null pointer argument"); return DQC_EINVAL; }
+    if ((long long)naux * rp > 2147483647LL / 2) { set_error("dqc_df_exchange: naux * rp beyond the row count of the rank update"); return DQC_EINVAL; }
+    const int nrow = naux * rp;
+    double *yt = d_work, *slack = yt + (size_t)nrow * lda, *ones = slack + 16;
+    hipLaunchKernelGGL(df_k_fill_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, st, slack, 16, ones, nrow);
+    DQC_CHECK_LAUNCH();
+    switch (rp / 16) {
+        case 1: launch_df_k_half<1>(yt, d_b, d_orb, nao, naux, ld, lda, st); break;
+        case 2: launch_df_k_half<2>(yt, d_b, d_orb, nao, naux, ld, lda, st); break;
+        case 3: launch_df_k_half<3>(yt, d_b, d_orb, nao, naux, ld, lda, st); break;
+        case 4: launch_df_k_half<4>(yt, d_b, d_orb, nao, naux, ld, lda, st); break;
+        case 6: launch_df_k_half<6>(yt, d_b, d_orb, nao, naux, ld, lda, st); break;
+        case 8: launch_df_k_half<8>(yt, d_b, d_orb, nao, naux, ld, lda, st); break;
+        default: set_error("dqc_df_exchange: no kernel for this factor width"); return DQC_EINVAL;
+    }
+    DQC_CHECK_LAUNCH();
+    return dqc_grid_vxc(d_k, yt, 1, nrow, nao, ones, ones, nullptr, stream);
 }
 
 }  // extern "C"

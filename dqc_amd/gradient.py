@@ -46,6 +46,10 @@ def nuclear_gradient(qc) -> torch.Tensor:
     if h._vext is not None:
         raise NotImplementedError("nuclear gradients with an external potential are not implemented: the vext term "
                                   "(grid points and basis centres moving in vext) is missing from dqc_amd.gradient")
+    if h.df is not None and h.df.exchange and (not eng.is_ks or getattr(eng, "exx", 0.0) != 0.0):
+        raise NotImplementedError("nuclear gradients with fitted exchange (densityfit(exchange=True)) are not implemented: the K "
+                                  "term needs the derivative three-index integrals contracted with a three-index density, "
+                                  "which is not built")
     X = h._orthozer
     pol = eng.polarized
     dms = [qc._dm.u, qc._dm.d] if pol else [qc._dm]

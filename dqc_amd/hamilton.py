@@ -158,6 +158,7 @@ class HamiltonMI355(_Base):
         # two-electron energies of the last build, and the orbital factors of the last two ao_orb2dm results (the spin-up and
         # spin-down matrices of an unrestricted iteration); per weight tensor: the last two occupation checks
         self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors = _Memo(), _Memo(), _Memo(), _Memo(2)
+        self._dfk_memo = _Memo(2)  # fitted exchange: K[D] of the last two matrices (the spin pair of an unrestricted iteration)
         self._w_checked = _Memo(2)
         # which density kernel the grid passes took: "factor" (rank-n_occ kernel, D = ao_orb2dm(...) recognised), "dense" (anonymous
         # full matrix: 0.84 instead of 0.50 ms on a 20-atom molecule).  A caller that forms more than two density matrices before
@@ -166,7 +167,7 @@ class HamiltonMI355(_Base):
 
     def clear_memos(self):
         """forget what was remembered per density matrix (a graph capture's tensors belong to its private pool)"""
-        for m in (self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors):
+        for m in (self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors, self._dfk_memo):
             m.clear()
 
     # ------------------------------------------------------------------ properties
@@ -348,9 +349,10 @@ class HamiltonMI355(_Base):
         """what a functional with the exact-exchange fraction `a` cannot be combined with (raises)"""
         if a == 0.0:
             return
-        if self._df is not None:
+        if self._df is not None and not self._df.exchange:
             raise NotImplementedError("hybrid functionals (exact-exchange fraction %g) cannot be used with density fitting: "
-                                      "Mol.densityfit() fits the Coulomb operator J only, there is no fitted exchange" % a)
+                                      "Mol.densityfit() fits the Coulomb operator J only, there is no fitted exchange "
+                                      "(densityfit(exchange=True) fits K as well)" % a)
         if self._pworld > 1:
             raise NotImplementedError("hybrid functionals (exact-exchange fraction %g) on a Hamiltonian sharded over several GPUs "
                                       "(shard_over) are not implemented" % a)
@@ -600,10 +602,15 @@ class HamiltonMI355(_Base):
 
     def get_exchange(self, dm):
         """returns -K/2 (hcgto.py:234); SpinParam input uses K(2 D_sigma) per spin (hcgto.py:238-241)"""
-        if self._df is not None:  # hcgto.py:229-230
+        if self._df is not None and not self._df.exchange:  # hcgto.py:229-230
             raise RuntimeError("Exact exchange cannot be computed with density fitting")
         if not self.is_built:
             raise RuntimeError("Please call `build()` before `get_exchange`")
+        if self._df is not None:  # fitted exchange: K[2 D_s] / 2 = K[D_s] per spin, from the factor of each matrix where it is known
+            if isinstance(dm, SpinParam):
+                return SpinParam(u=LinearOperator.m(-self._batched(self._dfk_orth, dm.u), is_hermitian=True),
+                                 d=LinearOperator.m(-self._batched(self._dfk_orth, dm.d), is_hermitian=True))
+            return LinearOperator.m(-0.5 * self._batched(self._dfk_orth, dm), is_hermitian=True)
         if isinstance(dm, SpinParam):
             if dm.u.dim() == 2 and dm.d.dim() == 2:  # both spins from one pass (memoised by get_elrep_exchange_pol)
                 ku, kd = self._jk_pol(dm)[1]
@@ -616,6 +623,19 @@ class HamiltonMI355(_Base):
         else:
             mat = -0.5 * self._jk_orth(dm, True)[1]
         return LinearOperator.m(mat, is_hermitian=True)
+
+    def _dfk_ao(self, dm, dao=None):
+        """fitted K of one (nao, nao) density in the AO basis: the kernel on the orbital factor of `dm` when it came out of ao_orb2dm
+        unmodified, else the torch form on `dao` = X dm X^T"""
+        fac = self._factor_of(dm)
+        if fac is None and dao is None:
+            dao = self._unconvert_dm(dm)
+        return self._df.exchange_ao(dao, fac)
+
+    def _dfk_orth(self, dm):
+        """fitted K[D] (plain K, not -K/2) of one (nao, nao) density, orthogonalised basis; remembered for the last two matrices"""
+        k = self._dfk_memo.get(dm)
+        return k if k is not None else self._dfk_memo.put(self._sym_orth(self._dfk_ao(dm)), dm)
 
     def _jk_pol(self, dm):
         """unrestricted Hartree-Fock: J[D_u + D_d], -K[2 D_u]/2, -K[2 D_d]/2 (hcgto.py:238-241, hf.py:93-103, 198-199) from
@@ -941,6 +961,8 @@ class HamiltonMI355(_Base):
     #   unrestricted hybrid  a            own=True             -- (no fused form: jk_multi)                  a E_K, keyed on the pair
     #
     # The torch form takes the AO density of restricted KS from a one-panel factor (one thin GEMM); the builds with K use X D X^T.
+    # Fitted exchange (densityfit(exchange=True)) rides on the torch form of every row with K: J from df.coulomb_ao, K from
+    # df.exchange_ao on the orbital factor (dqc_df_exchange), the same energies remembered.
 
     def _fock2e(self, dm, kfrac, vxc, core, mark=None):
         """J[D] - kfrac K[D] / 2 + Vxc[D] (+ core) of ONE restricted density matrix, orthogonalised basis.  kfrac None: no exchange;
@@ -949,7 +971,7 @@ class HamiltonMI355(_Base):
         version of `dm`, so that dm2energy(dm) right after dm2scp(dm) streams neither the tiles nor the grid again"""
         assert dm.dim() == 2 and (self.xc is not None or not vxc)
         with_k, hybrid = kfrac is not None, kfrac is not None and vxc
-        if with_k and self._df is not None:  # hcgto.py:229-230
+        if with_k and self._df is not None and not self._df.exchange:  # hcgto.py:229-230
             raise RuntimeError("Exact exchange cannot be computed with density fitting")
         if hybrid:
             self._check_hybrid(kfrac)
@@ -977,6 +999,7 @@ class HamiltonMI355(_Base):
                 self._beside(side, lambda: lib.jk_stream_prepared(tiles, n, work, with_k))
             elif self._df is not None:
                 jao = self._df.coulomb_ao(dao)
+                kao = self._dfk_ao(dm, dao) if with_k else None  # (fitted exchange: the kernel on the orbital factor)
             else:
                 jao, kao = self._beside(side, lambda: self._jk_ao(dao, with_k), dao)
             mark()
@@ -1008,14 +1031,31 @@ class HamiltonMI355(_Base):
     def _fock2e_pol(self, dm: SpinParam, kfrac, core):
         """stacked (2, nao, nao)  J[D_u + D_d] - kfrac K[D_s] + Vxc_s[D_u, D_d] (+ core) of an unrestricted pair, orthogonalised basis
         (a get_exchange(dm) is -a K[2 D_s] / 2 = -a K[D_s] per spin, hcgto.py:238-241); kfrac None: no exchange.  Needs
-        `tiles_resident`.  The pass over the tile store (HBM-bound) is enqueued on a second stream BESIDE the two-spin grid pass (its
+        `tiles_resident`, or with exchange a Hamiltonian whose density fitting covers K (the branch at the top).
+        The pass over the tile store (HBM-bound) is enqueued on a second stream BESIDE the two-spin grid pass (its
         Vxc products are bound by the matrix cores; a graph capture: one stream), and the two sums take ONE batched AO -> orthogonal
         conversion.  Without exchange and with both factors one panel the ends are fused: L L^T of the stacked factor [L_u | L_d] in one
         launch, then per spin J + V_s, X^T . X, the symmetrisation and the core Hamiltonian in one launch each.  With exchange: J and
         the two K from ONE pass (dqc_jk_from_tiles_multi), and a E_K of the pair is remembered"""
-        assert self.xc is not None and dm.u.dim() == 2 and self.tiles_resident
+        assert self.xc is not None and dm.u.dim() == 2
         if kfrac is not None:
             self._check_hybrid(kfrac)
+        if self._df is not None and kfrac is not None:
+            # fitted J and K: J from the total density, K per spin from the two factors, the torch ends
+            x = self._orthozer
+            ds = self._unconvert_dm(torch.stack([dm.u, dm.d]))
+            ds = (ds + ds.transpose(-2, -1)) * 0.5
+            jao = self._df.coulomb_ao(ds[0] + ds[1])
+            kao = torch.stack([self._dfk_ao(dm.u, ds[0]), self._dfk_ao(dm.d, ds[1])])
+            potinfo = self.xc.get_vxc(self._dm2densinfo_pol(dm))
+            n = self._nao_ao
+            vu, vd = self._vxc_ao_from_potinfo(potinfo.u), self._vxc_ao_from_potinfo(potinfo.d)
+            self._energy_memo.put(_Energies(ka=-0.5 * kfrac * (ds * kao).sum()), dm.u, dm.d)
+            mat = torch.stack([jao - kfrac * kao[0] + vu[:n, :n], jao - kfrac * kao[1] + vd[:n, :n]])
+            mat = x.transpose(-2, -1) @ mat @ x
+            mat = (mat + mat.transpose(-2, -1)) * 0.5
+            return mat if core is None else core + mat
+        assert self.tiles_resident
         n, x = self._nao_ao, self._orthozer
         fu, fd = self._factor_of(dm.u), self._factor_of(dm.d)
         one = fu is not None and fd is not None and len(fu) == 1 and len(fd) == 1
@@ -1103,10 +1143,12 @@ class HamiltonMI355(_Base):
         return ["orth_transforms", "jk_tiles", "grid_density", "xc_eval", "grid_vxc", "fock_assemble"], ev
 
     def getparamnames(self, methodname: str, prefix: str = "") -> List[str]:
+        # (fitted exchange: the whitened three-index tensor of the DFMI355 object and the orthogonaliser instead of the tile store)
+        knames = ["_tiles"] if self._df is None or not self._df.exchange else ["_df._b", "_orthozer"]
         table = {
             "get_kinnucl": ["kinnucl_mat"], "get_nuclattr": ["nucl_mat"], "get_overlap": ["olp_mat"],
-            "get_elrep": ["_tiles"], "get_exchange": ["_tiles"], "ao_orb2dm": [],
-            "get_e_hcore": ["kinnucl_mat"], "get_e_elrep": ["_tiles"], "get_e_exchange": ["_tiles"],
+            "get_elrep": ["_tiles"], "get_exchange": knames, "ao_orb2dm": [],
+            "get_e_hcore": ["kinnucl_mat"], "get_e_elrep": ["_tiles"], "get_e_exchange": knames,
             "get_e_xc": ["_ao", "_orthozer", "dvolume"], "get_vxc": ["_ao", "_orthozer", "dvolume"],
             "get_vext": ["_ao", "_orthozer", "dvolume"], "_dm2densinfo": ["_ao", "_orthozer"],
             "_get_vxc_from_potinfo": ["_ao", "_orthozer", "dvolume"],

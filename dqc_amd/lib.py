@@ -95,6 +95,9 @@ def load():
     lib.dqc_projector_tc2.argtypes = [c_dp, c_dp, c_dp, c_int, ctypes.c_double, c_int, ctypes.c_double, c_dp, c_vp]
     lib.dqc_purify_tc2_persist.argtypes = [c_dp, c_dp, c_int, ctypes.c_double, c_int, ctypes.c_double, c_dp, c_vp, c_vp]
     lib.dqc_df_coulomb.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_dp, c_vp]
+    lib.dqc_df_exchange.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_vp]
+    lib.dqc_df_exchange_work_doubles.argtypes = [c_int, c_int, c_int]
+    lib.dqc_df_exchange_work_doubles.restype = c_sz
     lib.dqc_eri_tiles_to_dense.argtypes = [c_dp, c_dp, c_int, c_vp]
     lib.dqc_jk_from_tiles.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_vp]
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
@@ -358,6 +361,38 @@ def df_coulomb(j3c, inv_j2c, dm_ao, work=None):
         _check(load().dqc_df_coulomb(_ptr(out), _ptr(j3c), _ptr(inv_j2c), _ptr(dm_ao), nao, naux, _ptr(work), st_),
                "dqc_df_coulomb")
     return out
+
+
+def df_exchange_work(nao, naux, rp, device):
+    """the work buffer of df_exchange for factors up to `rp` padded columns"""
+    return torch.empty(int(load().dqc_df_exchange_work_doubles(int(nao), int(naux), int(rp))), dtype=torch.float64, device=device)
+
+
+def df_exchange(b, factor_pair, work=None, naux=None):
+    """K_ao (nao, nao) = sum_P (B_P L) (B_P L)^T of the density D = L L^T: b (naux, nao, nao) the whitened three-index tensor
+    (one contiguous slab per auxiliary function), factor_pair = (orb (ld, rp), orbt (rp, ld)) the padded AO-basis factor of
+    fock_factor / pad_factor; naux: contract the leading `naux` slabs of b only (default: all).  Symmetric; under set_deterministic
+    bit-reproducible (the Vxc kernels' fixed point on 2^47: |K| < 2^16).  The arguments are checked before anything is launched"""
+    if b.dim() != 3 or b.shape[1] != b.shape[2] or b.shape[1] == 0:
+        raise DqcAmdError("df_exchange: b must be (naux, nao, nao), got %s" % (tuple(b.shape),))
+    nao = int(b.shape[1])
+    naux = int(b.shape[0]) if naux is None else int(naux)
+    if naux < 0 or naux > b.shape[0]:
+        raise DqcAmdError("df_exchange: naux = %d outside [0, %d]" % (naux, b.shape[0]))
+    orb, orbt = factor_pair
+    ld = padded_nao(nao)
+    rp = int(orb.shape[1]) if orb.dim() == 2 else 0
+    if orb.dim() != 2 or orb.shape[0] != ld or rp == 0 or padded_norb(rp) != rp:
+        raise DqcAmdError("df_exchange: the factor must be (%d, rp) with rp a padded width (padded_norb), got %s" % (ld, tuple(orb.shape)))
+    if orbt is not None and tuple(orbt.shape) != (rp, ld):
+        raise DqcAmdError("df_exchange: the transposed factor must be (%d, %d), got %s" % (rp, ld, tuple(orbt.shape)))
+    need = int(load().dqc_df_exchange_work_doubles(nao, naux, rp))
+    if work is None or work.numel() < need:
+        work = torch.empty(need, dtype=torch.float64, device=b.device)
+    out = torch.empty((ld, ld), dtype=torch.float64, device=b.device)
+    with _on(b.device) as st_:
+        _check(load().dqc_df_exchange(_ptr(out), _ptr(b), _ptr(orb), _ptr(orbt), nao, naux, rp, _ptr(work), st_), "dqc_df_exchange")
+    return out[:nao, :nao]
 
 
 def cart2sph_matrix(tab, device):

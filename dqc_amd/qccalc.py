@@ -113,7 +113,7 @@ class _Engine:
             return h.get_elrep_plus_exchange_plus_vxc(dm, core=self._core_matrix())
         if dm.dim() == 2 and self.is_ks:
             return h.get_elrep_plus_vxc(dm, core=self._core_matrix())
-        if dm.dim() == 2 and h.df is None:
+        if dm.dim() == 2 and (h.df is None or h.df.exchange):  # (fitted J and K: the same build in its torch form)
             return h.get_elrep_plus_exchange(dm, core=self._core_matrix())
         fock = (self.knvext + h.get_elrep(dm) + (h.get_vxc(dm) if self.is_ks else h.get_exchange(dm))).fullmatrix()
         return fock if a == 0.0 else fock + a * h.get_exchange(dm).fullmatrix()

@@ -133,8 +133,10 @@ class Mol:
             raise RuntimeError("atommasses: no mass table entry for Z = %s (dqc_amd ships Z = 1 .. 18)" % sorted(set(heavy)))
         return torch.tensor([self._AMU[int(z)] * 1822.888486209 for z in self._atomzs], dtype=self._dtype, device=self._device)
 
-    def densityfit(self, method=None, auxbasis=None):
+    def densityfit(self, method=None, auxbasis=None, exchange=False):
         """dqc/system/mol.py:170-204: switch the Hamiltonian to the density-fitted Coulomb operator.
+        exchange=True (not in the reference): the exchange operator is fitted too (RI-K: same auxiliary set, same Coulomb metric), so
+        that HF and hybrid functionals run without the ~nao^4-byte ERI tile store; False: J only, exchange and hybrids are refused.
         auxbasis: list (per atom) of lists of CGTOBasis, a basis name shipped under dqc_amd/data/basis, or "etb[:beta]"
         (the built-in even-tempered set, dqc_amd.basis.even_tempered_aux) or "autoaux[:beta]" (generated from the orbital basis,
         dqc_amd.basis.product_etb_aux).  The reference's default "cc-pvtz-jkfit" and the other named JK-fit sets are external
@@ -149,7 +151,7 @@ class Mol:
         info = {}
         auxbases = make_aux_atombases(self._atomzs, self._atompos, auxbasis, self._atombases, info)
         self.auxbasis_used = info["auxbasis_used"]  # (what the fit really uses: "autoaux (generated ...)" when the named set has no tables)
-        df = DensityFitInfo(method=method, auxbases=auxbases)
+        df = DensityFitInfo(method=method, auxbases=auxbases, exchange=bool(exchange))
         self._hamilton = HamiltonMI355(self._atombases, spherical=True, df=df, efield=self._efield, vext=self._vext,
                                        orthozer=self._orthogonalize_basis, aoparamzer=self._aoparamzer,
                                        device=self._device)

@@ -48,6 +48,7 @@ class DensityFitInfo:
     """dqc/utils/datastruct.py:73-76"""
     method: str
     auxbases: List[AtomCGTOBasis]
+    exchange: bool = False  # also fit the exchange operator K (RI-K), same auxiliary set and metric (dqc_amd only)
 
 
 @dataclass

@@ -289,6 +289,18 @@ int dqc_int2c2e(double *d_j2c, const int *atm, int natm, const int *bas, int nba
 int dqc_df_coulomb(double *d_j, const double *d_j3c, const double *d_inv_j2c, const double *d_dm_ao, int nao,
                    int naux, double *d_work, void *stream);
 
+/* density-fitted exchange matrix (RI-K), AO basis, of the density D = L L^T given by its padded factor pair:
+ *   Y[P, mu, i] = sum_lam B[P, mu, lam] L[lam, i],   K[mu, nu] = sum_P sum_i Y[P, mu, i] Y[P, nu, i].
+ * d_b (naux, nao, nao): the whitened three-index tensor B[P, mu, nu] = sum_Q (C^-1)[P, Q] (mu nu|Q), C the Cholesky factor of
+ * (P|Q), one contiguous nao x nao slab per auxiliary function.  d_orb (ld, rp) / d_orbt (rp, ld): the factor pair of
+ * dqc_grid_density_lr (ld = dqc_padded_nao(nao), rp = dqc_padded_norb(r); rows >= nao and columns >= r zero; d_orbt is not read).
+ * d_k (ld, ld) is overwritten: symmetric, rows / columns >= nao zero.  d_work: dqc_df_exchange_work_doubles doubles (the
+ * half-transformed tensor, written and read once).  The cross-block sums of K are those of dqc_grid_vxc: fp64 atomics, or under
+ * dqc_set_deterministic fixed point on 2^47 (bit-reproducible; |K| < 2^16).  Only enqueues on `stream`. */
+size_t dqc_df_exchange_work_doubles(int nao, int naux, int rp);
+int dqc_df_exchange(double *d_k, const double *d_b, const double *d_orb, const double *d_orbt, int nao, int naux, int rp,
+                    double *d_work, void *stream);
+
 /* ---- nuclear gradients of the SCF energy   ------------------------------------
  * The reference differentiates through its "ip" derivative integrals (molintor.py:463-500) and the implicit-function
  * backward of the SCF fixed point (scf_qccalc.py:63-67, 109-113); at convergence that is
