@@ -325,7 +325,9 @@ DQC_DEV void rys_roots(double X, double *u, double *w) {
         }
         return;
     }
-    int it = (int)(X * (1.0 / 2.5));
+    // (clamped to the last interval of this N: the double just below XMAX = 50, 55, 60 multiplies up to 14 + 2N, the first
+    // interval of the next N's table)
+    int it = min((int)(X * (1.0 / 2.5)), 13 + 2 * N);
     double x = (X - (it * 2.5 + 1.25)) * (1.0 / 1.25);
     const double *tab = RYS_TAB + RYS_OFF[N - 1] + (size_t)it * (2 * N) * (RYS_DEG + 1);
     double x2 = 2.0 * x;
@@ -374,7 +376,7 @@ DQC_DEV void rys_root1_lds(const __attribute__((address_space(3))) double *lt, d
         w = RYS_HERM_W[N][r] * sqrt(ix);
         return;
     }
-    int it = (int)(X * (1.0 / 2.5));
+    int it = min((int)(X * (1.0 / 2.5)), 13 + 2 * N);  // (clamp: see rys_roots)
     double x = (X - (it * 2.5 + 1.25)) * (1.0 / 1.25);
     const __attribute__((address_space(3))) double *c = lt + (it * N + r) * RYS_LDS_ROW;
     double x2 = 2.0 * x, a1 = 0, a2 = 0, b1 = 0, b2 = 0;
@@ -397,7 +399,7 @@ DQC_DEV void rys_root1(double X, int r, double &u, double &w) {
         w = RYS_HERM_W[N][r] * sqrt(ix);
         return;
     }
-    int it = (int)(X * (1.0 / 2.5));
+    int it = min((int)(X * (1.0 / 2.5)), 13 + 2 * N);  // (clamp: see rys_roots)
     double x = (X - (it * 2.5 + 1.25)) * (1.0 / 1.25);
     const double *cu = RYS_TAB + RYS_OFF[N - 1] + ((size_t)it * (2 * N) + r) * (RYS_DEG + 1);
     const double *cw = cu + N * (RYS_DEG + 1);

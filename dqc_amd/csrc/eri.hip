@@ -564,6 +564,45 @@ __global__ void shell_dmax_by_l_kernel(double *__restrict__ dl, const double *__
     const unsigned long long bits = (unsigned long long)__double_as_longlong(m);
     if (m > 0.0 && bits > *slot) atomicMax(slot, bits);  // (the plain read only saves atomics: a stale value is smaller)
 }
+
+// One X per thread through the production root / weight lookups (dqc_probe_rys): VAR 0 rys_roots, 1 rys_root1 per root, 2
+// rys_root1_lds from a staged table, 3 rys_root1_rt, 4 boys01_lds (u <- F_0, w <- F_1).  u, w: (nx, N) row-major
+template <int VAR, int N>
+__global__ __launch_bounds__(256) void probe_rys_kernel(const double *__restrict__ x, int nx, double *__restrict__ u, double *__restrict__ w) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    typedef __attribute__((address_space(3))) double lds_double_t;
+    lds_double_t *ltab = (lds_double_t *)lds;
+    if constexpr (VAR == 2) rys_stage_lds<N>(ltab, threadIdx.x, 256);
+    if constexpr (VAR == 4) boys_stage_lds(ltab, threadIdx.x, 256);
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nx) return;
+    const double X = x[i];
+    double ru[N], rw[N];
+    if constexpr (VAR == 0) rys_roots<N>(X, ru, rw);
+    if constexpr (VAR == 4) boys01_lds(ltab, X, ru[0], rw[0]);
+#pragma unroll
+    for (int r = 0; r < N; r++) {
+        if constexpr (VAR == 1) rys_root1<N>(X, r, ru[r], rw[r]);
+        if constexpr (VAR == 2) rys_root1_lds<N>(ltab, X, r, ru[r], rw[r]);
+        if constexpr (VAR == 3) rys_root1_rt(N, X, r, ru[r], rw[r]);
+        u[(size_t)i * N + r] = ru[r];
+        w[(size_t)i * N + r] = rw[r];
+    }
+}
+
+template <int VAR, int N>
+static int probe_rys_launch(int n, const double *d_x, int nx, double *d_u, double *d_w, hipStream_t st) {
+    if constexpr (N > 1) {
+        if (n != N) return probe_rys_launch<VAR, N - 1>(n, d_x, nx, d_u, d_w, st);
+    }
+    size_t lds_bytes = 0;
+    if constexpr (VAR == 2) lds_bytes = sizeof(double) * rys_lds_doubles<N>();
+    if constexpr (VAR == 4) lds_bytes = sizeof(double) * BOYS_DOUBLES;
+    hipLaunchKernelGGL((probe_rys_kernel<VAR, N>), dim3((nx + 255) / 256), dim3(256), lds_bytes, st, d_x, nx, d_u, d_w);
+    DQC_CHECK_LAUNCH();
+    return DQC_OK;
+}
 }  // namespace dqc
 
 extern "C" {
@@ -963,6 +1002,27 @@ int dqc_eri_tiles_to_dense(double *d_dense, const double *d_tiles, int nao, void
     hipLaunchKernelGGL(tiles_to_dense_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, d_dense, d_tiles, nao);
     DQC_CHECK_LAUNCH();
     return DQC_OK;
+}
+
+int dqc_probe_rys(int variant, int n, const double *d_x, int nx, double *d_u, double *d_w, void *stream) {
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    static const int nmax[5] = {RYS_NMAX, RYS_NMAX, 2, RYS_NMAX, 1};  // (the LDS tables exist for one and two roots: eri_core.hpp)
+    if (variant < 0 || variant > 4 || n < 1 || n > nmax[variant] || nx < 0) {
+        set_error("dqc_probe_rys: variant 0..4 with n in 1..9 (variant 2: 1..2, variant 4: 1)");
+        return DQC_EINVAL;
+    }
+    if (nx == 0) return DQC_OK;
+    int rc;
+    switch (variant) {
+    case 0: return probe_rys_launch<0, RYS_NMAX>(n, d_x, nx, d_u, d_w, st);
+    case 1: return probe_rys_launch<1, RYS_NMAX>(n, d_x, nx, d_u, d_w, st);
+    case 2: return probe_rys_launch<2, 2>(n, d_x, nx, d_u, d_w, st);
+    case 3: return probe_rys_launch<3, RYS_NMAX>(n, d_x, nx, d_u, d_w, st);
+    default:
+        if ((rc = boys_table_ensure())) return rc;
+        return probe_rys_launch<4, 1>(n, d_x, nx, d_u, d_w, st);
+    }
 }
 
 }  // extern "C"

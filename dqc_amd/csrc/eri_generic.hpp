@@ -39,7 +39,7 @@ DQC_DEV void rys_root1_rt(int N, double X, int r, double &u, double &w) {
         w = RYS_HERM_W[N][r] * sqrt(ix);
         return;
     }
-    const int it = (int)(X * (1.0 / 2.5));
+    const int it = min((int)(X * (1.0 / 2.5)), 13 + 2 * N);  // (clamp: see rys_roots)
     const double x = (X - (it * 2.5 + 1.25)) * (1.0 / 1.25);
     const double *cu = RYS_TAB + RYS_OFF[N - 1] + ((size_t)it * (2 * N) + r) * (RYS_DEG + 1);
     const double *cw = cu + N * (RYS_DEG + 1);

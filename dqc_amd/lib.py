@@ -143,6 +143,7 @@ def load():
     lib.dqc_grid_vxc.argtypes = [c_dp, c_dp, c_int, c_int, c_int, c_dp, c_dp, c_dp, c_vp]
     lib.dqc_probe_stream_read.argtypes = [c_dp, c_sz, c_dp, c_vp]
     lib.dqc_probe_mfma_f64.argtypes = [c_dp, c_int, c_vp]
+    lib.dqc_probe_rys.argtypes = [c_int, c_int, c_dp, c_int, c_dp, c_dp, c_vp]
     _lib = lib
     if os.environ.get("DQC_AMD_DETERMINISTIC", "0") == "1":
         lib.dqc_set_deterministic(1)
@@ -1268,6 +1269,18 @@ def probe_stream_read(buf):
     with _on(buf.device) as st_:
         _check(load().dqc_probe_stream_read(_ptr(buf), buf.numel(), _ptr(out), st_), "dqc_probe_stream_read")
     return out
+
+
+def probe_rys(variant, n, x):
+    """the integral kernels' own root / weight lookups at the arguments x (float64 device vector): (u, w), each (len(x), n) --
+    variant 0 rys_roots, 1 rys_root1, 2 rys_root1_lds, 3 rys_root1_rt; variant 4 (n = 1): boys01_lds, u = F_0, w = F_1
+    (include/dqc_amd.h: dqc_probe_rys)"""
+    x = x.contiguous()
+    u = torch.empty((x.numel(), max(int(n), 0)), dtype=torch.float64, device=x.device)
+    w = torch.empty_like(u)
+    with _on(x.device) as st_:
+        _check(load().dqc_probe_rys(int(variant), int(n), _ptr(x), x.numel(), _ptr(u), _ptr(w), st_), "dqc_probe_rys")
+    return u, w
 
 
 def probe_mfma_f64_tflops(device, iters=4000):

@@ -545,6 +545,16 @@ int dqc_probe_stream_read(const double *d_buf, size_t n, double *d_out, void *st
 /* fp64 MFMA (16x16x4) issue-rate probe: 2048 waves x 8 accumulators x iters MFMAs; d_out: 131072 doubles */
 int dqc_probe_mfma_f64(double *d_out, int iters, void *stream);
 
+/* ---- test probe: the Rys root / weight and Boys lookups of the integral kernels, one X = rho |PQ|^2 per thread -------------
+ * d_x (nx) -> d_u, d_w (nx, n) row-major, through the device functions the kernels call:
+ *   variant 0  rys_roots<n>      (int1e, gradients)             n 1..9
+ *   variant 1  rys_root1<n>, once per root (compile-time ERI classes)   n 1..9
+ *   variant 2  rys_root1_lds<n> from the table staged in LDS    n 1..2
+ *   variant 3  rys_root1_rt(n, ...) (runtime-angular-momentum kernel)   n 1..9
+ *   variant 4  boys01_lds: d_u <- F_0(x), d_w <- F_1(x)         n 1
+ * Any other (variant, n): DQC_EINVAL. */
+int dqc_probe_rys(int variant, int n, const double *d_x, int nx, double *d_u, double *d_w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,24 +274,73 @@ def test_oracle_vs_reference_generated_golden(name, golden_dir):
                 assert np.allclose(lapl.numpy()[idx], g["probe%d_lapl" % k], rtol=1e-9, atol=1e-10)
 
 
-def test_rys_tables_sum_to_boys(golden_dir):
-    """the generated Rys tables (used by the HIP ERI kernel) reproduce the Boys moments F_k(X), k < 2n"""
+def _rys_tables(golden_dir):
+    """RYS_OFF, RYS_TAB and the two Hermite tables of the generated header the HIP kernels include"""
     import re
     src = open(os.path.join(os.path.dirname(golden_dir), "..", "dqc_amd", "csrc", "rys_tables.inc")).read()
     offs = [int(x) for x in re.search(r"RYS_OFF\[\d+\] = \{(.*?)\}", src).group(1).split(",")]
     body = re.search(r"RYS_TAB\[RYS_TAB_LEN\] = \{(.*?)\};", src, re.S).group(1)
     tab = np.array([float(x) for x in body.replace("\n", " ").split(",") if x.strip()])
+    herm = []
+    for name in ("RYS_HERM_X2", "RYS_HERM_W"):
+        body = re.search(name + r"\[10\]\[9\] = \{(.*?)\};", src, re.S).group(1)
+        herm.append(np.array([float(x) for x in re.findall(r"[-+0-9.eE]+", body)]).reshape(10, 9))
+    return offs, tab, herm[0], herm[1]
+
+
+def _rys_lookup(tables, n, X):
+    """roots u and weights w of the n-point rule at X the way the device lookups (rys_roots, rys_root1, rys_root1_lds,
+    rys_root1_rt) take them: the Hermite form from XMAX = 35 + 5 n on, below it the interval it = (int)(X * (1.0 / 2.5))
+    clamped to the last interval of n, in double arithmetic"""
+    offs, tab, hx2, hw = tables
+    if X >= 35.0 + 5.0 * n:
+        ix = 1.0 / X
+        return hx2[n, :n] * ix, hw[n, :n] * np.sqrt(ix)
+    it = min(int(X * (1.0 / 2.5)), 13 + 2 * n)
+    x = (X - (it * 2.5 + 1.25)) * (1.0 / 1.25)
+    vals = [np.polynomial.chebyshev.chebval(x, tab[offs[n - 1] + (it * 2 * n + q) * 14: offs[n - 1] + (it * 2 * n + q + 1) * 14])
+            for q in range(2 * n)]
+    return np.array(vals[:n]), np.array(vals[n:])
+
+
+def test_rys_tables_sum_to_boys(golden_dir):
+    """the generated Rys tables (used by the HIP ERI kernel) reproduce the Boys moments F_k(X), k < 2n, for every n = 1 ... 9:
+    at random X against the oracle's Boys function, and at the arguments of tests/golden/rys_boys_moments.npz (every interval
+    edge with its neighbouring doubles, XMAX with its neighbours, the Hermite branch) against its 50-digit values.  The
+    interval index is the device's expression: the double below XMAX = 50, 55, 60 (n = 3, 4, 5) multiplies up to 14 + 2 n
+    and lands on the first interval of the next n's table unless it is clamped"""
+    tables = _rys_tables(golden_dir)
+    gold = np.load(os.path.join(golden_dir, "rys_boys_moments.npz"))
     rng = np.random.default_rng(7)
-    for n in range(1, 8):
+    for n in range(1, 10):
         for X in rng.uniform(0, 35 + 5 * n - 1e-6, 25):
-            it = int(X / 2.5)
-            x = (X - (it * 2.5 + 1.25)) / 1.25
-            vals = [np.polynomial.chebyshev.chebval(x, tab[offs[n - 1] + (it * 2 * n + q) * 14: offs[n - 1] + (it * 2 * n + q + 1) * 14])
-                    for q in range(2 * n)]
-            u, w = np.array(vals[:n]), np.array(vals[n:])
+            u, w = _rys_lookup(tables, n, X)
             F = nat.boys(2 * n - 1, X)
             for k in range(2 * n):
                 assert abs(np.sum(w * u ** k) - F[k]) < 2e-13 * F[0], (n, X, k)
+        xs, fs = gold["x_n%d" % n], gold["f_n%d" % n]
+        xmax = 35.0 + 5.0 * n
+        for X in (xmax, np.nextafter(xmax, 0.0), np.nextafter(xmax, np.inf), 2.5 * (13 + 2 * n), 1e5):
+            assert X in xs
+        for X, F in zip(xs, fs):
+            u, w = _rys_lookup(tables, n, float(X))
+            assert np.all(u > 0) and np.all(u < 1) and np.all(w > 0), (n, X)
+            for k in range(2 * n):
+                assert abs(np.sum(w * u ** k) - F[k]) <= 2e-13 * F[0], (n, X, k)
+
+
+def test_oracle_boys_vs_mpmath_fixture(golden_dir):
+    """nat.boys(17, X) -- the Boys function under every oracle integral, at the orders the (gg|gg) class and its gradient
+    companions reach -- against the 50-digit values of the fixture, to 1e-14 relative, over all of the fixture's arguments"""
+    gold = np.load(os.path.join(golden_dir, "rys_boys_moments.npz"))
+    worst = (0.0, None, None)
+    for key in ["n%d" % n for n in range(1, 10)] + ["boys"]:
+        for X, F in zip(gold["x_" + key], gold["f_" + key]):
+            e = np.abs(nat.boys(17, float(X)) - F) / F
+            if e.max() > worst[0]:
+                worst = (float(e.max()), float(X), int(e.argmax()))
+    print("nat.boys(17, X) vs mpmath: worst relative error %.3e at X = %r, order %d" % worst)
+    assert worst[0] <= 1e-14, worst
 
 
 def test_cart2sph_tables_agree(golden_dir):
