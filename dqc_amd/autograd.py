@@ -11,6 +11,7 @@ first derivative is a Hellmann-Feynman (+ Pulay) expression -- no response equat
     XC parameters    sum_g w_g d e_xc(rho_g; p) / dp         torch autograd of get_edensityxc at fixed rho
     atomzs           -V_C + sum_B Z_B / R_CB + dE/dN         dqc_int1e_potential at the nuclei; dE/dN: Janak, below
     orb_weights      eps_i of each channel (Janak)           eigenvalues of the converged Fock matrix
+    basis            dE/d alpha_p, dE/d c_p (Pulay terms)    dqc_amd.gradient.basis_gradient, chained through wfnormalize_
 
 dE/dN routes the derivative of the occupation numbers to orbital ceil(n) - 1 of each spin channel, as the reference's
 occnumber backward does (dqc/utils/safeops.py:75-77).  Derivatives of derivatives are not provided: a backward with
@@ -25,7 +26,8 @@ from . import lib
 
 def grad_inputs(qc):
     """(kinds, tensors): the caller's tensors the energy of `qc` depends on -- positions, floating-point charges, every efield
-    element, vext, user orb_weights (u, d) and the parameters of a torch.nn.Module functional"""
+    element, vext, user orb_weights (u, d), the basis table's exponents and normalised coefficients (functions of the caller's
+    CGTOBasis tensors, when one of them requires grad) and the parameters of a torch.nn.Module functional"""
     eng = qc._engine
     leaves = getattr(eng.get_system(), "_grad_leaves", {})
     kinds, tensors = [], []
@@ -41,6 +43,13 @@ def grad_inputs(qc):
         for s, w in enumerate(leaves["orb_weights"]):
             kinds.append(("orb_weights", s))
             tensors.append(w)
+    if "basis" in leaves:
+        # the table's exponents and normalised coefficients as torch functions of the caller's CGTOBasis tensors: autograd carries
+        # dE/d(table rows) (gradient.basis_gradient) through the normalisation to the leaves and sums shared tensors
+        from .basis import table_parameters
+        for i, t in enumerate(table_parameters(eng.get_system()._basis_shells)):
+            kinds.append(("basis", i))
+            tensors.append(t)
     if eng.is_ks and isinstance(eng.xc, torch.nn.Module):
         for k, p in enumerate(eng.xc.parameters()):
             kinds.append(("xc", k))
@@ -165,6 +174,11 @@ def energy_derivatives(qc, kinds):
                 nu, nd = (wts.u.numel(), wts.d.numel()) if pol else (wts.numel(), wts.numel())
                 d = d + 0.5 * (eu[_occ_index(mol._nup, nu)] + ed[_occ_index(mol._ndn, nd)])
             out[k] = d
+        elif what == "basis":
+            if "basis" not in out:
+                from .gradient import basis_gradient
+                out["basis"] = basis_gradient(qc)                 # (nprim_total, 2): by alpha_p, by the normalised c_p
+            out[k] = out["basis"][:, k[1]]
         elif what == "orb_weights":
             eu, ed = eigenvalues()
             e_s = eu if k[1] == 0 else ed

@@ -266,3 +266,42 @@ def make_tables(atombases: List[AtomCGTOBasis]):
             ptr += 2 * ng
     return (np.array(atm, dtype=np.int32).reshape(-1, 6), np.array(bas, dtype=np.int32).reshape(-1, 8),
             np.array(env, dtype=np.float64), (np.array(zs) if fracz else None))
+
+
+def primitive_rows(bas):
+    """(prim_shell (nprim_total,), shell_off (nsh + 1,)) of a `bas` table: the shell of every primitive row and the first row of
+    every shell -- the rows of dqc_amd.gradient.basis_gradient are the primitives in table order, shell by shell"""
+    bas = np.asarray(bas).reshape(-1, 8)
+    ng = bas[:, 2].astype(np.int64)
+    shell_off = np.concatenate([[0], np.cumsum(ng)])
+    return np.repeat(np.arange(bas.shape[0]), ng), shell_off
+
+
+def companion_tables(atm, bas, env):
+    """The per-primitive companion shells of the basis-parameter derivative (the layout dqc_eri_grad_basis builds on the host), as
+    (atm, bas, env) tables with 2 * nprim_total UNCONTRACTED shells in primitive-row order:
+        [0, nprim)          the primitive itself: l, exponent alpha_p, coefficient 1             d a / d c_p     = g_p
+        [nprim, 2 nprim)    its r_A^2 multiple:   l + 2, exponent alpha_p, coefficient -c_p      d a / d alpha_p = -c_p r_A^2 g_p
+    (Cartesian components: the l + 2 shell stands for the sum of the three components with one power raised by 2.)"""
+    bas = np.asarray(bas, dtype=np.int32).reshape(-1, 8)
+    env = list(np.asarray(env, dtype=np.float64))
+    rows = []
+    for up in (0, 1):
+        for sh in bas:
+            for k in range(int(sh[2])):
+                a, c = env[sh[5] + k], env[sh[6] + k]
+                rows.append([sh[0], sh[1] + 2 * up, 1, 1, 0, len(env), len(env) + 1, 0])
+                env.extend([a, -c if up else 1.0])
+    return np.asarray(atm, dtype=np.int32), np.array(rows, dtype=np.int32).reshape(-1, 8), np.array(env, dtype=np.float64)
+
+
+def table_parameters(shells):
+    """shells: [(angmom, alphas, coeffs, normalized)] in table order, the caller's tensors as handed to Mol.  Returns
+    (alphas (nprim_total,), coeffs (nprim_total,)): the exponents and NORMALISED coefficients of make_tables' rows as torch
+    functions of those tensors (CGTOBasis.wfnormalize_ is plain torch), for the chain from dE/d(table rows) to the caller's leaves"""
+    al, co = [], []
+    for l, a, c, normalized in shells:
+        sh = CGTOBasis(angmom=l, alphas=a, coeffs=c, normalized=normalized).wfnormalize_()
+        al.append(sh.alphas.to(torch.float64).cpu())
+        co.append(sh.coeffs.to(torch.float64).cpu())
+    return torch.cat(al), torch.cat(co)

@@ -225,6 +225,11 @@ struct EriOut {
     double *gpart = nullptr;        // (nslot, natm, 3) partial gradients (spread to keep atomics apart)
     int nslot = 1, natm = 0, norig = 0;
     int dirn = 0;                   // +1: first bra shell is an "up" companion, -1: "down"
+                                    // basis-parameter derivative (dqc_eri_grad_basis): the first bra shell is an UNCONTRACTED companion
+                                    // of one primitive p, +2: its r_A^2 multiple (l + 2, coefficient -c_p: component u meets u - 2 e_dir
+                                    // of the original shell), 0: the primitive itself (every direction repeats the same sum).  There
+                                    // norig = all shells of the table, so that `cao` and `sh_atom` are indexed by the companion itself:
+                                    // cao = the Cartesian offset of ITS original shell, sh_atom = its output row ("natm" = rows)
     double jscale = 1.0;            // weight of the Coulomb-type product
     double kscale = 0.0;            // weight of the exchange-type products (1: HF, 0: pure J)
     // density-fitting gradient (gmode 1: (d_A a b|k) D_ab c_k -> +2 to a's atom, -2 to k's atom;
@@ -801,15 +806,11 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
 #pragma unroll
                 for (int dir = 0; dir < 3; dir++) {
                     int o[3] = {u[0], u[1], u[2]};
-                    double coef;
-                    if (og.dirn > 0) {
-                        if (o[dir] == 0) continue;
-                        o[dir]--;
-                        coef = 1.0;
-                    } else {
-                        coef = -(o[dir] + 1.0);
-                        o[dir]++;
-                    }
+                    // up: one power down, coefficient 1; down: one power up, coefficient -(power + 1); basis-parameter companions: dirn = 2, two
+                    // powers down, or 0, the component itself (branch-free: a longer body stops the full unroll over m in the (ff|ff) class)
+                    o[dir] -= og.dirn;
+                    if (o[dir] < 0) continue;
+                    const double coef = og.dirn >= 0 ? 1.0 : -(double)o[dir];
                     const size_t ia = ca0 + cart_index(la, o[0], o[2]);
                     double f;
                     if (og.gmode == 0) {

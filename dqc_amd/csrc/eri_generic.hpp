@@ -305,15 +305,11 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
 #pragma unroll
                     for (int dir = 0; dir < 3; dir++) {
                         int o[3] = {u[0], u[1], u[2]};
-                        double coef;
-                        if (og.dirn > 0) {
-                            if (o[dir] == 0) continue;
-                            o[dir]--;
-                            coef = 1.0;
-                        } else {
-                            coef = -(o[dir] + 1.0);
-                            o[dir]++;
-                        }
+                        // up: one power down, coefficient 1; down: one power up, coefficient -(power + 1); basis-parameter companions: dirn = 2, two
+                        // powers down, or 0, the component itself (branch-free: a longer body stops the full unroll over m in the (ff|ff) class)
+                        o[dir] -= og.dirn;
+                        if (o[dir] < 0) continue;
+                        const double coef = og.dirn >= 0 ? 1.0 : -(double)o[dir];
                         const size_t ia = ca0 + cart_index(lorig, o[0], o[2]);
                         double f;
                         if (og.gmode == 0)

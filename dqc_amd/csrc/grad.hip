@@ -14,6 +14,9 @@
 // (D_cart = T^T D T, T = dqc_cart2sph_matrix), so no solid-harmonic transform is needed on the device.
 // Supported: shells up to g (companions up to h: the classes with a g shell or an h companion run through the runtime
 // kernel of eri_generic.hpp).
+// The same two contractions by the BASIS parameters of every primitive p (exponent alpha_p, stored coefficient c_p) instead of the
+// centres: dqc_eri_grad_basis / dqc_int1e_grad_basis, with d a / d c_p = g_p and d a / d alpha_p = -c_p r_A^2 g_p (an l + 2 shell) as
+// per-primitive uncontracted companions.  Orbital shells up to f there (f + 2 = h).
 #include "eri_generic.hpp"
 
 namespace dqc {
@@ -340,6 +343,129 @@ __global__ __launch_bounds__(64) void int1e_grad_kernel(double *__restrict__ gra
 }
 
 // ---------------------------------------------------------------------------------------------
+// basis-parameter derivatives, one-electron part: one thread per ORDERED shell pair (a, b), derivative on a's primitives.
+// d a / d c_p = g_p (the primitive alone), d a / d alpha_p = -c_p r_A^2 g_p = -c_p sum_d g_p[power of d raised by 2]: the same
+// 1-D tables as int1e_grad_kernel with the bra index reaching l + 2.  Orbital shells up to f (the host refuses more).
+// ---------------------------------------------------------------------------------------------
+static_assert(G1 >= GRAD_LMAX + 3 && G3 >= GRAD_LMAX + 3, "1-D overlap tables: bra index l + 2, ket index l + 2 for f shells");
+
+template <int N>
+DQC_DEV void nuc_basis_accumulate(double &vc, double &va, int la, int lb, double p, const double *P, const double *A,
+                                  const double *AB, const double *C, double pref, const double *dblk, size_t nc) {
+    // vc += pref sum_{ca,cb} D[ca][cb] (ca | 1/|r - C| | cb),  va += the same with r_A^2 ca in the bra (pref carries -Z, c_b, K, 2 pi / p)
+    const double X = p * ((P[0] - C[0]) * (P[0] - C[0]) + (P[1] - C[1]) * (P[1] - C[1]) + (P[2] - C[2]) * (P[2] - C[2]));
+    double u[N], w[N];
+    rys_roots<N>(X, u, w);
+    for (int r = 0; r < N; r++) {
+        double g[3][2 * DQC_LMAX + 2][G1];  // first index up to la + 2 + lb <= 2 GRAD_LMAX + 2
+        const double b10 = 0.5 * (1.0 - u[r]) / p;
+        for (int d = 0; d < 3; d++) {
+            const double c00 = (P[d] - A[d]) - u[r] * (P[d] - C[d]);
+            g[d][0][0] = 1.0;
+            g[d][1][0] = c00;
+            for (int n = 1; n < la + 2 + lb; n++) g[d][n + 1][0] = c00 * g[d][n][0] + n * b10 * g[d][n - 1][0];
+            for (int j = 1; j <= lb; j++)
+                for (int i = 0; i <= la + 2 + lb - j; i++) g[d][i][j] = g[d][i + 1][j - 1] + AB[d] * g[d][i][j - 1];
+        }
+        double s0 = 0.0, s2 = 0.0;
+        int ca = 0;
+        for (int ax = la; ax >= 0; ax--)
+            for (int ay = la - ax; ay >= 0; ay--, ca++) {
+                const int az = la - ax - ay;
+                int cb = 0;
+                for (int bx = lb; bx >= 0; bx--)
+                    for (int by = lb - bx; by >= 0; by--, cb++) {
+                        const int bz = lb - bx - by;
+                        const double dd = dblk[ca * nc + cb];
+                        const double gx = g[0][ax][bx], gy = g[1][ay][by], gz = g[2][az][bz];
+                        s0 += dd * gx * gy * gz;
+                        s2 += dd * (g[0][ax + 2][bx] * gy * gz + gx * g[1][ay + 2][by] * gz + gx * gy * g[2][az + 2][bz]);
+                    }
+            }
+        vc += pref * w[r] * s0;
+        va += pref * w[r] * s2;
+    }
+}
+
+__global__ __launch_bounds__(64) void int1e_grad_basis_kernel(double *__restrict__ out, DevShells sh, const int *__restrict__ cao,
+                                  const double *__restrict__ dcart, const double *__restrict__ wcart, int ncart, int natm,
+                                  const double *__restrict__ atom_xyz, const double *__restrict__ atom_z) {
+    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pair >= sh.nsh * sh.nsh) return;
+    const int ish = pair / sh.nsh, jsh = pair % sh.nsh;
+    const int la = sh.l[ish], lb = sh.l[jsh];
+    const size_t nc = ncart;
+    const double A[3] = {sh.xyz[ish * 3], sh.xyz[ish * 3 + 1], sh.xyz[ish * 3 + 2]};
+    const double B[3] = {sh.xyz[jsh * 3], sh.xyz[jsh * 3 + 1], sh.xyz[jsh * 3 + 2]};
+    const double AB[3] = {A[0] - B[0], A[1] - B[1], A[2] - B[2]};
+    const double ab2 = AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2];
+    const double *dblk = dcart + (size_t)cao[ish] * nc + cao[jsh];
+    const double *wblk = wcart + (size_t)cao[ish] * nc + cao[jsh];
+    const int nroots = (la + 2 + lb) / 2 + 1;
+    for (int ip = 0; ip < sh.nprim[ish]; ip++) {
+        const double a = sh.exps[sh.prim_off[ish] + ip];
+        double vc = 0.0, va = 0.0;  // sum_b [D (g_p|T + V|b) - W (g_p|b)] and the same with r_A^2 g_p
+        for (int jp = 0; jp < sh.nprim[jsh]; jp++) {
+            const double b = sh.exps[sh.prim_off[jsh] + jp];
+            const double p = a + b, hp = 0.5 / p;
+            const double cK = sh.coefs[sh.prim_off[jsh] + jp] * exp(-a * b / p * ab2);
+            double P[3];
+            for (int d = 0; d < 3; d++) P[d] = (a * A[d] + b * B[d]) / p;
+            if (blockIdx.y == 0) {  // ---- overlap and kinetic (the nuclei are split over grid.y as in int1e_grad_kernel)
+                double s[3][G1][G3];
+                for (int d = 0; d < 3; d++) overlap_1d_g(s[d], la + 2, lb + 2, P[d] - A[d], P[d] - B[d], hp);
+                const double pref = cK * pow(M_PI / p, 1.5);
+                auto tt = [&](int d, int i, int j) {  // -1/2 d2/dx2 on the ket index, 1D
+                    return -2.0 * b * b * s[d][i][j + 2] + b * (2 * j + 1) * s[d][i][j] - (j >= 2 ? 0.5 * j * (j - 1) * s[d][i][j - 2] : 0.0);
+                };
+                int ca = 0;
+                for (int ax = la; ax >= 0; ax--)
+                    for (int ay = la - ax; ay >= 0; ay--, ca++) {
+                        const int av[3] = {ax, ay, la - ax - ay};
+                        int cb = 0;
+                        for (int bx = lb; bx >= 0; bx--)
+                            for (int by = lb - bx; by >= 0; by--, cb++) {
+                                const int bv[3] = {bx, by, lb - bx - by};
+                                double sv[3], tv[3], s2[3], t2[3];
+                                for (int d = 0; d < 3; d++) {
+                                    sv[d] = s[d][av[d]][bv[d]];
+                                    tv[d] = tt(d, av[d], bv[d]);
+                                    s2[d] = s[d][av[d] + 2][bv[d]];
+                                    t2[d] = tt(d, av[d] + 2, bv[d]);
+                                }
+                                const double S0 = sv[0] * sv[1] * sv[2];
+                                const double T0 = tv[0] * sv[1] * sv[2] + sv[0] * tv[1] * sv[2] + sv[0] * sv[1] * tv[2];
+                                double S2 = 0.0, T2 = 0.0;
+                                for (int d = 0; d < 3; d++) {
+                                    const int e = (d + 1) % 3, f = (d + 2) % 3;
+                                    S2 += s2[d] * sv[e] * sv[f];
+                                    T2 += t2[d] * sv[e] * sv[f] + s2[d] * (tv[e] * sv[f] + sv[e] * tv[f]);
+                                }
+                                const double dd = pref * dblk[ca * nc + cb], ww = pref * wblk[ca * nc + cb];
+                                vc += dd * T0 - ww * S0;
+                                va += dd * T2 - ww * S2;
+                            }
+                    }
+            }
+            // ---- nuclear attraction, nucleus by nucleus
+            for (int ic = blockIdx.y; ic < natm; ic += gridDim.y) {
+                const double prn = -atom_z[ic] * cK * 2.0 * M_PI / p;
+                const double *C = atom_xyz + ic * 3;
+                switch (nroots) {
+                case 2: nuc_basis_accumulate<2>(vc, va, la, lb, p, P, A, AB, C, prn, dblk, nc); break;
+                case 3: nuc_basis_accumulate<3>(vc, va, la, lb, p, P, A, AB, C, prn, dblk, nc); break;
+                case 4: nuc_basis_accumulate<4>(vc, va, la, lb, p, P, A, AB, C, prn, dblk, nc); break;
+                default: nuc_basis_accumulate<5>(vc, va, la, lb, p, P, A, AB, C, prn, dblk, nc); break;
+                }
+            }
+        }
+        const size_t row = sh.prim_off[ish] + ip;  // (the primitives of the table in shell order: parse_basis)
+        atomicAdd(&out[row * 2], -2.0 * sh.coefs[row] * va);
+        atomicAdd(&out[row * 2 + 1], 2.0 * vc);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // electronic electrostatic potential at points: V_C = sum_ab D_ab <a| 1/|r - P_C| |b>  (the alchemical derivative
 // dE/dZ_C = -V_C + ...; the Rys quadrature of the nuclear attraction, contracted with D on the fly)
 // ---------------------------------------------------------------------------------------------
@@ -600,6 +726,140 @@ int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart,
     const int npair = nbas * nbas;
     hipLaunchKernelGGL(int1e_grad_kernel, dim3((npair + 63) / 64, natm < 32 ? natm : 32), dim3(64), 0, st, d_grad, ds, d_cao, d_atom, d_dcart, d_wcart,
                        ncart, natm, d_xyz, d_z);
+    DQC_CHECK_LAUNCH();
+    DQC_HIP(hipStreamSynchronize(st));
+    return DQC_OK;
+}
+
+// orbital shells up to f: the alpha derivative needs the l + 2 shell, and h is the highest the Rys kernels reach
+static int basis_grad_lcheck(const dqc::Basis &b, const char *who) {
+    for (const dqc::HostShell &h : b.shells)
+        if (h.l > dqc::GRAD_LMAX) {
+            dqc::set_error((std::string(who) + ": basis-parameter derivatives support orbital shells up to f (a g shell needs l + 2 = i integrals)").c_str());
+            return DQC_EINVAL;
+        }
+    return 0;
+}
+
+int dqc_eri_grad_basis(double *d_out, const double *d_dcart, double jscale, double kscale, const int *atm, int natm, const int *bas,
+                       int nbas, const double *env, int nenv, void *stream) {
+    // d_out (nprim_total, 2) += sum_{a has p} sum_bcd (d_theta a b|c d) [2 jscale D_ab D_cd - kscale D_ac D_bd], theta = alpha_p
+    // (column 0) or c_p (column 1) of every primitive p in table order; d_dcart (ncart, ncart)
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    Basis b;
+    int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, nullptr);
+    if (rc) return rc;
+    if (nbas == 0) return DQC_OK;
+    if ((rc = basis_grad_lcheck(b, "dqc_eri_grad_basis"))) return rc;
+    const int N = nbas, P = (int)b.exps.size();
+    std::vector<int> cao, rows(N + 2 * P, 0);
+    int ncart;
+    cart_offsets(b, N, cao, ncart);
+    cao.resize(N + 2 * P);
+    // per-primitive companion shells, uncontracted: [N, N + P) the primitive itself (l, coefficient 1),
+    // [N + P, N + 2P) its r_A^2 multiple (l + 2, coefficient -c_p).  The GRAD epilogue (eri_core.hpp, dirn 0 / 2) looks both maps up
+    // by the companion shell itself: cao = the Cartesian offset of its original shell, rows = its row of the partial sums
+    // (2P rows of 3 "directions": row p the same sum three times, row P + p the three raised powers)
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < N; i++)
+            for (int p = 0; p < b.shells[i].nprim; p++) {
+                HostShell h = b.shells[i];
+                const int row = b.shells[i].prim_off + p, comp = N + pass * P + row;
+                cao[comp] = cao[i];
+                rows[comp] = pass * P + row;
+                h.l += 2 * pass;
+                h.nprim = 1;
+                h.prim_off = (int)b.exps.size();
+                b.exps.push_back(b.exps[row]);
+                b.coefs.push_back(pass == 0 ? 1.0 : -b.coefs[row]);
+                b.shells.push_back(h);
+            }
+    HostPairs hsame, hup2, hket;
+    build_pairs_ordered(b, hsame, N, N + P, 0, N);
+    build_pairs_ordered(b, hup2, N + P, N + 2 * P, 0, N);
+    build_pairs(b, hket, 0, N);
+    if ((rc = boys_table_ensure())) return rc;
+    DevPool pool;
+    GradCtx c;
+    if ((rc = upload_shells(c.ds, b, pool, st))) { set_error("dqc_eri_grad_basis: device upload failed"); return rc; }
+    auto up = [&](HostPairs &hp, DevPairs &dp) {
+        int *d_sh = nullptr, *d_off = nullptr;
+        double *d_pp = nullptr;
+        int r;
+        if ((r = pool.upload(&d_sh, hp.sh, st)) || (r = pool.upload(&d_off, hp.pp_off, st)) || (r = pool.upload(&d_pp, hp.pp, st)))
+            return r;
+        dp = DevPairs{d_sh, d_off, d_pp};
+        return 0;
+    };
+    DevPairs dsame, dup2, dket;
+    int *d_cao = nullptr, *d_rows = nullptr;
+    if ((rc = up(hsame, dsame)) || (rc = up(hup2, dup2)) || (rc = up(hket, dket)) || (rc = pool.upload(&d_cao, cao, st)) ||
+        (rc = pool.upload(&d_rows, rows, st))) {
+        set_error("dqc_eri_grad_basis: device upload failed");
+        return rc;
+    }
+    const int nslot = 64, nrow = 2 * P;
+    const size_t npart = (size_t)nslot * nrow * 3;
+    double *d_part = nullptr;
+    if (hipMalloc((void **)&d_part, sizeof(double) * npart) != hipSuccess) { set_error("dqc_eri_grad_basis: out of memory"); return DQC_ENOMEM; }
+    pool.ptrs.push_back(d_part);
+    DQC_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * npart, st));
+    c.dket = dket;
+    c.hket = &hket;
+    c.og = EriOut{0, 0, 0, 0};
+    c.og.dcart = d_dcart; c.og.ncart = ncart; c.og.cao = d_cao; c.og.sh_atom = d_rows; c.og.gpart = d_part;
+    c.og.nslot = nslot; c.og.natm = nrow; c.og.norig = N + 2 * P; c.og.jscale = jscale; c.og.kscale = kscale;
+    SideJoin sj;  // (declared after the scratch pools of this call: destroyed, i.e. joined, before they are released)
+    if ((c.side = side_streams()) != nullptr && (rc = c.side->fork(st))) { set_error("dqc_eri_grad_basis: stream fork failed"); return rc; }
+    sj.arm(c.side, st);
+    c.dbra = dsame; c.hbra = &hsame; c.og.dirn = 0;
+    if ((rc = launch_grad_all(c, st))) return rc;
+    c.dbra = dup2; c.hbra = &hup2; c.og.dirn = 2;
+    if ((rc = launch_grad_all(c, st))) return rc;
+    if ((rc = sj.done())) { set_error("dqc_eri_grad_basis: stream join failed"); return rc; }
+    // fold the slots into d_out on the host side of the stream: tiny
+    std::vector<double> part(npart), g((size_t)P * 2);
+    DQC_HIP(hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
+    DQC_HIP(hipMemcpyAsync(g.data(), d_out, sizeof(double) * g.size(), hipMemcpyDeviceToHost, st));
+    DQC_HIP(hipStreamSynchronize(st));
+    for (int sidx = 0; sidx < nslot; sidx++)
+        for (int p = 0; p < P; p++) {
+            const double *same = &part[((size_t)sidx * nrow + p) * 3], *up2 = &part[((size_t)sidx * nrow + P + p) * 3];
+            g[(size_t)p * 2] += up2[0] + up2[1] + up2[2];
+            g[(size_t)p * 2 + 1] += same[0];
+        }
+    DQC_HIP(hipMemcpyAsync(d_out, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice, st));
+    DQC_HIP(hipStreamSynchronize(st));
+    return DQC_OK;
+}
+
+int dqc_int1e_grad_basis(double *d_out, const double *d_dcart, const double *d_wcart, const int *atm, int natm, const int *bas,
+                         int nbas, const double *env, int nenv, const double *zs, void *stream) {
+    // d_out (nprim_total, 2) += 2 sum_{a has p} sum_b [D_ab (d_theta a|T + V|b) - W_ab (d_theta a|b)], theta = alpha_p (column 0) or
+    // c_p (column 1); d_dcart / d_wcart: Cartesian-basis density and energy-weighted density (ncart, ncart)
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    Basis b;
+    int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, zs);
+    if (rc) return rc;
+    if (nbas == 0) return DQC_OK;
+    if ((rc = basis_grad_lcheck(b, "dqc_int1e_grad_basis"))) return rc;
+    std::vector<int> cao;
+    int ncart;
+    cart_offsets(b, nbas, cao, ncart);
+    DevPool pool;
+    DevShells ds;
+    if ((rc = upload_shells(ds, b, pool, st))) { set_error("dqc_int1e_grad_basis: device upload failed"); return rc; }
+    double *d_xyz = nullptr, *d_z = nullptr;
+    int *d_cao = nullptr;
+    if ((rc = pool.upload(&d_xyz, b.atom_xyz, st)) || (rc = pool.upload(&d_z, b.atom_z, st)) || (rc = pool.upload(&d_cao, cao, st))) {
+        set_error("dqc_int1e_grad_basis: device upload failed");
+        return rc;
+    }
+    const int npair = nbas * nbas;
+    hipLaunchKernelGGL(int1e_grad_basis_kernel, dim3((npair + 63) / 64, natm < 32 ? natm : 32), dim3(64), 0, st, d_out, ds, d_cao, d_dcart,
+                       d_wcart, ncart, natm, d_xyz, d_z);
     DQC_CHECK_LAUNCH();
     DQC_HIP(hipStreamSynchronize(st));
     return DQC_OK;

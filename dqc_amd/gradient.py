@@ -50,6 +50,25 @@ def nuclear_gradient(qc) -> torch.Tensor:
         raise NotImplementedError("nuclear gradients with fitted exchange (densityfit(exchange=True)) are not implemented: the K "
                                   "term needs the derivative three-index integrals contracted with a three-index density, "
                                   "which is not built")
+    d_aos, d_tot, w_ao = _pulay_densities(qc)
+    T = lib.cart2sph_matrix(h._tab, dev)                                        # (nao, ncart)
+    tocart = lambda m: (T.T @ m @ T).contiguous()  # noqa: E731
+    natm = len(mol.atomzs)
+    grad = torch.zeros((natm, 3), dtype=torch.float64, device=dev)
+    lib.int1e_grad(grad, tocart(d_tot), tocart(w_ao), h._tab, h._zs)
+    if h.df is not None:
+        _df_coulomb_gradient(h, d_tot, grad)
+    else:
+        _two_electron_terms(lib.eri_grad, eng, grad, d_tot, d_aos, tocart, h._tab)
+    if eng.is_ks:
+        grad = grad + _xc_gradient(eng, d_aos)
+    return grad + _nuclei_gradient(mol).to(dev)
+
+
+def _pulay_densities(qc):
+    """([D_s], D, W): the symmetrised AO densities spin by spin, their sum and the energy-weighted density of a converged run"""
+    eng = qc._engine
+    h = eng.hamilton
     X = h._orthozer
     pol = eng.polarized
     dms = [qc._dm.u, qc._dm.d] if pol else [qc._dm]
@@ -76,34 +95,150 @@ def nuclear_gradient(qc) -> torch.Tensor:
             w_ao = w_ao + X @ ((Cocc * (w * eps[:n]).unsqueeze(0)) @ Cocc.T) @ X.T     # energy-weighted density
         d = X @ dm @ X.T
         d_aos.append((d + d.T) * 0.5)
-    d_tot = sum(d_aos)
-    T = lib.cart2sph_matrix(h._tab, dev)                                        # (nao, ncart)
-    tocart = lambda m: (T.T @ m @ T).contiguous()  # noqa: E731
-    natm = len(mol.atomzs)
-    grad = torch.zeros((natm, 3), dtype=torch.float64, device=dev)
-    lib.int1e_grad(grad, tocart(d_tot), tocart(w_ao), h._tab, h._zs)
-    if h.df is not None:
-        _df_coulomb_gradient(h, d_tot, grad)
-    elif eng.is_ks and getattr(eng, "exx", 0.0) != 0.0:
+    return d_aos, sum(d_aos), w_ao
+
+
+def _two_electron_terms(contract, eng, out, d_tot, d_aos, tocart, tab):
+    """the j / k cases of the exact two-electron term; contract = lib.eri_grad (out (natm, 3)) or lib.eri_grad_basis (out
+    (nprim, 2)): out += sum (d a b|c d) [2 j D_ab D_cd - k D_ac D_bd]"""
+    pol = eng.polarized
+    if eng.is_ks and getattr(eng, "exx", 0.0) != 0.0:
         # hybrid functional, exact-exchange fraction a: the Hartree-Fock two-electron term with the exchange scaled by a
         a = float(eng.exx)
         if not pol:
-            lib.eri_grad(grad, tocart(d_tot), a, h._tab)
+            contract(out, tocart(d_tot), a, tab)
         else:  # J from the total density, -a K[D_s] spin by spin
-            lib.eri_grad(grad, tocart(d_tot), 0.0, h._tab)
+            contract(out, tocart(d_tot), 0.0, tab)
             for d in d_aos:
-                lib.eri_grad(grad, tocart(d), 2.0 * a, h._tab, jscale=0.0)
+                contract(out, tocart(d), 2.0 * a, tab, jscale=0.0)
     elif eng.is_ks:
-        lib.eri_grad(grad, tocart(d_tot), 0.0, h._tab)
+        contract(out, tocart(d_tot), 0.0, tab)
     elif not pol:
-        lib.eri_grad(grad, tocart(d_tot), 1.0, h._tab)
+        contract(out, tocart(d_tot), 1.0, tab)
     else:  # UHF: J from the total density, -K[D_s] spin by spin  (E_K = -1/2 sum_s sum D^s_ac D^s_bd (ab|cd))
-        lib.eri_grad(grad, tocart(d_tot), 0.0, h._tab)
+        contract(out, tocart(d_tot), 0.0, tab)
         for d in d_aos:
-            lib.eri_grad(grad, tocart(d), 2.0, h._tab, jscale=0.0)
+            contract(out, tocart(d), 2.0, tab, jscale=0.0)
+
+
+def basis_gradient(qc) -> torch.Tensor:
+    """qc: a converged dqc_amd.HF / dqc_amd.KS.  Returns dE/d(basis parameters), shape (nprim_total, 2): one row per primitive of
+    the Hamiltonian's table (dqc_amd.basis.make_tables order, shell by shell), column 0 by the exponent alpha_p, column 1 by the
+    stored, normalised coefficient c_p.  The Pulay expression of nuclear_gradient with d/dR_A replaced by d/dtheta:
+
+        dE/dtheta = 2 sum_{a has p} sum_b [D_ab (d_theta a|T+V|b) - W_ab (d_theta a|b)]       -> dqc_int1e_grad_basis
+                  +   sum_{a has p} sum_bcd (d_theta a b|c d) [2 j D_ab D_cd - k D_ac D_bd]   -> dqc_eri_grad_basis
+                  +   dE_xc/dtheta at fixed AO density                                        -> _xc_basis_gradient
+
+    (no operator, Becke-weight or E_nn term: neither the nuclei nor the grid depend on the basis).  Orbital shells up to f."""
+    from .basis import primitive_rows
+    eng = qc._engine
+    h = eng.hamilton
+    dev = h.device
+    if h.df is not None:
+        raise NotImplementedError("basis-parameter gradients of a density-fitted Hamiltonian are not implemented: the fitted "
+                                  "Coulomb / exchange energies need the derivative three-index integrals by exponent and coefficient")
+    if getattr(h, "sharded", False):
+        raise NotImplementedError("basis-parameter gradients of a Hamiltonian sharded over several GPUs (shard_over) are not "
+                                  "implemented: the XC term needs the whole grid")
+    ef = getattr(h, "_efield", None)
+    if ef is not None and any(bool((e != 0).any()) for e in ef):
+        raise NotImplementedError("basis-parameter gradients in a non-zero electric field are not implemented (multipole integrals "
+                                  "differentiated by exponent and coefficient)")
+    if h._vext is not None:
+        raise NotImplementedError("basis-parameter gradients with an external potential are not implemented: the vext term "
+                                  "(sum_g w vext d rho / d theta) is missing from dqc_amd.gradient")
+    if int(h._tab.bas[:, 1].max()) > 3:
+        raise NotImplementedError("basis-parameter gradients support orbital shells up to f: the exponent derivative of a g shell "
+                                  "is an l + 2 = i shell, above the h limit of the integral kernels")
+    if eng.is_ks and h.xcfamily >= 4:
+        raise NotImplementedError("basis-parameter gradients of meta-GGA functionals are not implemented (the tau term of dE_xc/dtheta)")
+    d_aos, d_tot, w_ao = _pulay_densities(qc)
+    T = lib.cart2sph_matrix(h._tab, dev)                                        # (nao, ncart)
+    tocart = lambda m: (T.T @ m @ T).contiguous()  # noqa: E731
+    nprim = primitive_rows(h._tab.bas)[0].shape[0]
+    out = torch.zeros((nprim, 2), dtype=torch.float64, device=dev)
+    lib.int1e_grad_basis(out, tocart(d_tot), tocart(w_ao), h._tab, h._zs)
+    _two_electron_terms(lib.eri_grad_basis, eng, out, d_tot, d_aos, tocart, h._tab)
     if eng.is_ks:
-        grad = grad + _xc_gradient(eng, d_aos)
-    return grad + _nuclei_gradient(mol).to(dev)
+        out = out + _xc_basis_gradient(h, d_aos)
+    return out
+
+
+_XC_BASIS_CHUNK = 1 << 16  # grid points per pass of _xc_basis_gradient (bounds the per-primitive AO arrays)
+
+
+def _xc_basis_gradient(h, d_aos):
+    """dE_xc/dtheta_p = 2 sum_g w sum_{mu in shell(p)} [chi_mu (v_rho b_mu + u . c_mu) + b_mu u . grad chi_mu],  chi = d_theta phi_mu,
+    at fixed AO density (b, c, u, v_rho as in _xc_gradient; LDA: u = 0); LDA and GGA, spin by spin.  chi comes from dqc_eval_gto on
+    the table that lists every primitive as its own shell (dqc_amd.basis.companion_tables):
+        chi_c = phi_prim,    chi_alpha = -c_p r_A^2 phi_prim,    grad chi_alpha = -c_p (2 (r - A) phi_prim + r_A^2 grad phi_prim)."""
+    from .basis import companion_tables, primitive_rows
+    from .utils.datastruct import ValGrad
+    dev = h.device
+    nao, ld = h._nao_ao, h._ld
+    gga = h.xcfamily >= 2
+    tab = h._tab
+    prim_shell, _ = primitive_rows(tab.bas)
+    nprim = prim_shell.shape[0]
+    catm, cbas, cenv = companion_tables(tab.atm, tab.bas, tab.env)
+    ptab = lib.Tables(catm, cbas[:nprim], cenv)                               # the primitives themselves (same l, coefficient 1)
+    ao_off = [0]
+    for b in tab.bas:
+        ao_off.append(ao_off[-1] + 2 * int(b[1]) + 1)
+    col_ao, col_prim, col_atom = [], [], []  # per column of the primitive table: the AO it belongs to, its primitive, its atom
+    for p, ish in enumerate(prim_shell.tolist()):
+        ns = 2 * int(tab.bas[ish, 1]) + 1
+        col_ao.extend(range(ao_off[ish], ao_off[ish] + ns))
+        col_prim.extend([p] * ns)
+        col_atom.extend([int(tab.bas[ish, 0])] * ns)
+    col_ao, col_prim, col_atom = (torch.tensor(x, device=dev) for x in (col_ao, col_prim, col_atom))
+    ncol = col_ao.numel()
+    coef = torch.as_tensor([tab.env[int(tab.bas[ish, 6]) + k] for ish in range(tab.nbas) for k in range(int(tab.bas[ish, 2]))],
+                           dtype=torch.float64, device=dev)
+    pos = torch.as_tensor(tab.env[tab.atm[:, 1, None] + [0, 1, 2]], dtype=torch.float64, device=dev)          # (natm, 3)
+    dpads = [lib.pad_matrix(d, ld) for d in d_aos]
+    col_c = torch.zeros(ncol, dtype=torch.float64, device=dev)
+    col_a = torch.zeros(ncol, dtype=torch.float64, device=dev)
+    for g0 in range(0, h.rgrid.shape[0], _XC_BASIS_CHUNK):
+        pts = h.rgrid[g0:g0 + _XC_BASIS_CHUNK].contiguous()
+        w = h.dvolume[g0:g0 + _XC_BASIS_CHUNK]
+        ao = lib.eval_gto(tab, pts, 1)                                         # (4, n, lda)
+        lda = ao.shape[-1]
+        infos, bs, cs_ = [], [], []
+        for dp in dpads:
+            rho_s, grho_s = lib.grid_density(ao, nao, dp, True)
+            dq = dp[:lda, :lda]
+            bs.append(ao[0] @ dq)
+            cs_.append([ao[1 + i] @ dq for i in range(3)] if gga else None)
+            infos.append(ValGrad(value=rho_s, grad=grho_s if gga else None))
+        dens = infos[0] if len(infos) == 1 else SpinParam(u=infos[0], d=infos[1])
+        pot = h.xc.get_vxc(dens)
+        pots = [pot] if len(infos) == 1 else [pot.u, pot.d]
+        pao = lib.eval_gto(ptab, pts, 1 if gga else 0)
+        phi = (pao[0] if gga else pao)[:, :ncol]                               # (n, ncol) primitive AOs
+        dvec = pts.unsqueeze(1) - pos.unsqueeze(0)                             # (n, natm, 3)  r - A
+        r2 = (dvec * dvec).sum(-1)[:, col_atom]                                # (n, ncol)  r_A^2
+        for b, c, pt in zip(bs, cs_, pots):
+            vrho, u = pt.value, pt.grad
+            t1 = vrho.unsqueeze(-1) * b
+            if gga:
+                t1 = t1 + sum(u[i].unsqueeze(-1) * c[i] for i in range(3))
+            e = phi * t1[:, col_ao]
+            if gga:
+                bcol = b[:, col_ao]
+                e = e + bcol * sum(u[i].unsqueeze(-1) * pao[1 + i][:, :ncol] for i in range(3))
+            col_c += w @ e
+            ea = r2 * e
+            if gga:
+                ud = torch.einsum("ig,gai->ga", u, dvec)[:, col_atom]          # u . (r - A)
+                ea = ea + 2.0 * bcol * ud * phi
+            col_a += w @ ea
+    out = torch.zeros((nprim, 2), dtype=torch.float64, device=dev)
+    out[:, 1].index_add_(0, col_prim, 2.0 * col_c)
+    out[:, 0].index_add_(0, col_prim, 2.0 * col_a)
+    out[:, 0] *= -coef
+    return out
 
 
 def _df_coulomb_gradient(h, d_ao, grad):

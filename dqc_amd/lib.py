@@ -80,6 +80,8 @@ def load():
     lib.dqc_cart2sph_matrix.argtypes = [dp, ip, c_int]
     lib.dqc_int1e_grad.argtypes = [c_dp, c_dp, c_dp] + tab + [dp, c_vp]
     lib.dqc_eri_grad.argtypes = [c_dp, c_dp, ctypes.c_double, ctypes.c_double] + tab + [c_vp]
+    lib.dqc_int1e_grad_basis.argtypes = [c_dp, c_dp, c_dp] + tab + [dp, c_vp]
+    lib.dqc_eri_grad_basis.argtypes = [c_dp, c_dp, ctypes.c_double, ctypes.c_double] + tab + [c_vp]
     lib.dqc_int1e_potential.argtypes = [c_dp, c_dp, c_dp, c_int] + tab + [c_vp]
     lib.dqc_df_grad.argtypes = [c_dp, c_dp, c_dp] + tab + [c_int, c_int, c_int, c_int, c_vp]
     lib.dqc_becke_weights.argtypes = [c_dp, c_dp, c_vp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.c_double, c_vp]
@@ -433,6 +435,41 @@ def eri_grad(grad, dcart, kscale, tab, jscale=1.0):
     with _on(grad.device) as st_:
         _check(load().dqc_eri_grad(_ptr(grad), _ptr(dcart), float(jscale), float(kscale), *tab.args(), st_), "dqc_eri_grad")
     return grad
+
+
+def _check_basis_grad(who, out, mats, tab):
+    """out (nprim_total, 2) and the (ncart, ncart) matrices: float64, contiguous, on one device; orbital shells up to f"""
+    nprim = int(tab.bas[:, 2].sum())
+    ncart = int(((tab.bas[:, 1] + 1) * (tab.bas[:, 1] + 2) // 2).sum())
+    if tab.nbas and int(tab.bas[:, 1].max()) > 3:
+        raise NotImplementedError("%s: basis-parameter derivatives support orbital shells up to f (the exponent derivative of a "
+                                  "g shell needs l + 2 = i integrals)" % who)
+    if tuple(out.shape) != (nprim, 2) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise DqcAmdError("%s: out must be a contiguous float64 (%d, 2) tensor, got %s" % (who, nprim, tuple(out.shape)))
+    for m in mats:
+        if tuple(m.shape) != (ncart, ncart) or m.dtype != torch.float64 or not m.is_contiguous() or m.device != out.device:
+            raise DqcAmdError("%s: the Cartesian matrices must be contiguous float64 (%d, %d) tensors on the device of out, got %s"
+                              % (who, ncart, ncart, tuple(m.shape)))
+
+
+def int1e_grad_basis(out, dcart, wcart, tab, zs=None):
+    """out (nprim_total, 2) += one-electron Pulay terms by every primitive's exponent (column 0) and coefficient (column 1)"""
+    _check_basis_grad("int1e_grad_basis", out, (dcart, wcart), tab)
+    zp = None
+    if zs is not None:
+        zs = np.ascontiguousarray(zs, dtype=np.float64)
+        zp = zs.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    with _on(out.device) as st_:
+        _check(load().dqc_int1e_grad_basis(_ptr(out), _ptr(dcart), _ptr(wcart), *tab.args(), zp, st_), "dqc_int1e_grad_basis")
+    return out
+
+
+def eri_grad_basis(out, dcart, kscale, tab, jscale=1.0):
+    """out (nprim_total, 2) += sum (d_theta a b|c d) [2 jscale D_ab D_cd - kscale D_ac D_bd], theta = alpha_p, c_p"""
+    _check_basis_grad("eri_grad_basis", out, (dcart,), tab)
+    with _on(out.device) as st_:
+        _check(load().dqc_eri_grad_basis(_ptr(out), _ptr(dcart), float(jscale), float(kscale), *tab.args(), st_), "dqc_eri_grad_basis")
+    return out
 
 
 def becke_weights(xyz, atom_off, pos, inv_rij, aij, cut):

@@ -427,6 +427,16 @@ class SCF_QCCalc:
         from .gradient import nuclear_gradient
         return nuclear_gradient(self)
 
+    def basis_gradient(self):
+        """dE/d(exponent), dE/d(normalised coefficient) of every primitive of the basis table, (nprim_total, 2), of the converged
+        energy (dqc_amd/gradient.py); torch.autograd.grad(energy, CGTOBasis tensors) chains it to the caller's tensors"""
+        assert self._has_run
+        if not self.accepted:
+            warnings.warn("basis_gradient() of an unconverged SCF (max|[F,D]| = %.2e) is not the derivative of its energy"
+                          % self.scf_error)
+        from .gradient import basis_gradient
+        return basis_gradient(self)
+
     def dm2energy(self, dm):
         return self._engine.dm2energy(dm)
 

@@ -29,6 +29,13 @@ class Mol:
         atomzs, atompos = atomzs.detach(), atompos.detach()
         self._atomzs, self._atompos = atomzs, atompos
         self._atombases = make_atombases(atomzs, atompos, basis)
+        # the caller's exponents / coefficients of every shell in table order, before make_tables normalises the shells in place
+        # (a CGTOBasis an earlier Mol normalised still carries the tensor it was given)
+        self._basis_shells = [(sh.angmom, sh.alphas, getattr(sh, "_raw_coeffs", sh.coeffs), sh.normalized and not hasattr(sh, "_raw_coeffs"))
+                              for ab in self._atombases for sh in ab.bases]
+        bleaves = {id(t): t for _, a, c, _ in self._basis_shells for t in (a, c) if t.requires_grad}
+        if bleaves:
+            self._grad_leaves["basis"] = tuple(bleaves.values())
         self._user_weights = None
         if orb_weights is not None:
             # mol.py:143-167: explicit occupations (SpinParam of equally long 1-D tensors); electron count, spin and charge

@@ -28,6 +28,7 @@ class CGTOBasis:
         if self.normalized:
             return self
         l = self.angmom
+        self._raw_coeffs = self.coeffs  # (the caller's tensor: the energy's autograd node differentiates through this function)
         coeffs = self.coeffs / torch.sqrt(gaussian_int(2 * l + 2, 2 * self.alphas))
         ee = gaussian_int(2 * l + 2, self.alphas.unsqueeze(-1) + self.alphas.unsqueeze(-2))
         s1 = 1 / torch.sqrt(torch.einsum("a,ab,b", coeffs, ee, coeffs))

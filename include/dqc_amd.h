@@ -318,6 +318,18 @@ int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart,
                    const int *bas, int nbas, const double *env, int nenv, const double *zs, void *stream);
 int dqc_eri_grad(double *d_grad, const double *d_dcart, double jscale, double kscale, const int *atm, int natm, const int *bas,
                  int nbas, const double *env, int nenv, void *stream);
+/* the same two contractions differentiated by the BASIS-SET parameters instead of the centres: theta = the exponent alpha_p or
+ * the stored (normalised) coefficient c_p of one primitive.  For a shell a = sum_p c_p g_p:  d a / d c_p = g_p,
+ * d a / d alpha_p = -c_p r_A^2 g_p (an l + 2 Cartesian shell), so the Pulay terms are the same shell-pair and shell-quartet
+ * evaluations with per-primitive uncontracted companion shells first in the bra.  No operator, weight or E_nn term exists.
+ *   dqc_int1e_grad_basis: 2 sum_{a has p} sum_b [D_ab (d_theta a|T+V|b) - W_ab (d_theta a|b)]
+ *   dqc_eri_grad_basis  : sum_{a has p} sum_bcd (d_theta a b|c d) [2 jscale D_ab D_cd - kscale D_ac D_bd]
+ * Both ADD into d_out (nprim_total, 2) -- one row per primitive in table order, shell by shell; column 0 = d/d alpha,
+ * column 1 = d/d c -- and synchronise the stream.  Orbital shells up to f (l + 2 companions up to h); a g shell is DQC_EINVAL. */
+int dqc_int1e_grad_basis(double *d_out, const double *d_dcart, const double *d_wcart, const int *atm, int natm,
+                         const int *bas, int nbas, const double *env, int nenv, const double *zs, void *stream);
+int dqc_eri_grad_basis(double *d_out, const double *d_dcart, double jscale, double kscale, const int *atm, int natm, const int *bas,
+                       int nbas, const double *env, int nenv, void *stream);
 /* electronic electrostatic potential at npts device points (the alchemical derivative dE/dZ_C = -V_C + ...):
  *   d_out[C] = sum_ab D_ab <a| 1/|r - P_C| |b>,   d_points (npts, 3), d_out (npts,)
  * D in the CARTESIAN AO basis as for dqc_int1e_grad (D_cart = T^T D_ao T).  Contracted on the fly; per-block partials are
