@@ -34,29 +34,12 @@ static int df_setup(DfSetup &s, const int *atm, int natm, const int *bas, int nb
     s.og.nao = ao_of(sh1) - ao_of(sh0);
     s.og.aux0 = ao_of(k0);
     s.og.naux = ao_of(k1) - ao_of(k0);
-    // the unit shell
-    HostShell u;
-    u.atom = 0; u.l = 0; u.nprim = 1; u.ao_off = s.b.nao; u.prim_off = (int)s.b.exps.size();
-    u.r[0] = u.r[1] = u.r[2] = 0.0;
-    s.b.exps.push_back(0.0);
-    s.b.coefs.push_back(3.5449077018110320546);  // sqrt(4 pi)
-    s.b.shells.push_back(u);
-    const int unit = nbas;
+    const int unit = append_unit_shell(s.b, 3.5449077018110320546);  // sqrt(4 pi)
     if (need_orb) build_pairs(s.b, s.orb, sh0, sh1);
     build_pairs(s.b, s.aux, k0, k1, unit);
     if ((rc = upload_shells(s.ds, s.b, s.pool, st))) { set_error(std::string(who) + ": device upload failed"); return rc; }
-    auto up = [&](HostPairs &hp, DevPairs &dp) {
-        int *d_sh = nullptr, *d_off = nullptr;
-        double *d_pp = nullptr;
-        int r;
-        if ((r = s.pool.upload(&d_sh, hp.sh, st)) || (r = s.pool.upload(&d_off, hp.pp_off, st)) ||
-            (r = s.pool.upload(&d_pp, hp.pp, st)))
-            return r;
-        dp = DevPairs{d_sh, d_off, d_pp};
-        return 0;
-    };
-    if (need_orb && (rc = up(s.orb, s.dorb))) { set_error(std::string(who) + ": device upload failed"); return rc; }
-    if ((rc = up(s.aux, s.daux))) { set_error(std::string(who) + ": device upload failed"); return rc; }
+    if (need_orb && (rc = upload_pairs(s.pool, s.orb, s.dorb, st))) { set_error(std::string(who) + ": device upload failed"); return rc; }
+    if ((rc = upload_pairs(s.pool, s.aux, s.daux, st))) { set_error(std::string(who) + ": device upload failed"); return rc; }
     return 0;
 }
 

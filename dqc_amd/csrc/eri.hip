@@ -627,17 +627,16 @@ int dqc_jk_direct(double *d_J, double *d_K, const double *d_dm, const int *atm, 
     DevPool pool(st);
     DevShells ds;
     if ((rc = upload_shells(ds, bg, pool, st))) { set_error("dqc_jk_direct: device upload failed"); return rc; }
-    int *d_sh = nullptr, *d_off = nullptr;
-    double *d_pp = nullptr, *d_sym = nullptr, *d_a = nullptr, *d_b = nullptr;
+    DevPairs dp;
+    double *d_sym = nullptr, *d_a = nullptr, *d_b = nullptr;
     const size_t n2 = (size_t)b.nao * b.nao;
-    if ((rc = pool.upload(&d_sh, hp.sh, st)) || (rc = pool.upload(&d_off, hp.pp_off, st)) || (rc = pool.upload(&d_pp, hp.pp, st)) ||
-        (rc = pool.alloc(&d_sym, n2)) || (rc = pool.alloc(&d_a, n2)) || (d_K && (rc = pool.alloc(&d_b, n2)))) {
+    if ((rc = upload_pairs(pool, hp, dp, st)) || (rc = pool.alloc(&d_sym, n2)) || (rc = pool.alloc(&d_a, n2)) ||
+        (d_K && (rc = pool.alloc(&d_b, n2)))) {
         set_error("dqc_jk_direct: device allocation failed");
         return rc;
     }
     hipLaunchKernelGGL(jk_direct_prep_kernel, dim3(256), dim3(256), 0, st, d_sym, d_a, d_b, d_dm, b.nao);
     DQC_CHECK_LAUNCH();
-    DevPairs dp{d_sh, d_off, d_pp, hp.stride};
     EriOut og{b.nao, 0, 0, 0};
     og.dmat = d_sym;
     og.jacc = d_a;
@@ -675,15 +674,13 @@ int dqc_direct_create(void **ctx_out, const int *atm, int natm, const int *bas, 
     c->qm.assign(np * 4, 0.0);
     {   // Schwarz bounds from the unsorted tables (scratch of this block only): four slots per pair, one per member shell pair
         DevPool tmp;
-        int *d_sh = nullptr, *d_off = nullptr;
-        double *d_pp = nullptr, *d_q0 = nullptr;
-        if ((rc = tmp.upload(&d_sh, c->hp.sh, st)) || (rc = tmp.upload(&d_off, c->hp.pp_off, st)) || (rc = tmp.upload(&d_pp, c->hp.pp, st)) ||
-            (rc = tmp.alloc(&d_q0, np * 4))) {
+        DevPairs dp0;
+        double *d_q0 = nullptr;
+        if ((rc = upload_pairs(tmp, c->hp, dp0, st)) || (rc = tmp.alloc(&d_q0, np * 4))) {
             set_error("dqc_direct_create: device allocation failed");
             return rc;
         }
         DQC_HIP(hipMemsetAsync(d_q0, 0, sizeof(double) * np * 4, st));
-        DevPairs dp0{d_sh, d_off, d_pp, c->hp.stride};
         constexpr int NCLS = (ERI_LMAX + 1) * (ERI_LMAX + 2) / 2;
         if ((rc = ClassLoopSchwarz<NCLS - 1>::run(d_q0, c->ds, dp0, c->hp, st))) return rc;
         if ((rc = run_generic_classes<ERI_OUT_SCHWARZ>(d_q0, c->ds, dp0, c->hp, EriOut{0, 0, 0, 0}, st))) return rc;
@@ -698,22 +695,19 @@ int dqc_direct_create(void **ctx_out, const int *atm, int natm, const int *bas, 
         int slot[4], sa[4], sb[4];
         c->wpre[i + 1] = c->wpre[i] + group_pair_members(c->bg, c->hp.sh[2 * i], c->hp.sh[2 * i + 1], slot, sa, sb);
     }
-    int *d_sh = nullptr, *d_off = nullptr;
-    double *d_pp = nullptr;
     size_t ntoff = 0;
     for (int cb = 0; cb < NCLS_ALL; cb++)
         for (int ck = 0; ck <= cb; ck++)
             if (c->hp.cls_count[cb] && c->hp.cls_count[ck])
                 ntoff += (size_t)std::max(c->hp.cls_count[cb], c->hp.cls_count[ck]) * SCREEN_NBIN + 1;
-    if ((rc = c->pool.upload(&d_sh, c->hp.sh, st)) || (rc = c->pool.upload(&d_off, c->hp.pp_off, st)) ||
-        (rc = c->pool.upload(&d_pp, c->hp.pp, st)) || (rc = c->pool.upload(&c->d_q, c->q, st)) || (rc = c->pool.upload(&c->d_bins, c->bins, st)) || (rc = c->pool.alloc(&c->d_dsh, nsh * nsh)) ||
+    if ((rc = upload_pairs(c->pool, c->hp, c->dp, st)) || (rc = c->pool.upload(&c->d_q, c->q, st)) ||
+        (rc = c->pool.upload(&c->d_bins, c->bins, st)) || (rc = c->pool.alloc(&c->d_dsh, nsh * nsh)) ||
         (rc = c->pool.alloc(&c->d_sym, n2)) || (rc = c->pool.alloc(&c->d_a, n2)) || (rc = c->pool.alloc(&c->d_b, n2)) ||
         (rc = c->pool.alloc(&c->d_dmax, 26)) || (rc = c->pool.alloc(&c->d_toff, ntoff))) {
         set_error("dqc_direct_create: device allocation failed");
         return rc;
     }
     DQC_HIP(hipStreamSynchronize(st));  // the uploads read host vectors that may move
-    c->dp = DevPairs{d_sh, d_off, d_pp, c->hp.stride};
     c->n_toff = ntoff;
     if (hipHostMalloc((void **)&c->h_toff, sizeof(long long) * std::max<size_t>(ntoff, 1), hipHostMallocDefault) != hipSuccess) {
         c->h_toff = nullptr;
@@ -863,14 +857,8 @@ int dqc_eri_fill_tiles_part(double *d_tiles_part, const int *atm, int natm, cons
     SideJoin sj;       // (after the pool: destroyed -- i.e. the side streams joined -- before the scratch is released)
     DevShells ds;
     if ((rc = upload_shells(ds, bu, pool, st))) { set_error("dqc_eri_fill_tiles: device upload failed"); return rc; }
-    int *d_sh = nullptr, *d_off = nullptr;
-    double *d_pp = nullptr;
-    if ((rc = pool.upload(&d_sh, hp.sh, st)) || (rc = pool.upload(&d_off, hp.pp_off, st)) ||
-        (rc = pool.upload(&d_pp, hp.pp, st))) {
-        set_error("dqc_eri_fill_tiles: device upload failed");
-        return rc;
-    }
-    DevPairs dp{d_sh, d_off, d_pp, hp.stride};
+    DevPairs dp;
+    if ((rc = upload_pairs(pool, hp, dp, st))) { set_error("dqc_eri_fill_tiles: device upload failed"); return rc; }
     constexpr int NCLS = (ERI_LMAX + 1) * (ERI_LMAX + 2) / 2;
     EriOut og{0, 0, 0, 0};
     og.st_lo = lo;
@@ -942,16 +930,8 @@ int dqc_eri_fill_tiles_part(double *d_tiles_part, const int *atm, int natm, cons
                 h.pp_off.push_back((int)(h.pp.size() / hp.stride));
             }
         (void)np;
-        DevPairs d1{nullptr, nullptr, nullptr, hp.stride}, d0{nullptr, nullptr, nullptr, hp.stride};
-        auto up = [&](HostPairs &h, DevPairs &d) {
-            int *q_sh = nullptr, *q_off = nullptr;
-            double *q_pp = nullptr;
-            int r;
-            if ((r = pool.upload(&q_sh, h.sh, st)) || (r = pool.upload(&q_off, h.pp_off, st)) || (r = pool.upload(&q_pp, h.pp, st))) return r;
-            d = DevPairs{q_sh, q_off, q_pp, h.stride};
-            return 0;
-        };
-        if ((rc = up(h1, d1)) || (rc = up(h0, d0))) { set_error("dqc_eri_fill_tiles_part: device upload failed"); return rc; }
+        DevPairs d1, d0;
+        if ((rc = upload_pairs(pool, h1, d1, st)) || (rc = upload_pairs(pool, h0, d0, st))) { set_error("dqc_eri_fill_tiles_part: device upload failed"); return rc; }
         const FillTables f11{&d1, &d1, &h1, &h1, FILL_SAME_TABLE}, f10{&d1, &d0, &h1, &h0, FILL_CROSS}, f01{&d0, &d1, &h0, &h1, FILL_CROSS_OFFDIAG};
         if (wm.side && (rc = wm.side->fork(st))) { set_error("dqc_eri_fill_tiles_part: stream fork failed"); return rc; }
         sj.arm(wm.side, st);

@@ -1081,12 +1081,40 @@ inline bool prim_pair_negligible(double ck, double ab2, int lsum) {
     return f < PRIM_PAIR_EPS;
 }
 
+// one shell pair on its way into a pair table: shells, class index, primitive-pair records (`stride` doubles each)
+struct PairRec {
+    int a, b, cls;
+    std::vector<double> pp;
+};
+
+// the tail of every pair-list builder: the pairs sorted by class, inside a class deepest contraction first (a STABLE sort: the
+// kernels' task maps and launch_grad_class's dmax rely on that order), then packed into `hp`
+static void pack_pairs(std::vector<PairRec> &all, HostPairs &hp, int stride) {
+    auto npp = [stride](const PairRec &x) { return (int)x.pp.size() / stride; };
+    std::stable_sort(all.begin(), all.end(), [&](const PairRec &x, const PairRec &y) {
+        if (x.cls != y.cls) return x.cls < y.cls;
+        return npp(x) > npp(y);
+    });
+    for (int c = 0; c < 48; c++) { hp.cls_start[c] = 0; hp.cls_count[c] = 0; }
+    hp.sh.clear(); hp.pp.clear(); hp.pp_off.clear();
+    hp.pp_off.push_back(0);
+    for (size_t n = 0; n < all.size(); n++) {
+        const PairRec &pr = all[n];
+        if (hp.cls_count[pr.cls] == 0) hp.cls_start[pr.cls] = (int)n;
+        hp.cls_count[pr.cls]++;
+        hp.sh.push_back(pr.a);
+        hp.sh.push_back(pr.b);
+        hp.pp.insert(hp.pp.end(), pr.pp.begin(), pr.pp.end());
+        hp.pp_off.push_back((int)hp.pp.size() / stride);
+    }
+    hp.stride = stride;
+}
+
 // shell pairs (i >= j) of the shells [s0, s1); unit >= 0: instead the "pairs" (i, unit shell) used by the 2- and
 // 3-centre integrals (the unit shell has exponent 0, so P = A and K = 1)
 static void build_pairs(const Basis &b, HostPairs &hp, int s0 = 0, int s1 = -1, int unit = -1) {
     if (s1 < 0) s1 = (int)b.shells.size();
-    struct P { int a, b, cls, npp; std::vector<double> pp; };
-    std::vector<P> all;
+    std::vector<PairRec> all;
     all.reserve((size_t)(s1 - s0) * (s1 - s0 + 1) / 2);
     // grouped view (Basis::grouped): PP_STRIDE_G doubles per primitive pair -- four coefficient slots 2 xa + xb over the members
     // of the two groups (only s groups have a second member); otherwise five doubles, one coefficient
@@ -1097,7 +1125,7 @@ static void build_pairs(const Basis &b, HostPairs &hp, int s0 = 0, int s1 = -1, 
             int a = i, c = j;
             if (b.shells[c].l > b.shells[a].l) std::swap(a, c);
             const HostShell &A = b.shells[a], &B = b.shells[c];
-            P pr;
+            PairRec pr;
             pr.a = a; pr.b = c; pr.cls = A.l * (A.l + 1) / 2 + B.l;
             double ab2 = 0;
             for (int d = 0; d < 3; d++) ab2 += (A.r[d] - B.r[d]) * (A.r[d] - B.r[d]);
@@ -1127,25 +1155,32 @@ static void build_pairs(const Basis &b, HostPairs &hp, int s0 = 0, int s1 = -1, 
                         pr.pp.push_back(cf[3]);
                     }
                 }
-            pr.npp = (int)pr.pp.size() / stride;
             all.push_back(std::move(pr));
         }
-    std::stable_sort(all.begin(), all.end(), [](const P &x, const P &y) {
-        if (x.cls != y.cls) return x.cls < y.cls;
-        return x.npp > y.npp;
-    });
-    for (int c = 0; c < 48; c++) { hp.cls_start[c] = 0; hp.cls_count[c] = 0; }
-    hp.pp_off.push_back(0);
-    for (size_t n = 0; n < all.size(); n++) {
-        const P &pr = all[n];
-        if (hp.cls_count[pr.cls] == 0) hp.cls_start[pr.cls] = (int)n;
-        hp.cls_count[pr.cls]++;
-        hp.sh.push_back(pr.a);
-        hp.sh.push_back(pr.b);
-        hp.pp.insert(hp.pp.end(), pr.pp.begin(), pr.pp.end());
-        hp.pp_off.push_back((int)hp.pp.size() / stride);
-    }
-    hp.stride = stride;
+    pack_pairs(all, hp, stride);
+}
+
+// appends the unit shell of the 2- and 3-centre integrals (an s shell at the origin with exponent 0 and coefficient `coef`) and
+// returns its index
+static int append_unit_shell(Basis &b, double coef) {
+    HostShell u;
+    u.atom = 0; u.l = 0; u.nprim = 1; u.ao_off = b.nao; u.prim_off = (int)b.exps.size();
+    u.r[0] = u.r[1] = u.r[2] = 0.0;
+    b.exps.push_back(0.0);
+    b.coefs.push_back(coef);
+    b.shells.push_back(u);
+    return (int)b.shells.size() - 1;
+}
+
+// device copy of a pair table through `pool`: sh, pp_off, pp, in that order on the stream
+static int upload_pairs(DevPool &pool, const HostPairs &hp, DevPairs &dp, hipStream_t st) {
+    int *d_sh = nullptr, *d_off = nullptr;
+    double *d_pp = nullptr;
+    int rc;
+    if ((rc = pool.upload(&d_sh, hp.sh, st)) || (rc = pool.upload(&d_off, hp.pp_off, st)) || (rc = pool.upload(&d_pp, hp.pp, st)))
+        return rc;
+    dp = DevPairs{d_sh, d_off, d_pp, hp.stride};
+    return 0;
 }
 
 // depth-binned wave table of one DIAGONAL class launch (eri_split_lanes; kernel branch og.wtab): per (ket pair, bra depth bin) the

@@ -17,6 +17,11 @@
 // The same two contractions by the BASIS parameters of every primitive p (exponent alpha_p, stored coefficient c_p) instead of the
 // centres: dqc_eri_grad_basis / dqc_int1e_grad_basis, with d a / d c_p = g_p and d a / d alpha_p = -c_p r_A^2 g_p (an l + 2 shell) as
 // per-primitive uncontracted companions.  Orbital shells up to f there (f + 2 = h).
+// Host side: dqc_eri_grad, dqc_eri_grad_basis and dqc_df_grad (the same passes over (orbital pair | auxiliary) and (auxiliary |
+// auxiliary) for the density-fitted Coulomb energy) only parse, build their companions and ordered bra pair lists, name their
+// passes (bra list, dirn, gmode, launcher) in a GradJob and say how summed rows become output entries; run_grad_job owns the
+// rest -- uploads, the 64 slots of partial sums, the side-stream fork and join, the launches and the host fold.  The two
+// one-electron entry points share int1e_grad_setup in the same way.
 #include "eri_generic.hpp"
 
 namespace dqc {
@@ -43,14 +48,13 @@ static void cart_offsets(const Basis &b, int nsh, std::vector<int> &cao, int &nc
 
 // ordered pairs (first in [f0, f1), second in [0, nsecond)), class index = la * 8 + lb, NO swap
 static void build_pairs_ordered(const Basis &b, HostPairs &hp, int f0, int f1, int s0, int s1) {
-    struct P { int a, b, cls, npp; std::vector<double> pp; };
-    std::vector<P> all;
+    std::vector<PairRec> all;
     for (int i = f0; i < f1; i++) {
         const HostShell &A = b.shells[i];
         if (A.l < 0) continue;  // placeholder (no down companion of an s shell)
         for (int j = s0; j < s1; j++) {
             const HostShell &B = b.shells[j];
-            P pr;
+            PairRec pr;
             pr.a = i; pr.b = j; pr.cls = A.l * 8 + B.l;
             double ab2 = 0;
             for (int d = 0; d < 3; d++) ab2 += (A.r[d] - B.r[d]) * (A.r[d] - B.r[d]);
@@ -64,26 +68,28 @@ static void build_pairs_ordered(const Basis &b, HostPairs &hp, int f0, int f1, i
                     for (int d = 0; d < 3; d++) pr.pp.push_back((ea * A.r[d] + eb * B.r[d]) / p);
                     pr.pp.push_back(b.coefs[A.prim_off + ip] * b.coefs[B.prim_off + jp] * std::exp(-arg) / p);  // c_a c_b K_ab / p
                 }
-            pr.npp = (int)pr.pp.size() / 5;
             all.push_back(std::move(pr));
         }
     }
-    std::stable_sort(all.begin(), all.end(), [](const P &x, const P &y) {
-        if (x.cls != y.cls) return x.cls < y.cls;
-        return x.npp > y.npp;
-    });
-    for (int c = 0; c < 48; c++) { hp.cls_start[c] = 0; hp.cls_count[c] = 0; }
-    hp.sh.clear(); hp.pp.clear(); hp.pp_off.clear();
-    hp.pp_off.push_back(0);
-    for (size_t n = 0; n < all.size(); n++) {
-        const P &pr = all[n];
-        if (hp.cls_count[pr.cls] == 0) hp.cls_start[pr.cls] = (int)n;
-        hp.cls_count[pr.cls]++;
-        hp.sh.push_back(pr.a);
-        hp.sh.push_back(pr.b);
-        hp.pp.insert(hp.pp.end(), pr.pp.begin(), pr.pp.end());
-        hp.pp_off.push_back((int)hp.pp.size() / 5);
-    }
+    pack_pairs(all, hp, 5);
+}
+
+// companion shells of the centre derivative, appended to the N shells of the table: [N, 2N) up (l + 1, coefficients 2 alpha c),
+// [2N, 3N) down (l - 1; l = -1 marks "none")
+static void append_centre_companions(Basis &b, int N) {
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < N; i++) {
+            HostShell h = b.shells[i];
+            h.l = pass == 0 ? h.l + 1 : h.l - 1;
+            const int po = (int)b.exps.size();
+            for (int p = 0; p < h.nprim; p++) {
+                const double e = b.exps[b.shells[i].prim_off + p], c = b.coefs[b.shells[i].prim_off + p];
+                b.exps.push_back(e);
+                b.coefs.push_back(pass == 0 ? 2.0 * e * c : c);
+            }
+            h.prim_off = po;
+            b.shells.push_back(h);
+        }
 }
 
 struct GradCtx {
@@ -198,6 +204,89 @@ static int launch_grad_all(const GradCtx &c, hipStream_t st) {
     DQC_GB(0) DQC_GB(1) DQC_GB(2) DQC_GB(3) DQC_GB(4)
 #undef DQC_GB
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// host driver of a GRAD-mode pass set: dqc_eri_grad, dqc_eri_grad_basis and dqc_df_grad describe their work as a GradJob
+// ---------------------------------------------------------------------------------------------
+struct GradPass {
+    const HostPairs *bra;  // ordered pairs (companion shell, original shell): build_pairs_ordered
+    int dirn, gmode;       // EriOut::dirn and EriOut::gmode of the pass
+    int (*launch)(const GradCtx &, hipStream_t);  // launch_grad_all, launch_grad_df3c or launch_grad_df2c
+};
+
+struct GradJob {
+    const char *who = nullptr;  // the entry point, for the error strings
+    Basis b;                    // the parsed table, then its companion shells
+    HostPairs hket;
+    std::vector<GradPass> passes;
+    std::vector<int> cao, rows;  // per shell below norig: Cartesian offset, row of the partial sums (EriOut::cao, EriOut::sh_atom)
+    int ncart = 0, nrow = 0, norig = 0;
+    EriOut og{0, 0, 0, 0};  // what only some entry points set: jscale, kscale, ccart
+    bool fork = false;      // deal the class launches to the side streams
+    int wmap_depth = 0;     // > 0: depth-binned wave map for class pairs at least this deep (GradCtx)
+};
+
+// the nuclear forms: the rows are the atoms, g[a][d] += row[a][d]
+static void add_rows(const std::vector<double> &row, std::vector<double> &g) {
+    for (size_t i = 0; i < g.size(); i++) g[i] += row[i];
+}
+
+// Uploads the tables of the job, runs its passes into 64 zeroed slots of (nrow, 3) partial sums, sums the slots on the host and
+// lets fold(row, out) add the summed rows to the host copy of d_out (nout doubles), which is then written back.
+template <class Fold>
+static int run_grad_job(GradJob &j, const double *d_dcart, double *d_out, size_t nout, Fold fold, hipStream_t st) {
+    const std::string who(j.who);
+    int rc;
+    if ((rc = boys_table_ensure())) return rc;
+    // upload_shells needs l >= 0 everywhere: placeholders become s shells (never referenced by a pair)
+    for (HostShell &h : j.b.shells)
+        if (h.l < 0) h.l = 0;
+    DevPool pool;       // synchronous: the call ends with a stream synchronise
+    DevPool wpool(st);  // stream-ordered, for the wave tables alone
+    GradCtx c;
+    if (j.wmap_depth > 0) { c.pool = &wpool; c.wmap_depth = j.wmap_depth; }
+    if ((rc = upload_shells(c.ds, j.b, pool, st))) { set_error(who + ": device upload failed"); return rc; }
+    std::vector<DevPairs> dbra(j.passes.size());
+    for (size_t k = 0; k < dbra.size() && !rc; k++) rc = upload_pairs(pool, *j.passes[k].bra, dbra[k], st);
+    int *d_cao = nullptr, *d_rows = nullptr;
+    if (rc || (rc = upload_pairs(pool, j.hket, c.dket, st)) || (rc = pool.upload(&d_cao, j.cao, st)) ||
+        (rc = pool.upload(&d_rows, j.rows, st))) {
+        set_error(who + ": device upload failed");
+        return rc;
+    }
+    const int nslot = 64;
+    const size_t npart = (size_t)nslot * j.nrow * 3;
+    double *d_part = nullptr;
+    if (hipMalloc((void **)&d_part, sizeof(double) * npart) != hipSuccess) { set_error(who + ": out of memory"); return DQC_ENOMEM; }
+    pool.ptrs.push_back(d_part);
+    DQC_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * npart, st));
+    c.hket = &j.hket;
+    c.og = j.og;
+    c.og.dcart = d_dcart; c.og.ncart = j.ncart; c.og.cao = d_cao; c.og.sh_atom = d_rows; c.og.gpart = d_part;
+    c.og.nslot = nslot; c.og.natm = j.nrow; c.og.norig = j.norig;
+    SideJoin sj;  // (declared after the scratch pools of this call: destroyed, i.e. joined, before they are released)
+    if (j.fork) {
+        if ((c.side = side_streams()) != nullptr && (rc = c.side->fork(st))) { set_error(who + ": stream fork failed"); return rc; }
+        sj.arm(c.side, st);
+    }
+    for (size_t k = 0; k < dbra.size(); k++) {
+        const GradPass &p = j.passes[k];
+        c.dbra = dbra[k]; c.hbra = p.bra; c.og.dirn = p.dirn; c.og.gmode = p.gmode;
+        if ((rc = p.launch(c, st))) return rc;
+    }
+    if ((rc = sj.done())) { set_error(who + ": stream join failed"); return rc; }
+    // fold the slots into d_out on the host side of the stream: tiny
+    std::vector<double> part(npart), row((size_t)j.nrow * 3, 0.0), out(nout);
+    DQC_HIP(hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
+    DQC_HIP(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st));
+    DQC_HIP(hipStreamSynchronize(st));
+    for (int sidx = 0; sidx < nslot; sidx++)
+        for (size_t i = 0; i < row.size(); i++) row[i] += part[sidx * row.size() + i];
+    fold(row, out);
+    DQC_HIP(hipMemcpyAsync(d_out, out.data(), sizeof(double) * out.size(), hipMemcpyHostToDevice, st));
+    DQC_HIP(hipStreamSynchronize(st));
+    return DQC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -579,6 +668,46 @@ __global__ __launch_bounds__(64) void int1e_potential_sum(double *__restrict__ o
     out[ic] = t;
 }
 
+// orbital shells up to f: the alpha derivative needs the l + 2 shell, and h is the highest the Rys kernels reach
+static int basis_grad_lcheck(const Basis &b, const char *who) {
+    for (const HostShell &h : b.shells)
+        if (h.l > GRAD_LMAX) {
+            set_error((std::string(who) + ": basis-parameter derivatives support orbital shells up to f (a g shell needs l + 2 = i integrals)").c_str());
+            return DQC_EINVAL;
+        }
+    return 0;
+}
+
+// what dqc_int1e_grad and dqc_int1e_grad_basis (`basis`: with its refusal of shells above f) set up alike: the table parsed with the
+// charges `zs`, its Cartesian offsets, the device copies, and the launch grid (64 ordered shell pairs per block, the nuclei along y)
+struct Int1eGradSetup {
+    Basis b;
+    std::vector<int> cao;
+    int ncart = 0;
+    DevPool pool;
+    DevShells ds;
+    double *d_xyz = nullptr, *d_z = nullptr;
+    int *d_cao = nullptr;
+    dim3 grid;
+};
+// nbas == 0: returns DQC_OK with nothing uploaded (the callers return, too)
+static int int1e_grad_setup(Int1eGradSetup &s, const char *who, bool basis, const int *atm, int natm, const int *bas, int nbas,
+                            const double *env, int nenv, const double *zs, hipStream_t st) {
+    int rc = parse_basis(s.b, atm, natm, bas, nbas, env, nenv, zs);
+    if (rc) return rc;
+    if (nbas == 0) return DQC_OK;
+    if (basis && (rc = basis_grad_lcheck(s.b, who))) return rc;
+    cart_offsets(s.b, nbas, s.cao, s.ncart);
+    if ((rc = upload_shells(s.ds, s.b, s.pool, st)) || (rc = s.pool.upload(&s.d_xyz, s.b.atom_xyz, st)) ||
+        (rc = s.pool.upload(&s.d_z, s.b.atom_z, st)) || (rc = s.pool.upload(&s.d_cao, s.cao, st))) {
+        set_error(std::string(who) + ": device upload failed");
+        return rc;
+    }
+    const int npair = nbas * nbas;
+    s.grid = dim3((npair + 63) / 64, natm < 32 ? natm : 32);
+    return DQC_OK;
+}
+
 }  // namespace dqc
 
 extern "C" {
@@ -613,90 +742,30 @@ int dqc_eri_grad(double *d_grad, const double *d_dcart, double jscale, double ks
     // d_grad (natm, 3) += sum_{a in A} sum_bcd (d_A a b|c d) [2 jscale D_ab D_cd - kscale D_ac D_bd]; d_dcart (ncart, ncart)
     using namespace dqc;
     hipStream_t st = (hipStream_t)stream;
-    Basis b;
+    GradJob j;
+    j.who = "dqc_eri_grad";
+    Basis &b = j.b;
     int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, nullptr);
     if (rc) return rc;
     if (nbas == 0) return DQC_OK;
     const int N = nbas;
-    std::vector<int> cao, sh_atom(N);
-    int ncart;
-    cart_offsets(b, N, cao, ncart);
-    for (int i = 0; i < N; i++) sh_atom[i] = b.shells[i].atom;
-    // companion shells: [N, 2N) up (l+1, coefficients 2 alpha c), [2N, 3N) down (l-1; l = -1 marks "none")
-    for (int pass = 0; pass < 2; pass++)
-        for (int i = 0; i < N; i++) {
-            HostShell h = b.shells[i];
-            h.l = pass == 0 ? h.l + 1 : h.l - 1;
-            const int po = (int)b.exps.size();
-            for (int p = 0; p < h.nprim; p++) {
-                const double e = b.exps[b.shells[i].prim_off + p], c = b.coefs[b.shells[i].prim_off + p];
-                b.exps.push_back(e);
-                b.coefs.push_back(pass == 0 ? 2.0 * e * c : c);
-            }
-            h.prim_off = po;
-            b.shells.push_back(h);
-        }
-    HostPairs hup, hdown, hket;
+    cart_offsets(b, N, j.cao, j.ncart);
+    j.rows.resize(N);
+    for (int i = 0; i < N; i++) j.rows[i] = b.shells[i].atom;
+    append_centre_companions(b, N);
+    HostPairs hup, hdown;
     build_pairs_ordered(b, hup, N, 2 * N, 0, N);
     build_pairs_ordered(b, hdown, 2 * N, 3 * N, 0, N);
-    build_pairs(b, hket, 0, N);
-    // upload_shells needs l >= 0 everywhere: placeholders become s shells (never referenced by a pair)
-    for (HostShell &h : b.shells)
-        if (h.l < 0) h.l = 0;
-    if ((rc = boys_table_ensure())) return rc;
-    DevPool pool;
-    GradCtx c;
+    build_pairs(b, j.hket, 0, N);
+    j.passes = {{&hup, +1, 0, launch_grad_all}, {&hdown, -1, 0, launch_grad_all}};
+    j.nrow = natm; j.norig = N; j.og.jscale = jscale; j.og.kscale = kscale;
+    j.fork = true;
     // the depth-binned wave map of the fill (eri_core.hpp) is OFF here: measured on a 20-atom cc-pVDZ gradient it is slower for every
     // depth threshold -- 0.160 s (classes deeper than 64 primitive quartets), 0.149 (256), 0.140 (1024) against 0.107 s for the flat
     // task maps (DQC_GRAD_WMAP = the depth threshold for A/B runs, 0 / unset = never)
-    DevPool wpool(st);
     static const int wmap_env = [] { const char *e = getenv("DQC_GRAD_WMAP"); return e ? atoi(e) : 0; }();
-    if (wmap_env > 0) { c.pool = &wpool; c.wmap_depth = wmap_env; }
-    if ((rc = upload_shells(c.ds, b, pool, st))) { set_error("dqc_eri_grad: device upload failed"); return rc; }
-    auto up = [&](HostPairs &hp, DevPairs &dp) {
-        int *d_sh = nullptr, *d_off = nullptr;
-        double *d_pp = nullptr;
-        int r;
-        if ((r = pool.upload(&d_sh, hp.sh, st)) || (r = pool.upload(&d_off, hp.pp_off, st)) || (r = pool.upload(&d_pp, hp.pp, st)))
-            return r;
-        dp = DevPairs{d_sh, d_off, d_pp};
-        return 0;
-    };
-    DevPairs dup, ddown, dket;
-    int *d_cao = nullptr, *d_atom = nullptr;
-    if ((rc = up(hup, dup)) || (rc = up(hdown, ddown)) || (rc = up(hket, dket)) || (rc = pool.upload(&d_cao, cao, st)) ||
-        (rc = pool.upload(&d_atom, sh_atom, st))) {
-        set_error("dqc_eri_grad: device upload failed");
-        return rc;
-    }
-    const int nslot = 64;
-    double *d_part = nullptr;
-    if (hipMalloc((void **)&d_part, sizeof(double) * nslot * natm * 3) != hipSuccess) { set_error("dqc_eri_grad: out of memory"); return DQC_ENOMEM; }
-    pool.ptrs.push_back(d_part);
-    DQC_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * nslot * natm * 3, st));
-    c.dket = dket;
-    c.hket = &hket;
-    c.og = EriOut{0, 0, 0, 0};
-    c.og.dcart = d_dcart; c.og.ncart = ncart; c.og.cao = d_cao; c.og.sh_atom = d_atom; c.og.gpart = d_part;
-    c.og.nslot = nslot; c.og.natm = natm; c.og.norig = N; c.og.jscale = jscale; c.og.kscale = kscale;
-    SideJoin sj;  // (declared after the scratch pools of this call: destroyed, i.e. joined, before they are released)
-    if ((c.side = side_streams()) != nullptr && (rc = c.side->fork(st))) { set_error("dqc_eri_grad: stream fork failed"); return rc; }
-    sj.arm(c.side, st);
-    c.dbra = dup; c.hbra = &hup; c.og.dirn = +1;
-    if ((rc = launch_grad_all(c, st))) return rc;
-    c.dbra = ddown; c.hbra = &hdown; c.og.dirn = -1;
-    if ((rc = launch_grad_all(c, st))) return rc;
-    if ((rc = sj.done())) { set_error("dqc_eri_grad: stream join failed"); return rc; }
-    // fold the slots into d_grad on the host side of the stream: tiny
-    std::vector<double> part((size_t)nslot * natm * 3), g((size_t)natm * 3);
-    DQC_HIP(hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
-    DQC_HIP(hipMemcpyAsync(g.data(), d_grad, sizeof(double) * g.size(), hipMemcpyDeviceToHost, st));
-    DQC_HIP(hipStreamSynchronize(st));
-    for (int sidx = 0; sidx < nslot; sidx++)
-        for (size_t i = 0; i < g.size(); i++) g[i] += part[(size_t)sidx * natm * 3 + i];
-    DQC_HIP(hipMemcpyAsync(d_grad, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice, st));
-    DQC_HIP(hipStreamSynchronize(st));
-    return DQC_OK;
+    j.wmap_depth = wmap_env;
+    return run_grad_job(j, d_dcart, d_grad, (size_t)natm * 3, add_rows, st);
 }
 
 int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart, const int *atm, int natm, const int *bas,
@@ -705,40 +774,18 @@ int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart,
     // term of every nucleus; d_dcart / d_wcart: Cartesian-basis density and energy-weighted density (ncart, ncart)
     using namespace dqc;
     hipStream_t st = (hipStream_t)stream;
-    Basis b;
-    int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, zs);
-    if (rc) return rc;
-    if (nbas == 0) return DQC_OK;
-    std::vector<int> cao, sh_atom(nbas);
-    int ncart;
-    cart_offsets(b, nbas, cao, ncart);
-    for (int i = 0; i < nbas; i++) sh_atom[i] = b.shells[i].atom;
-    DevPool pool;
-    DevShells ds;
-    if ((rc = upload_shells(ds, b, pool, st))) { set_error("dqc_int1e_grad: device upload failed"); return rc; }
-    double *d_xyz = nullptr, *d_z = nullptr;
-    int *d_cao = nullptr, *d_atom = nullptr;
-    if ((rc = pool.upload(&d_xyz, b.atom_xyz, st)) || (rc = pool.upload(&d_z, b.atom_z, st)) ||
-        (rc = pool.upload(&d_cao, cao, st)) || (rc = pool.upload(&d_atom, sh_atom, st))) {
-        set_error("dqc_int1e_grad: device upload failed");
-        return rc;
-    }
-    const int npair = nbas * nbas;
-    hipLaunchKernelGGL(int1e_grad_kernel, dim3((npair + 63) / 64, natm < 32 ? natm : 32), dim3(64), 0, st, d_grad, ds, d_cao, d_atom, d_dcart, d_wcart,
-                       ncart, natm, d_xyz, d_z);
+    Int1eGradSetup s;
+    int rc = int1e_grad_setup(s, "dqc_int1e_grad", false, atm, natm, bas, nbas, env, nenv, zs, st);
+    if (rc || nbas == 0) return rc;
+    std::vector<int> sh_atom(nbas);
+    for (int i = 0; i < nbas; i++) sh_atom[i] = s.b.shells[i].atom;
+    int *d_atom = nullptr;
+    if ((rc = s.pool.upload(&d_atom, sh_atom, st))) { set_error("dqc_int1e_grad: device upload failed"); return rc; }
+    hipLaunchKernelGGL(int1e_grad_kernel, s.grid, dim3(64), 0, st, d_grad, s.ds, s.d_cao, d_atom, d_dcart, d_wcart, s.ncart, natm, s.d_xyz,
+                       s.d_z);
     DQC_CHECK_LAUNCH();
     DQC_HIP(hipStreamSynchronize(st));
     return DQC_OK;
-}
-
-// orbital shells up to f: the alpha derivative needs the l + 2 shell, and h is the highest the Rys kernels reach
-static int basis_grad_lcheck(const dqc::Basis &b, const char *who) {
-    for (const dqc::HostShell &h : b.shells)
-        if (h.l > dqc::GRAD_LMAX) {
-            dqc::set_error((std::string(who) + ": basis-parameter derivatives support orbital shells up to f (a g shell needs l + 2 = i integrals)").c_str());
-            return DQC_EINVAL;
-        }
-    return 0;
 }
 
 int dqc_eri_grad_basis(double *d_out, const double *d_dcart, double jscale, double kscale, const int *atm, int natm, const int *bas,
@@ -747,16 +794,18 @@ int dqc_eri_grad_basis(double *d_out, const double *d_dcart, double jscale, doub
     // (column 0) or c_p (column 1) of every primitive p in table order; d_dcart (ncart, ncart)
     using namespace dqc;
     hipStream_t st = (hipStream_t)stream;
-    Basis b;
+    GradJob j;
+    j.who = "dqc_eri_grad_basis";
+    Basis &b = j.b;
     int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, nullptr);
     if (rc) return rc;
     if (nbas == 0) return DQC_OK;
-    if ((rc = basis_grad_lcheck(b, "dqc_eri_grad_basis"))) return rc;
+    if ((rc = basis_grad_lcheck(b, j.who))) return rc;
     const int N = nbas, P = (int)b.exps.size();
-    std::vector<int> cao, rows(N + 2 * P, 0);
-    int ncart;
-    cart_offsets(b, N, cao, ncart);
+    std::vector<int> &cao = j.cao, &rows = j.rows;
+    cart_offsets(b, N, cao, j.ncart);
     cao.resize(N + 2 * P);
+    rows.assign(N + 2 * P, 0);
     // per-primitive companion shells, uncontracted: [N, N + P) the primitive itself (l, coefficient 1),
     // [N + P, N + 2P) its r_A^2 multiple (l + 2, coefficient -c_p).  The GRAD epilogue (eri_core.hpp, dirn 0 / 2) looks both maps up
     // by the companion shell itself: cao = the Cartesian offset of its original shell, rows = its row of the partial sums
@@ -775,63 +824,22 @@ int dqc_eri_grad_basis(double *d_out, const double *d_dcart, double jscale, doub
                 b.coefs.push_back(pass == 0 ? 1.0 : -b.coefs[row]);
                 b.shells.push_back(h);
             }
-    HostPairs hsame, hup2, hket;
+    HostPairs hsame, hup2;
     build_pairs_ordered(b, hsame, N, N + P, 0, N);
     build_pairs_ordered(b, hup2, N + P, N + 2 * P, 0, N);
-    build_pairs(b, hket, 0, N);
-    if ((rc = boys_table_ensure())) return rc;
-    DevPool pool;
-    GradCtx c;
-    if ((rc = upload_shells(c.ds, b, pool, st))) { set_error("dqc_eri_grad_basis: device upload failed"); return rc; }
-    auto up = [&](HostPairs &hp, DevPairs &dp) {
-        int *d_sh = nullptr, *d_off = nullptr;
-        double *d_pp = nullptr;
-        int r;
-        if ((r = pool.upload(&d_sh, hp.sh, st)) || (r = pool.upload(&d_off, hp.pp_off, st)) || (r = pool.upload(&d_pp, hp.pp, st)))
-            return r;
-        dp = DevPairs{d_sh, d_off, d_pp};
-        return 0;
-    };
-    DevPairs dsame, dup2, dket;
-    int *d_cao = nullptr, *d_rows = nullptr;
-    if ((rc = up(hsame, dsame)) || (rc = up(hup2, dup2)) || (rc = up(hket, dket)) || (rc = pool.upload(&d_cao, cao, st)) ||
-        (rc = pool.upload(&d_rows, rows, st))) {
-        set_error("dqc_eri_grad_basis: device upload failed");
-        return rc;
-    }
-    const int nslot = 64, nrow = 2 * P;
-    const size_t npart = (size_t)nslot * nrow * 3;
-    double *d_part = nullptr;
-    if (hipMalloc((void **)&d_part, sizeof(double) * npart) != hipSuccess) { set_error("dqc_eri_grad_basis: out of memory"); return DQC_ENOMEM; }
-    pool.ptrs.push_back(d_part);
-    DQC_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * npart, st));
-    c.dket = dket;
-    c.hket = &hket;
-    c.og = EriOut{0, 0, 0, 0};
-    c.og.dcart = d_dcart; c.og.ncart = ncart; c.og.cao = d_cao; c.og.sh_atom = d_rows; c.og.gpart = d_part;
-    c.og.nslot = nslot; c.og.natm = nrow; c.og.norig = N + 2 * P; c.og.jscale = jscale; c.og.kscale = kscale;
-    SideJoin sj;  // (declared after the scratch pools of this call: destroyed, i.e. joined, before they are released)
-    if ((c.side = side_streams()) != nullptr && (rc = c.side->fork(st))) { set_error("dqc_eri_grad_basis: stream fork failed"); return rc; }
-    sj.arm(c.side, st);
-    c.dbra = dsame; c.hbra = &hsame; c.og.dirn = 0;
-    if ((rc = launch_grad_all(c, st))) return rc;
-    c.dbra = dup2; c.hbra = &hup2; c.og.dirn = 2;
-    if ((rc = launch_grad_all(c, st))) return rc;
-    if ((rc = sj.done())) { set_error("dqc_eri_grad_basis: stream join failed"); return rc; }
-    // fold the slots into d_out on the host side of the stream: tiny
-    std::vector<double> part(npart), g((size_t)P * 2);
-    DQC_HIP(hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
-    DQC_HIP(hipMemcpyAsync(g.data(), d_out, sizeof(double) * g.size(), hipMemcpyDeviceToHost, st));
-    DQC_HIP(hipStreamSynchronize(st));
-    for (int sidx = 0; sidx < nslot; sidx++)
+    build_pairs(b, j.hket, 0, N);
+    j.passes = {{&hsame, 0, 0, launch_grad_all}, {&hup2, 2, 0, launch_grad_all}};
+    j.nrow = 2 * P; j.norig = N + 2 * P; j.og.jscale = jscale; j.og.kscale = kscale;
+    j.fork = true;
+    // alpha_p: the three raised powers of row P + p together; c_p: row p holds the same sum three times
+    auto fold = [P](const std::vector<double> &row, std::vector<double> &out) {
         for (int p = 0; p < P; p++) {
-            const double *same = &part[((size_t)sidx * nrow + p) * 3], *up2 = &part[((size_t)sidx * nrow + P + p) * 3];
-            g[(size_t)p * 2] += up2[0] + up2[1] + up2[2];
-            g[(size_t)p * 2 + 1] += same[0];
+            const double *same = &row[(size_t)p * 3], *up2 = &row[(size_t)(P + p) * 3];
+            out[(size_t)p * 2] += up2[0] + up2[1] + up2[2];
+            out[(size_t)p * 2 + 1] += same[0];
         }
-    DQC_HIP(hipMemcpyAsync(d_out, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice, st));
-    DQC_HIP(hipStreamSynchronize(st));
-    return DQC_OK;
+    };
+    return run_grad_job(j, d_dcart, d_out, (size_t)P * 2, fold, st);
 }
 
 int dqc_int1e_grad_basis(double *d_out, const double *d_dcart, const double *d_wcart, const int *atm, int natm, const int *bas,
@@ -840,26 +848,11 @@ int dqc_int1e_grad_basis(double *d_out, const double *d_dcart, const double *d_w
     // c_p (column 1); d_dcart / d_wcart: Cartesian-basis density and energy-weighted density (ncart, ncart)
     using namespace dqc;
     hipStream_t st = (hipStream_t)stream;
-    Basis b;
-    int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, zs);
-    if (rc) return rc;
-    if (nbas == 0) return DQC_OK;
-    if ((rc = basis_grad_lcheck(b, "dqc_int1e_grad_basis"))) return rc;
-    std::vector<int> cao;
-    int ncart;
-    cart_offsets(b, nbas, cao, ncart);
-    DevPool pool;
-    DevShells ds;
-    if ((rc = upload_shells(ds, b, pool, st))) { set_error("dqc_int1e_grad_basis: device upload failed"); return rc; }
-    double *d_xyz = nullptr, *d_z = nullptr;
-    int *d_cao = nullptr;
-    if ((rc = pool.upload(&d_xyz, b.atom_xyz, st)) || (rc = pool.upload(&d_z, b.atom_z, st)) || (rc = pool.upload(&d_cao, cao, st))) {
-        set_error("dqc_int1e_grad_basis: device upload failed");
-        return rc;
-    }
-    const int npair = nbas * nbas;
-    hipLaunchKernelGGL(int1e_grad_basis_kernel, dim3((npair + 63) / 64, natm < 32 ? natm : 32), dim3(64), 0, st, d_out, ds, d_cao, d_dcart,
-                       d_wcart, ncart, natm, d_xyz, d_z);
+    Int1eGradSetup s;
+    int rc = int1e_grad_setup(s, "dqc_int1e_grad_basis", true, atm, natm, bas, nbas, env, nenv, zs, st);
+    if (rc || nbas == 0) return rc;
+    hipLaunchKernelGGL(int1e_grad_basis_kernel, s.grid, dim3(64), 0, st, d_out, s.ds, s.d_cao, d_dcart, d_wcart, s.ncart, natm, s.d_xyz,
+                       s.d_z);
     DQC_CHECK_LAUNCH();
     DQC_HIP(hipStreamSynchronize(st));
     return DQC_OK;
@@ -913,95 +906,32 @@ int dqc_df_grad(double *d_grad, const double *d_dcart, const double *d_ccart, co
     // (zero outside the orbital block / auxiliary segment).
     using namespace dqc;
     hipStream_t st = (hipStream_t)stream;
-    Basis b;
+    GradJob j;
+    j.who = "dqc_df_grad";
+    Basis &b = j.b;
     int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, nullptr);
     if (rc) return rc;
     if (sh0 < 0 || sh1 > nbas || sh0 > sh1 || k0 < 0 || k1 > nbas || k0 > k1) { set_error("dqc_df_grad: shell ranges outside the table"); return DQC_EINVAL; }
     if (sh0 == sh1 || k0 == k1) return DQC_OK;
     const int N = nbas;
-    std::vector<int> cao, sh_atom(3 * N + 1, 0);
-    int ncart;
-    cart_offsets(b, N, cao, ncart);
-    cao.resize(3 * N + 1, 0);
-    for (int i = 0; i < N; i++) sh_atom[i] = b.shells[i].atom;
-    for (int pass = 0; pass < 2; pass++)
-        for (int i = 0; i < N; i++) {
-            HostShell h = b.shells[i];
-            h.l = pass == 0 ? h.l + 1 : h.l - 1;
-            const int po = (int)b.exps.size();
-            for (int p = 0; p < h.nprim; p++) {
-                const double e = b.exps[b.shells[i].prim_off + p], c = b.coefs[b.shells[i].prim_off + p];
-                b.exps.push_back(e);
-                b.coefs.push_back(pass == 0 ? 2.0 * e * c : c);
-            }
-            h.prim_off = po;
-            b.shells.push_back(h);
-        }
-    HostShell u;
-    u.atom = 0; u.l = 0; u.nprim = 1; u.ao_off = b.nao; u.prim_off = (int)b.exps.size();
-    u.r[0] = u.r[1] = u.r[2] = 0.0;
-    b.exps.push_back(0.0);
-    b.coefs.push_back(1.0);  // GRAD mode contracts CARTESIAN blocks: the unit function is the Cartesian s function 1
-                             // (df.hip uses sqrt(4 pi) because there the l = 0 solid-harmonic factor is applied)
-    b.shells.push_back(u);
-    const int unit = 3 * N;
-    HostPairs h3up, h3down, h2up, h2down, hket;
+    cart_offsets(b, N, j.cao, j.ncart);
+    j.cao.resize(3 * N + 1, 0);
+    j.rows.assign(3 * N + 1, 0);
+    for (int i = 0; i < N; i++) j.rows[i] = b.shells[i].atom;
+    append_centre_companions(b, N);
+    // GRAD mode contracts CARTESIAN blocks: the unit function is the Cartesian s function 1 (df.hip uses sqrt(4 pi) because there
+    // the l = 0 solid-harmonic factor is applied)
+    const int unit = append_unit_shell(b, 1.0);
+    HostPairs h3up, h3down, h2up, h2down;
     build_pairs_ordered(b, h3up, N + sh0, N + sh1, sh0, sh1);
     build_pairs_ordered(b, h3down, 2 * N + sh0, 2 * N + sh1, sh0, sh1);
     build_pairs_ordered(b, h2up, N + k0, N + k1, unit, unit + 1);
     build_pairs_ordered(b, h2down, 2 * N + k0, 2 * N + k1, unit, unit + 1);
-    build_pairs(b, hket, k0, k1, unit);
-    for (HostShell &h : b.shells)
-        if (h.l < 0) h.l = 0;
-    if ((rc = boys_table_ensure())) return rc;
-    DevPool pool;
-    GradCtx c;
-    if ((rc = upload_shells(c.ds, b, pool, st))) { set_error("dqc_df_grad: device upload failed"); return rc; }
-    auto up = [&](HostPairs &hp, DevPairs &dp) {
-        int *d_sh = nullptr, *d_off = nullptr;
-        double *d_pp = nullptr;
-        int r;
-        if ((r = pool.upload(&d_sh, hp.sh, st)) || (r = pool.upload(&d_off, hp.pp_off, st)) || (r = pool.upload(&d_pp, hp.pp, st)))
-            return r;
-        dp = DevPairs{d_sh, d_off, d_pp};
-        return 0;
-    };
-    DevPairs d3up, d3down, d2up, d2down, dket;
-    int *d_cao = nullptr, *d_atom = nullptr;
-    if ((rc = up(h3up, d3up)) || (rc = up(h3down, d3down)) || (rc = up(h2up, d2up)) || (rc = up(h2down, d2down)) ||
-        (rc = up(hket, dket)) || (rc = pool.upload(&d_cao, cao, st)) || (rc = pool.upload(&d_atom, sh_atom, st))) {
-        set_error("dqc_df_grad: device upload failed");
-        return rc;
-    }
-    const int nslot = 64;
-    double *d_part = nullptr;
-    if (hipMalloc((void **)&d_part, sizeof(double) * nslot * natm * 3) != hipSuccess) { set_error("dqc_df_grad: out of memory"); return DQC_ENOMEM; }
-    pool.ptrs.push_back(d_part);
-    DQC_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * nslot * natm * 3, st));
-    c.dket = dket;
-    c.hket = &hket;
-    c.og = EriOut{0, 0, 0, 0};
-    c.og.dcart = d_dcart; c.og.ccart = d_ccart; c.og.ncart = ncart; c.og.cao = d_cao; c.og.sh_atom = d_atom; c.og.gpart = d_part;
-    c.og.nslot = nslot; c.og.natm = natm; c.og.norig = N;
-    c.og.gmode = 1;
-    c.dbra = d3up; c.hbra = &h3up; c.og.dirn = +1;
-    if ((rc = launch_grad_df3c(c, st))) return rc;
-    c.dbra = d3down; c.hbra = &h3down; c.og.dirn = -1;
-    if ((rc = launch_grad_df3c(c, st))) return rc;
-    c.og.gmode = 2;
-    c.dbra = d2up; c.hbra = &h2up; c.og.dirn = +1;
-    if ((rc = launch_grad_df2c(c, st))) return rc;
-    c.dbra = d2down; c.hbra = &h2down; c.og.dirn = -1;
-    if ((rc = launch_grad_df2c(c, st))) return rc;
-    std::vector<double> part((size_t)nslot * natm * 3), g((size_t)natm * 3);
-    DQC_HIP(hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
-    DQC_HIP(hipMemcpyAsync(g.data(), d_grad, sizeof(double) * g.size(), hipMemcpyDeviceToHost, st));
-    DQC_HIP(hipStreamSynchronize(st));
-    for (int sidx = 0; sidx < nslot; sidx++)
-        for (size_t i = 0; i < g.size(); i++) g[i] += part[(size_t)sidx * natm * 3 + i];
-    DQC_HIP(hipMemcpyAsync(d_grad, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice, st));
-    DQC_HIP(hipStreamSynchronize(st));
-    return DQC_OK;
+    build_pairs(b, j.hket, k0, k1, unit);
+    j.passes = {{&h3up, +1, 1, launch_grad_df3c}, {&h3down, -1, 1, launch_grad_df3c},
+                {&h2up, +1, 2, launch_grad_df2c}, {&h2down, -1, 2, launch_grad_df2c}};
+    j.nrow = natm; j.norig = N; j.og.ccart = d_ccart;
+    return run_grad_job(j, d_dcart, d_grad, (size_t)natm * 3, add_rows, st);
 }
 
 }  // extern "C"

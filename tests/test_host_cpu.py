@@ -316,6 +316,69 @@ def test_cart2sph_matrix_host_function():
     assert np.abs(out).max() == 0.0
 
 
+def test_gradient_entry_points_host_gates_without_a_gpu():
+    """the gates dqc_eri_grad, dqc_eri_grad_basis, dqc_df_grad, dqc_int1e_grad, dqc_int1e_grad_basis and dqc_int1e_potential take
+    BEFORE their first HIP call (raw ctypes, null device pointers and stream, H2O / STO-3G): empty tables and empty shell ranges
+    return 0, bad ranges, a negative point count, a g shell in the basis-parameter forms and a bad atom index are refused with
+    their messages"""
+    from dqc_amd import build, lib
+    build.build()
+    so = ctypes.CDLL(lib.libpath())
+    so.dqc_last_error.restype = ctypes.c_char_p
+    t = ob.make_tables(M.H2O, "sto-3g")
+    atm = np.ascontiguousarray(t.atm, dtype=np.int32)
+    env = np.ascontiguousarray(t.env, dtype=np.float64)
+    zs = np.ascontiguousarray(atm[:, 0], dtype=np.float64)
+    natm, nenv = atm.shape[0], env.shape[0]
+    ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+    I, D, V = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
+    so.dqc_eri_grad.argtypes = so.dqc_eri_grad_basis.argtypes = [V, V, D, D, ip, I, ip, I, dp, I, V]
+    so.dqc_int1e_grad.argtypes = so.dqc_int1e_grad_basis.argtypes = [V, V, V, ip, I, ip, I, dp, I, dp, V]
+    so.dqc_df_grad.argtypes = [V, V, V, ip, I, ip, I, dp, I, I, I, I, I, V]
+    so.dqc_int1e_potential.argtypes = [V, V, V, I, ip, I, ip, I, dp, I, V]
+
+    def tables(bas, nbas=None):
+        bas = np.ascontiguousarray(bas, dtype=np.int32)
+        return (atm.ctypes.data_as(ip), natm, bas.ctypes.data_as(ip), bas.shape[0] if nbas is None else nbas, env.ctypes.data_as(dp), nenv), bas
+
+    def eri(fn, bas, nbas=None):
+        tab, keep = tables(bas, nbas)
+        return fn(None, None, 1.0, 1.0, *tab, None)
+
+    def int1e(fn, bas, nbas=None):
+        tab, keep = tables(bas, nbas)
+        return fn(None, None, None, *tab, zs.ctypes.data_as(dp), None)
+
+    def df(sh0, sh1, k0, k1):
+        tab, keep = tables(t.bas)
+        return so.dqc_df_grad(None, None, None, *tab, sh0, sh1, k0, k1, None)
+
+    def pot(npts):
+        tab, keep = tables(t.bas)
+        return so.dqc_int1e_potential(None, None, None, npts, *tab, None)
+
+    err = lambda: so.dqc_last_error().decode()  # noqa: E731
+    nbas = t.bas.shape[0]
+    assert eri(so.dqc_eri_grad, t.bas, 0) == 0 and eri(so.dqc_eri_grad_basis, t.bas, 0) == 0
+    assert int1e(so.dqc_int1e_grad, t.bas, 0) == 0 and int1e(so.dqc_int1e_grad_basis, t.bas, 0) == 0
+    assert df(2, 2, 0, nbas) == 0       # empty orbital range
+    assert df(0, nbas, nbas, nbas) == 0  # empty auxiliary range
+    assert df(0, nbas + 1, 0, nbas) == -1 and err() == "dqc_df_grad: shell ranges outside the table"
+    assert eri(so.dqc_eri_grad, t.bas, 0) == 0  # (a success in between: the next message is the next refusal's own)
+    assert df(3, 2, 0, nbas) == -1 and err() == "dqc_df_grad: shell ranges outside the table"
+    assert pot(0) == 0
+    assert pot(-1) == -1 and err() == "dqc_int1e_potential: npts must be >= 0"
+    gbas = np.array(t.bas, dtype=np.int32)
+    gbas[1, 1] = 4
+    assert eri(so.dqc_eri_grad_basis, gbas) == -1
+    assert err().startswith("dqc_eri_grad_basis: basis-parameter derivatives support orbital shells up to f")
+    assert int1e(so.dqc_int1e_grad_basis, gbas) == -1
+    assert err().startswith("dqc_int1e_grad_basis: basis-parameter derivatives support orbital shells up to f")
+    abas = np.array(t.bas, dtype=np.int32)
+    abas[0, 0] = 9
+    assert eri(so.dqc_eri_grad, abas) == -1 and err() == "bas: atom index out of range"
+
+
 def test_purification_restatement_on_cpu():
     """dqc_amd.purify (torch form of the TC2 iteration the HIP kernel fuses): projector of a random gapped symmetric
     matrix == eigh projector; gapless input is reported through the error"""
