@@ -112,9 +112,17 @@ DQC_DEV void rowdot_epilogue_paired(const v4d (&acc)[NCT], double (&p)[4][GGA ? 
     auto issue = [&](int bt, double2 (&d2)[NP > 0 ? NP : 1], double &d1) {
         const int r = bt / NQ, q = bt % NQ + Q0;
         const double *base = (q == 0 ? blk0 : blkg + q * cs) + col0;  // uniform; tile pairs at immediate offsets
+        // Q0 = 1 (the factor-form kernels): the gradient arrays are read here and nowhere else in the launch -- streamed
+        // (load_once*).  Q0 = 0 (density_kernel) reads the array its K loop has just read and keeps the default policy.
+        if constexpr (Q0 != 0) {
 #pragma unroll
-        for (int m = 0; m < NP; m++) d2[m] = *reinterpret_cast<const double2 *>(base + roff[r] + m * 32);
-        if (ODD) d1 = base[(roff[r] - lr) + (NCT - 1) * 16];
+            for (int m = 0; m < NP; m++) d2[m] = load_once16(base + roff[r] + m * 32);
+            if (ODD) d1 = load_once8(base + (roff[r] - lr) + (NCT - 1) * 16);
+        } else {
+#pragma unroll
+            for (int m = 0; m < NP; m++) d2[m] = *reinterpret_cast<const double2 *>(base + roff[r] + m * 32);
+            if (ODD) d1 = base[(roff[r] - lr) + (NCT - 1) * 16];
+        }
     };
 #pragma unroll
     for (int b0 = 0; b0 < DP - 1 && b0 < NB; b0++) issue(b0, t2[b0], t1[b0]);
@@ -430,9 +438,9 @@ __global__ __launch_bounds__(256, 2) void density_lr_kernel(double *__restrict__
 #define DQC_LR_PREFETCH(KC, S)                                                                            \
     {                                                                                                     \
         const int kq = min((KC), nk - 1); /* past-the-end chunks re-read the last one, never staged */     \
-        const double *s_ = aoblk + kq * DEN_KC + aoff;                                                    \
-        pa##S##a = *reinterpret_cast<const double2 *>(s_);                                                \
-        pa##S##b = *reinterpret_cast<const double2 *>(s_ + 2);                                            \
+        const double *s_ = aoblk + kq * DEN_KC + aoff; /* Phi: read once per launch, streamed; L: reused */ \
+        pa##S##a = load_once16(s_);                                                                       \
+        pa##S##b = load_once16(s_ + 2);                                                                   \
         const double *l_ = orb + (size_t)kq * DEN_KC * RP; /* the (KC x RP) chunk is contiguous in orb */ \
         pl##S##a = *reinterpret_cast<const double2 *>(l_ + lo0);                                          \
         if (NL2 > 1) pl##S##b = *reinterpret_cast<const double2 *>(l_ + lo1);                             \
@@ -759,11 +767,11 @@ __global__ __launch_bounds__(ROLE_NT, 1) void density_roles_kernel(double *__res
         double2 pa0a, pa0b, pa1a, pa1b, pa2a, pa2b, pa3a, pa3b;
         static_assert(NPF == 4, "four named prefetch sets");
 #define DQC_ROLE_REQUEST(T, KC, SET)                                                                       \
-    {   /* chunk KC of tile T: 16 rows x 128 bytes */                                                      \
+    {   /* chunk KC of tile T: 16 rows x 128 bytes, read once per launch (streamed) */                     \
         const int rmax_ = ngrid - 1 - (T) * DEN_BM;                                                        \
         const double *s_ = ao + (size_t)(T) * DEN_BM * lda + (min(w * 16 + arow, rmax_) * lda + aseg) + (KC) * DEN_KC; \
-        pa##SET##a = *reinterpret_cast<const double2 *>(s_);                                               \
-        pa##SET##b = *reinterpret_cast<const double2 *>(s_ + 2);                                           \
+        pa##SET##a = load_once16(s_);                                                                      \
+        pa##SET##b = load_once16(s_ + 2);                                                                  \
     }
 #define DQC_ROLE_STEP(KC, SET)                                                                             \
     if ((KC) < NT) {                                                                                       \
