@@ -100,6 +100,9 @@ def load():
     lib.dqc_df_exchange.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_int, c_int, c_dp, c_vp]
     lib.dqc_df_exchange_work_doubles.argtypes = [c_int, c_int, c_int]
     lib.dqc_df_exchange_work_doubles.restype = c_sz
+    lib.dqc_mp2_work_doubles.argtypes = [c_int] * 5
+    lib.dqc_mp2_work_doubles.restype = c_sz
+    lib.dqc_mp2_pair_energies.argtypes = [c_dp] * 8 + [c_int] * 8 + [c_dp, c_vp]
     lib.dqc_eri_tiles_to_dense.argtypes = [c_dp, c_dp, c_int, c_vp]
     lib.dqc_jk_from_tiles.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_vp]
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
@@ -396,6 +399,41 @@ def df_exchange(b, factor_pair, work=None, naux=None):
     with _on(b.device) as st_:
         _check(load().dqc_df_exchange(_ptr(out), _ptr(b), _ptr(orb), _ptr(orbt), nao, naux, rp, _ptr(work), st_), "dqc_df_exchange")
     return out[:nao, :nao]
+
+
+def mp2_pair_energies(bi, bj, eps_oi, eps_oj, eps_va, eps_vb, same, work=None):
+    """RI-MP2 pair energies (csrc/mp2.hip): bi (noi, naux, ldva), bj (noj, naux, ldvb) the occupied-virtual three-index tensors, one
+    (naux, ldv) slab per occupied orbital, ldv a multiple of 16 (columns >= nv are ignored); eps_*: the orbital energies, whose lengths
+    are the orbital counts.  same=True (bj is bi): (e_os, e_ss), both (no, no) and symmetric; same=False: (e_os (noi, noj), None).
+    e_os[i, j] = sum_ab V^2 / D, e_ss[i, j] = sum_ab V (V - V^T) / D.  No atomics: bit-reproducible.  The arguments are checked
+    before anything is launched"""
+    same = bool(same)
+    for name, t in (("bi", bi), ("bj", bj)):
+        if t.dim() != 3 or t.shape[2] % 16:
+            raise DqcAmdError("mp2_pair_energies: %s must be (nocc, naux, ldv) with ldv a multiple of 16, got %s" % (name, tuple(t.shape)))
+    noi, naux, ldva = (int(x) for x in bi.shape)
+    noj, ldvb = int(bj.shape[0]), int(bj.shape[2])
+    nva, nvb = int(eps_va.numel()), int(eps_vb.numel())
+    if int(bj.shape[1]) != naux:
+        raise DqcAmdError("mp2_pair_energies: bi and bj have %d and %d auxiliary functions" % (naux, bj.shape[1]))
+    if int(eps_oi.numel()) != noi or int(eps_oj.numel()) != noj:
+        raise DqcAmdError("mp2_pair_energies: %d and %d occupied energies for %d and %d slabs" % (eps_oi.numel(), eps_oj.numel(), noi, noj))
+    if nva > ldva or nvb > ldvb:
+        raise DqcAmdError("mp2_pair_energies: %d and %d virtual energies for slabs of %d and %d columns" % (nva, nvb, ldva, ldvb))
+    if same and (bj is not bi and bj.data_ptr() != bi.data_ptr() or tuple(bi.shape) != tuple(bj.shape) or nva != nvb):
+        raise DqcAmdError("mp2_pair_energies: same=True takes one tensor and one set of virtual energies on both sides")
+    if bi.data_ptr() % 16 or bj.data_ptr() % 16:
+        raise DqcAmdError("mp2_pair_energies: the tensors must be 16-byte aligned")
+    L = load()
+    need = int(L.dqc_mp2_work_doubles(noi, noj, nva, nvb, int(same)))
+    if work is None or work.numel() < need:
+        work = torch.empty(max(need, 1), dtype=torch.float64, device=bi.device)
+    eos = torch.empty((noi, noj), dtype=torch.float64, device=bi.device)
+    ess = torch.empty((noi, noj), dtype=torch.float64, device=bi.device) if same else None
+    with _on(bi.device) as st_:
+        _check(L.dqc_mp2_pair_energies(_ptr(eos), _ptr(ess), _ptr(bi), _ptr(bj), _ptr(eps_oi), _ptr(eps_oj), _ptr(eps_va), _ptr(eps_vb),
+                                       noi, noj, nva, nvb, ldva, ldvb, naux, int(same), _ptr(work), st_), "dqc_mp2_pair_energies")
+    return eos, ess
 
 
 def cart2sph_matrix(tab, device):

@@ -301,6 +301,21 @@ size_t dqc_df_exchange_work_doubles(int nao, int naux, int rp);
 int dqc_df_exchange(double *d_k, const double *d_b, const double *d_orb, const double *d_orbt, int nao, int naux, int rp,
                     double *d_work, void *stream);
 
+/* RI-MP2 pair energies from occupied-virtual three-index tensors, fused (the (ia|jb) are never stored):
+ *   V^{ij}_{ab} = sum_P Bi[i, P, a] Bj[j, P, b],   D^{ij}_{ab} = eoi[i] + eoj[j] - eva[a] - evb[b],
+ *   e_os[i, j] = sum_ab V_ab^2 / D_ab,   e_ss[i, j] = sum_ab V_ab (V_ab - V_ba) / D_ab.
+ * d_bi (noi, naux, ldva), d_bj (noj, naux, ldvb): one (naux, ldv) slab per occupied orbital, 16-byte aligned; ldv a multiple of 16,
+ * >= nv; columns >= nv are masked (whatever they hold contributes exactly zero).  d_eoi (noi), d_eoj (noj), d_eva (nva), d_evb (nvb):
+ * orbital energies.  same != 0 (restricted, alpha-alpha, beta-beta): d_bj == d_bi and equal shapes; d_eos and d_ess (noi, noi) are
+ * overwritten, symmetric (i <= j is computed and mirrored).  same == 0 (alpha-beta): d_eos (noi, noj) is overwritten, d_ess is not
+ * touched (may be null).  noi or noj zero: nothing to write; nva, nvb or naux zero: zeros.  d_work: dqc_mp2_work_doubles doubles --
+ * one slot per block, added in slot order: no atomics, bit-reproducible with or without dqc_set_deterministic.  Every argument is
+ * checked before anything is launched (negative counts, ldv, same mode with differing shapes: DQC_EINVAL).  Only enqueues. */
+size_t dqc_mp2_work_doubles(int noi, int noj, int nva, int nvb, int same);
+int dqc_mp2_pair_energies(double *d_eos, double *d_ess, const double *d_bi, const double *d_bj, const double *d_eoi,
+                          const double *d_eoj, const double *d_eva, const double *d_evb, int noi, int noj, int nva, int nvb,
+                          int ldva, int ldvb, int naux, int same, double *d_work, void *stream);
+
 /* ---- nuclear gradients of the SCF energy   ------------------------------------
  * The reference differentiates through its "ip" derivative integrals (molintor.py:463-500) and the implicit-function
  * backward of the SCF fixed point (scf_qccalc.py:63-67, 109-113); at convergence that is
