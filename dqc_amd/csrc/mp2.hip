@@ -23,6 +23,17 @@
 // Padded virtuals (a >= nva or b >= nvb) are masked in the epilogue (their denominator is replaced by 1, their term by 0): whatever the
 // padding columns hold, they contribute exactly zero.  The partial sums of a block -- lanes by butterfly, waves in order -- go to its slot
 // of the work buffer, and mp2_sum_kernel adds the slots of a pair in slot order: no atomics, bit-reproducible as it stands.
+//
+// Amplitudes (mp2_amp_kernel, dqc_mp2_amplitudes): the same staging and the same two accumulators, same mode only, for the occupied
+// block i in [i0, i0 + ni) against every j -- ordered pairs, one block per (i, j, panel pair Ap <= Bp) -- but the epilogue STORES
+//     T[i - i0, j, a, b] = V_ab / D_ab,       Tt[i - i0, j, a, b] = (c_os + c_ss) T_ab - c_ss T_ba        (two (ni, noj, ldv, ldv) buffers)
+// THE CHOICE FOR THE LOWER TRIANGLE: tiles B < A are not computed.  acc2 of the tile pair A < B IS the tile (B, A) of V, held
+// transposed (V_ba in the lane of V_ab), so the wave stores (a, b) straight from its registers and (b, a) through a 16 x 17 LDS
+// scratch of its own: written [b][a], read back by rows.  Every store instruction of a wave is then four full 128-byte rows (the 16
+// lanes of equal lane >> 4 write 16 consecutive b), each V element costs one MFMA pass (2 naux flop), and T^{ij}_{ab}, T^{ji}_{ba}
+// are bit-equal: the same products in the same order, and D is formed as (eps_i + eps_j) - (eps_a + eps_b), symmetric term by term.
+// The (ldv, ldv) faces are written whole: a >= nv or b >= nv is stored as 0.0 whatever the inputs' padding columns hold (tiles that
+// hold no real virtual skip their MFMAs).  Every element is written once, by one lane: no atomics, bit-reproducible.
 #include "common.hpp"
 #include "grid_common.hpp"
 
@@ -199,6 +210,125 @@ __global__ __launch_bounds__(64) void mp2_sum_kernel(double *__restrict__ eos, d
     }
 }
 
+struct Mp2AmpArgs {
+    const double *b, *eo, *ev;
+    double *t, *tt;      // [i - i0][j][a][b], faces of ldv x ldv
+    double c1, c2;       // Tt = c1 T - c2 T^T: c_os + c_ss, c_ss
+    int noj, nv, ldv, naux, i0;
+    long long ntp;       // panel pairs per occupied pair
+};
+
+// a wave's LDS traffic is in order; this keeps the compiler from moving its own accesses of the transpose scratch across the point
+DQC_DEV void mp2_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(256, 2) void mp2_amp_kernel(Mp2AmpArgs g) {
+    __shared__ __align__(16) double s_p[4][MP2_KC][MP2_LS];  // [Bi A][Bj B][Bj A][Bi B]
+    __shared__ double s_tr[4][16][17];                       // per wave: one tile on its way to the transposed position
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
+    const long long pair = blockIdx.x / g.ntp, tp = blockIdx.x - pair * g.ntp;  // pair = (i - i0) noj + j
+    const int il = (int)(pair / g.noj), j = (int)(pair - (long long)il * g.noj), i = g.i0 + il;
+    int pa, pb;
+    mp2_tri(tp, pa, pb);
+    const double *slab_i = g.b + (size_t)i * g.naux * g.ldv, *slab_j = g.b + (size_t)j * g.naux * g.ldv;
+    const double *src[4] = {slab_i, slab_j, slab_j, slab_i};
+    const int scol[4] = {pa * MP2_PW, pb * MP2_PW, pa * MP2_PW, pb * MP2_PW};
+    const int tA = 4 * pa + wave;
+    bool inside[4], live[4];  // the tile pair is this wave's to store; it holds a real virtual on both sides
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const int tB = 4 * pb + t;
+        inside[t] = 16 * tA < g.ldv && 16 * tB < g.ldv && tA <= tB;
+        live[t] = inside[t] && 16 * tA < g.nv && 16 * tB < g.nv;
+    }
+    const bool any = live[0] || live[1] || live[2] || live[3];
+    v4d acc1[4], acc2[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc1[t] = acc2[t] = v4d{0.0, 0.0, 0.0, 0.0};
+
+    double2 nx[4][2];
+    auto fetch = [&](int c0) {
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
+                nx[p][u] = mp2_load2(src[p], g.ldv, g.naux, c0 + k, scol[p] + c2);
+            }
+    };
+    fetch(0);
+    for (int c0 = 0; c0 < g.naux; c0 += MP2_KC) {
+        __syncthreads();  // (the previous chunk has been read by every wave)
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
+                *reinterpret_cast<double2 *>(&s_p[p][k][c2]) = nx[p][u];
+            }
+        __syncthreads();
+        if (c0 + MP2_KC < g.naux) fetch(c0 + MP2_KC);
+        if (!any) continue;
+        const int nk = min(MP2_KC, (g.naux - c0 + 3) & ~3);
+        for (int k0 = 0; k0 < nk; k0 += 4) {
+            const double ai = s_p[0][k0 + q][16 * wave + l15], aj = s_p[2][k0 + q][16 * wave + l15];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                if (!live[t]) continue;  // (wave-uniform)
+                acc1[t] = mfma_f64(ai, s_p[1][k0 + q][16 * t + l15], acc1[t]);
+                acc2[t] = mfma_f64(aj, s_p[3][k0 + q][16 * t + l15], acc2[t]);
+            }
+        }
+    }
+    // epilogue: lane (l15, q), register r holds a = 16 tA + q + 4 r, b = 16 tB + l15 (acc1: V_ab, acc2: V_ba)
+    const size_t ld = (size_t)g.ldv;
+    double *ot = g.t + (size_t)pair * ld * ld, *ott = g.tt + (size_t)pair * ld * ld;
+    const double eij = g.eo[i] + g.eo[j];
+    double ea[4];
+    bool oka[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int a = 16 * tA + q + 4 * r;
+        oka[r] = a < g.nv;
+        ea[r] = oka[r] ? g.ev[a] : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        if (!inside[t]) continue;  // (wave-uniform)
+        const int tB = 4 * pb + t, b = 16 * tB + l15;
+        const bool okb = b < g.nv;
+        const double eb = okb ? g.ev[b] : 0.0;
+        double xt[4], yt[4];  // the transposed position's T and Tt
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const bool ok = oka[r] && okb;
+            const double d = ok ? eij - (ea[r] + eb) : 1.0;
+            const double x = ok ? acc1[t][r] / d : 0.0, y = ok ? acc2[t][r] / d : 0.0;
+            const size_t o = (size_t)(16 * tA + q + 4 * r) * ld + b;
+            ot[o] = x;
+            ott[o] = ok ? g.c1 * x - g.c2 * y : 0.0;
+            xt[r] = y;
+            yt[r] = ok ? g.c1 * y - g.c2 * x : 0.0;
+        }
+        if (tA == tB) continue;
+        // (b, a): scratch [b][a] <- the lane's column, then rows b = 16 tB + q + 4 r, 16 consecutive a per 16 lanes
+#pragma unroll
+        for (int r = 0; r < 4; r++) s_tr[wave][l15][q + 4 * r] = xt[r];
+        mp2_wave_sync();
+#pragma unroll
+        for (int r = 0; r < 4; r++) ot[(size_t)(16 * tB + q + 4 * r) * ld + 16 * tA + l15] = s_tr[wave][q + 4 * r][l15];
+        mp2_wave_sync();
+#pragma unroll
+        for (int r = 0; r < 4; r++) s_tr[wave][l15][q + 4 * r] = yt[r];
+        mp2_wave_sync();
+#pragma unroll
+        for (int r = 0; r < 4; r++) ott[(size_t)(16 * tB + q + 4 * r) * ld + 16 * tA + l15] = s_tr[wave][q + 4 * r][l15];
+        mp2_wave_sync();
+    }
+}
+
 // (occupied pairs, panel pairs per occupied pair); false: an argument is out of range
 static bool mp2_counts(int noi, int noj, int nva, int nvb, int same, long long &npair, long long &ntp, int &npa, int &npb) {
     if (noi < 0 || noj < 0 || nva < 0 || nvb < 0) return false;
@@ -259,6 +389,32 @@ int dqc_mp2_pair_energies(double *d_eos, double *d_ess, const double *d_bi, cons
     DQC_CHECK_LAUNCH();
     hipLaunchKernelGGL(mp2_sum_kernel, dim3((unsigned)((npair + 63) / 64)), dim3(64), 0, st, d_eos, d_ess, (const double *)d_work, npair,
                        ntp, noj, same);
+    DQC_CHECK_LAUNCH();
+    return DQC_OK;
+}
+
+int dqc_mp2_amplitudes(double *d_t, double *d_tt, size_t out_doubles, const double *d_bov, const double *d_eo, const double *d_ev,
+                       int nocc, int nv, int ldv, int naux, int i0, int ni, double c_os, double c_ss, void *stream) {
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    if (nocc < 0 || nv < 0 || ldv < 0 || naux < 0 || i0 < 0 || ni < 0) { set_error("dqc_mp2_amplitudes: negative count"); return DQC_EINVAL; }
+    if (ldv % 16 || ldv < nv) { set_error("dqc_mp2_amplitudes: ldv must be a multiple of 16 and at least nv"); return DQC_EINVAL; }
+    if ((long long)i0 + ni > nocc) { set_error("dqc_mp2_amplitudes: the occupied block [i0, i0 + ni) leaves the occupied space"); return DQC_EINVAL; }
+    const size_t need = (size_t)ni * (size_t)nocc * (size_t)ldv * (size_t)ldv;
+    if (need > out_doubles) { set_error("dqc_mp2_amplitudes: the output buffers are smaller than ni * nocc * ldv * ldv doubles"); return DQC_EINVAL; }
+    if (need == 0) return DQC_OK;  // (empty outputs)
+    if (!d_t || !d_tt) { set_error("dqc_mp2_amplitudes: null output"); return DQC_EINVAL; }
+    if (nv == 0 || naux == 0) {
+        DQC_HIP(hipMemsetAsync(d_t, 0, sizeof(double) * need, st));
+        DQC_HIP(hipMemsetAsync(d_tt, 0, sizeof(double) * need, st));
+        return DQC_OK;
+    }
+    if (!d_bov || !d_eo || !d_ev) { set_error("dqc_mp2_amplitudes: null pointer argument"); return DQC_EINVAL; }
+    if ((size_t)d_bov % 16) { set_error("dqc_mp2_amplitudes: the tensor must be 16-byte aligned"); return DQC_EINVAL; }
+    const long long np = (ldv + MP2_PW - 1) / MP2_PW, ntp = np * (np + 1) / 2, nblk = (long long)ni * nocc * ntp;
+    if (nblk > 2147483647LL) { set_error("dqc_mp2_amplitudes: more blocks than one launch holds"); return DQC_EINVAL; }
+    Mp2AmpArgs g{d_bov, d_eo, d_ev, d_t, d_tt, c_os + c_ss, c_ss, nocc, nv, ldv, naux, i0, ntp};
+    hipLaunchKernelGGL(mp2_amp_kernel, dim3((unsigned)nblk), dim3(256), 0, st, g);
     DQC_CHECK_LAUNCH();
     return DQC_OK;
 }

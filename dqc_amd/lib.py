@@ -103,6 +103,7 @@ def load():
     lib.dqc_mp2_work_doubles.argtypes = [c_int] * 5
     lib.dqc_mp2_work_doubles.restype = c_sz
     lib.dqc_mp2_pair_energies.argtypes = [c_dp] * 8 + [c_int] * 8 + [c_dp, c_vp]
+    lib.dqc_mp2_amplitudes.argtypes = [c_dp, c_dp, c_sz, c_dp, c_dp, c_dp] + [c_int] * 6 + [ctypes.c_double, ctypes.c_double, c_vp]
     lib.dqc_eri_tiles_to_dense.argtypes = [c_dp, c_dp, c_int, c_vp]
     lib.dqc_jk_from_tiles.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_vp]
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
@@ -434,6 +435,41 @@ def mp2_pair_energies(bi, bj, eps_oi, eps_oj, eps_va, eps_vb, same, work=None):
         _check(L.dqc_mp2_pair_energies(_ptr(eos), _ptr(ess), _ptr(bi), _ptr(bj), _ptr(eps_oi), _ptr(eps_oj), _ptr(eps_va), _ptr(eps_vb),
                                        noi, noj, nva, nvb, ldva, ldvb, naux, int(same), _ptr(work), st_), "dqc_mp2_pair_energies")
     return eos, ess
+
+
+def mp2_amplitudes(bov, eo, ev, i0, ni, c_os=1.0, c_ss=1.0, out=None):
+    """RI-MP2 amplitudes of the occupied block [i0, i0 + ni) against every occupied orbital (csrc/mp2.hip: dqc_mp2_amplitudes), restricted:
+    bov (nocc, naux, ldv) as `mp2_pair_energies` takes it, eo (nocc), ev (nv <= ldv) -> (t, tt), both (ni, nocc, ldv, ldv):
+    t[i - i0, j, a, b] = V^{ij}_{ab} / D^{ij}_{ab}, tt = (c_os + c_ss) t - c_ss t^T (2 T - T^T by default).  Rows and columns >= nv are
+    written as exactly 0.0.  out: a pair of contiguous float64 device tensors of at least ni * nocc * ldv^2 elements each to write into
+    (the results are views of them).  No atomics: bit-reproducible.  The arguments are checked before anything is launched"""
+    if bov.dim() != 3 or bov.shape[2] % 16:
+        raise DqcAmdError("mp2_amplitudes: bov must be (nocc, naux, ldv) with ldv a multiple of 16, got %s" % (tuple(bov.shape),))
+    nocc, naux, ldv = (int(x) for x in bov.shape)
+    nv, i0, ni = int(ev.numel()), int(i0), int(ni)
+    if int(eo.numel()) != nocc:
+        raise DqcAmdError("mp2_amplitudes: %d occupied energies for %d slabs" % (eo.numel(), nocc))
+    if nv > ldv:
+        raise DqcAmdError("mp2_amplitudes: %d virtual energies for slabs of %d columns" % (nv, ldv))
+    if i0 < 0 or ni < 0 or i0 + ni > nocc:
+        raise DqcAmdError("mp2_amplitudes: the block [%d, %d) is not inside the %d occupied orbitals" % (i0, i0 + ni, nocc))
+    if bov.data_ptr() % 16:
+        raise DqcAmdError("mp2_amplitudes: the tensor must be 16-byte aligned")
+    need = ni * nocc * ldv * ldv
+    if out is None:
+        out = (torch.empty(need, dtype=torch.float64, device=bov.device), torch.empty(need, dtype=torch.float64, device=bov.device))
+    t, tt = out
+    for o in (t, tt):
+        if o.numel() < need or o.device != bov.device or o.dtype != torch.float64 or not o.is_contiguous():
+            raise DqcAmdError("mp2_amplitudes: each output needs %d contiguous float64 elements on the device of bov, got %s"
+                              % (need, tuple(o.shape)))
+    if need and t.data_ptr() == tt.data_ptr():
+        raise DqcAmdError("mp2_amplitudes: the two outputs must be different buffers")
+    with _on(bov.device) as st_:
+        _check(load().dqc_mp2_amplitudes(_ptr(t), _ptr(tt), min(t.numel(), tt.numel()), _ptr(bov), _ptr(eo), _ptr(ev), nocc, nv, ldv, naux,
+                                         i0, ni, float(c_os), float(c_ss), st_), "dqc_mp2_amplitudes")
+    shape = (ni, nocc, ldv, ldv)
+    return t.reshape(-1)[:need].view(shape), tt.reshape(-1)[:need].view(shape)
 
 
 def cart2sph_matrix(tab, device):

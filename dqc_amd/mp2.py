@@ -21,7 +21,11 @@ Steps: the tensor B (the Hamiltonian's own when it was built with densityfit(exc
 energies by the fused kernel dqc_mp2_pair_energies (csrc/mp2.hip, O(o^2 v^2 naux): the (ia|jb) are never stored).  `Bov` must fit
 in device memory; there is no batching over occupied blocks.  No gradient and no autograd: the result is detached.
 
-`pair_energies_reference` is the yardstick of the kernel: plain torch on any device, V formed per occupied orbital i."""
+`pair_energies_reference` is the yardstick of the kernel: plain torch on any device, V formed per occupied orbital i.
+
+One-particle densities (`mp2_density`, restricted): the unrelaxed occupied-occupied and virtual-virtual blocks and, for Hartree-Fock on
+exact integrals, the orbital-relaxed density (natural orbitals, dipole moments) -- formulas and factors above `density_reference`, the
+yardstick of that path.  The amplitudes come from dqc_mp2_amplitudes one block of occupied orbitals at a time (that path IS batched)."""
 import torch
 
 from . import lib
@@ -215,7 +219,218 @@ def mp2(qc, frozen=0, auxbasis=None, c_os=1.0, c_ss=1.0):
     return MP2(e_scf, e_os, e_ss, pair_os, pair_ss, c_os, c_ss, frozen, df)
 
 
+# ------------------------------------------------------------------------------------------------ one-particle densities
+# Restricted closed shell; i, j, k active occupied, a, b, c virtual; T = V / D, Tt = (c_os + c_ss) T - c_ss T^T (2 T - T^T for MP2):
+#
+#     e_corr = sum_ijab V^{ij}_{ab} Tt^{ij}_{ab}
+#     P_ab =  2 sum_ij sum_c T^{ij}_{ac} Tt^{ij}_{bc}          P_ij = -2 sum_k sum_ab T^{ki}_{ab} Tt^{kj}_{ab}       (both symmetrised)
+#     Gamma[i, P, a] = sum_jb Tt^{ij}_{ab} Bov[j, P, b]          (sum Gamma Bov = e_corr)
+#
+# P_oo and P_vv are the derivatives of the Hylleraas functional by the occupied-occupied and virtual-virtual Fock blocks (P_aa =
+# d e_corr / d eps_a, P_ii = d e_corr / d eps_i), the UNRELAXED density.  The relaxed one adds the response of the SCF orbitals: under
+# a rotation kappa_ai (the variables of response.OrbitalHessian: dC_i = sum_a C_a kappa_ai, dC_a = -sum_i C_i kappa_ai) the functional
+# changes by L . kappa,
+#
+#     L_ai = 4 [ (C_v^T G[Pbar] C_o)_ai + X_ai - Y_ai ],     Pbar = C_v P_vv C_v^T + C_o P_oo C_o^T,   G[D] = J[D] - K[D] / 2
+#     X_ci = sum_aP Gamma[i, P, a] B^P_ca,      Y_ak = sum_iP Gamma[i, P, a] B^P_ik
+#
+# (the first term: the Fock blocks follow the SCF density; X - Y: 2 sum Tt dV), and a one-electron perturbation lambda O moves the
+# orbitals by d kappa / d lambda = -4 H^-1 O_vo (H = 4 (A + B), the Hessian of OrbitalHessian, whose gradient is 4 F_ai).  So
+#
+#     H z = -L,     P_ai = P_ia = 2 z_ai,     d E_MP2 / d lambda = tr[(D_SCF + C P C^T) O]
+#
+# X is evaluated through the AO tensor -- Gamma back-transformed in its virtual index, contracted with B[P, mu, nu] over chunks of P --
+# and Y from B^P_ik, so no B_vv is ever stored.  tests/test_gpu_mp2_density.py holds the factors against finite-field derivatives.
+
+
+def density_reference(bov, eo, ev, c_os=1.0, c_ss=1.0):
+    """(P_oo (no, no), P_vv (nv, nv), Gamma (no, naux, nv)) of the formulas above in plain torch, on the device of the inputs: the
+    yardstick of `mp2_density`.  bov (no, naux, >= nv): columns past the number of virtual energies (padding) are ignored.  The dense
+    T^{i.} is formed one occupied orbital i at a time -- (no, nv, nv) doubles"""
+    no, nv = int(bov.shape[0]), int(ev.numel())
+    b = bov[:, :, :nv]
+    p_oo = torch.zeros((no, no), dtype=b.dtype, device=b.device)
+    p_vv = torch.zeros((nv, nv), dtype=b.dtype, device=b.device)
+    gamma = torch.zeros((no, int(b.shape[1]), nv), dtype=b.dtype, device=b.device)
+    for i in range(no):
+        v = torch.einsum("pa,jpb->jab", b[i], b)
+        t = v / (eo[i] + eo[:, None, None] - ev[None, :, None] - ev[None, None, :])
+        tt = (c_os + c_ss) * t - c_ss * t.transpose(1, 2)
+        p_vv += 2.0 * torch.einsum("jac,jbc->ab", t, tt)
+        p_oo -= 2.0 * torch.einsum("jab,kab->jk", t, tt)
+        gamma[i] = torch.einsum("jab,jpb->pa", tt, b)
+    return 0.5 * (p_oo + p_oo.t()), 0.5 * (p_vv + p_vv.t()), gamma
+
+
+class MP2Density:
+    """what `mp2_density` returns (detached tensors on the device of the calculation):
+    `dm_mo` (n, n): the correction to the SCF density in the basis of the canonical orbitals (all of them, in energy order; the rows
+    and columns of frozen orbitals are zero); occupied-occupied and virtual-virtual blocks always, the occupied-virtual ones when relaxed;
+    `dm_ao`: the SCF density plus the correction, AO basis; `natural_occupations` (descending, they sum to the electron count) and
+    `natural_orbitals` (AO coefficients, columns, C^T S C = 1) of it; `dipole(unit)`; `e_corr` = sum Gamma Bov (equal to mp2().e_corr);
+    `relaxed`, `z_residual` (the relative residual the Z-vector solve stopped at; None when unrelaxed); `c_os`, `c_ss`, `frozen`,
+    `naux`, `block` (occupied orbitals per amplitude block)"""
+
+    def __init__(self, dm_mo, dm_ao, occ, orbs, dip_au, e_corr, relaxed, z_residual, c_os, c_ss, frozen, naux, block):
+        self.dm_mo, self.dm_ao, self.natural_occupations, self.natural_orbitals = dm_mo, dm_ao, occ, orbs
+        self._dip_au, self.e_corr, self.relaxed, self.z_residual = dip_au, e_corr, bool(relaxed), z_residual
+        self.c_os, self.c_ss, self.frozen, self.naux, self.block = float(c_os), float(c_ss), int(frozen), int(naux), int(block)
+
+    def dipole(self, unit="Debye"):
+        """electric dipole moment (3,) of the MP2 density, nuclear part included: sign and units of `properties.edipole`"""
+        from .properties import _DIPOLE_UNITS, _unit
+        return self._dip_au * _unit(_DIPOLE_UNITS, unit, "dipole")
+
+    def __repr__(self):
+        return "MP2Density(%s, e_corr=%.10f, c_os=%g, c_ss=%g, frozen=%d, naux=%d)" % (
+            "relaxed" if self.relaxed else "unrelaxed", float(self.e_corr), self.c_os, self.c_ss, self.frozen, self.naux)
+
+
+def _free_bytes(dev):
+    free, _total = torch.cuda.mem_get_info(dev)
+    return free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)  # (cached blocks are reusable)
+
+
+def unrelaxed_blocks(bov, eo, ev, c_os=1.0, c_ss=1.0, block=None, amplitudes=None):
+    """(P_oo, P_vv (nv, nv), Gamma (no, naux, ldv), occupied orbitals per block) from the amplitude kernel, one occupied block at a
+    time: per block lib.mp2_amplitudes, then library GEMMs on the padded shapes -- P_vv += 2 T^T Tt over the rows (k, j, c), split [by
+    T^{kj}_{ca} = T^{jk}_{ac} the sum over all blocks is the P_ab above], P_oo -= 2 sum_k T[k] Tt[k]^T over (a, b), Gamma[blk] +=
+    Tt[:, j] Bov[j]^T for every j.  Only Bov and Gamma (the same size) stay resident; the two amplitude buffers are reused.
+    `amplitudes`: a stand-in with the signature of lib.mp2_amplitudes (tools/gpu_mp2_density_time.py times an all-torch one)"""
+    amplitudes = lib.mp2_amplitudes if amplitudes is None else amplitudes
+    no, naux, ldv = (int(x) for x in bov.shape)
+    nv = int(ev.numel())
+    per = 2 * 8 * no * ldv * ldv + 8 * ldv * naux          # T and Tt of one occupied orbital, its slab of Gamma^T
+    if block is None:
+        fixed = 8 * no * naux * ldv * 2 + 8 * ldv * ldv    # Gamma, Bov transposed
+        block = (_free_bytes(bov.device) - fixed) // 2 // max(per, 1)
+    nb = max(1, min(no, int(block)))
+    p_oo = torch.zeros((no, no), dtype=bov.dtype, device=bov.device)
+    p_vv = torch.zeros((ldv, ldv), dtype=bov.dtype, device=bov.device)
+    gamma = torch.empty_like(bov)
+    bovt = bov.transpose(1, 2).contiguous()                # [j, b, P]
+    out = None
+    if amplitudes is lib.mp2_amplitudes:
+        out = tuple(torch.empty(nb * no * ldv * ldv, dtype=bov.dtype, device=bov.device) for _ in range(2))
+    for i0 in range(0, no, nb):
+        ni = min(nb, no - i0)
+        t, tt = amplitudes(bov, eo, ev, i0, ni, c_os, c_ss, out=out)
+        # both sums are long (ni no ldv and ldv^2 terms) with small results: as single GEMMs they run on a handful of workgroups (20 and
+        # 5 ms at nocc 46, ldv 176 against 0.7 and 1.3 ms), so the sum is split into batches and the partial results added
+        split = max(d for d in range(1, min(ni * no, 128) + 1) if (ni * no) % d == 0)
+        p_vv += 2.0 * torch.bmm(t.view(split, -1, ldv).transpose(1, 2), tt.view(split, -1, ldv)).sum(0)
+        for k in range(ni):   # batches: the first virtual index
+            p_oo -= 2.0 * torch.bmm(t[k].transpose(0, 1), tt[k].permute(1, 2, 0)).sum(0)
+        g = torch.zeros((ni, ldv, naux), dtype=bov.dtype, device=bov.device)
+        for j in range(no):
+            g.baddbmm_(tt[:, j], bovt[j].expand(ni, ldv, naux))
+        gamma[i0:i0 + ni] = g.transpose(1, 2)
+    return 0.5 * (p_oo + p_oo.t()), (0.5 * (p_vv + p_vv.t()))[:nv, :nv].contiguous(), gamma, nb
+
+
+def _lagrangian(h, b, co, cv, p_oo, p_vv, gamma):
+    """L_ai (nv, no) of the comment above; b (naux, nao, nao), gamma (no, naux, ldv), all orbitals active"""
+    no, nv, naux, nao = int(co.shape[1]), int(cv.shape[1]), int(b.shape[0]), int(b.shape[1])
+    pbar = (cv @ p_vv @ cv.t() + co @ p_oo @ co.t()).reshape(1, nao, nao).contiguous()
+    jm, km = lib.jk_multi(h._tiles, pbar, pbar, h._multi_work(1, 1))
+    lag = cv.t() @ (jm[0] - 0.5 * km[0]) @ co
+    w = torch.zeros((nao, no), dtype=b.dtype, device=b.device)   # W[mu, i] = sum_P,nu B[P, mu, nu] Gamma^P[i, nu]
+    y = torch.zeros((nv, no), dtype=b.dtype, device=b.device)
+    step = max(1, min(naux, (1 << 25) // max(nao * max(nao, no), 1)))
+    cvt = cv.t().contiguous()
+    for p0 in range(0, naux, step):
+        bp = b[p0:p0 + step]
+        gp = gamma[:, p0:p0 + step, :nv]                                  # (no, pc, nv)
+        gao = torch.matmul(gp, cvt)                                       # (no, pc, nao): the virtual index back in the AO basis
+        w += torch.einsum("pmn,ipn->mi", bp, gao)
+        boo = torch.matmul(co.t(), torch.matmul(bp, co))                  # (pc, no, no): B^P_ik
+        y += torch.einsum("ipa,pik->ak", gp, boo)
+    return 4.0 * (lag + cv.t() @ w - y)
+
+
+def _density(qc, frozen, auxbasis, c_os, c_ss, relaxed, tol, block):
+    from .properties import _total_ao_density
+    from .response import OrbitalHessian
+    h = qc._engine.hamilton
+    df = _b_tensor(qc, auxbasis)
+    b = df._b
+    co, cv, eo, ev = _orbitals(qc, frozen)[0]
+    c_frozen = _orbitals(qc, 0)[0][0][:, :frozen]
+    bov = transform_ov(b, co, cv)
+    p_oo, p_vv, gamma, nb = unrelaxed_blocks(bov, eo, ev, c_os, c_ss, block)
+    e_corr = (gamma * bov).sum().reshape(1)
+    nf, no, nv = int(c_frozen.shape[1]), int(co.shape[1]), int(cv.shape[1])
+    n = nf + no + nv
+    dm_mo = torch.zeros((n, n), dtype=b.dtype, device=b.device)
+    dm_mo[nf:nf + no, nf:nf + no] = p_oo
+    dm_mo[nf + no:, nf + no:] = p_vv
+    z_residual = None
+    if relaxed:
+        lag = _lagrangian(h, b, co, cv, p_oo, p_vv, gamma)
+        c_all, e_all = torch.cat([co, cv], dim=1), torch.cat([eo, ev])
+        oh = OrbitalHessian(qc, orbitals=(c_all, e_all))
+        z = oh.solve(-lag.reshape(1, -1), tol=tol).reshape(nv, no)
+        z_residual = float(oh.last_residual)
+        dm_mo[nf + no:, nf:nf + no] = 2.0 * z
+        dm_mo[nf:nf + no, nf + no:] = 2.0 * z.t()
+    c_all = torch.cat([c_frozen, co, cv], dim=1)
+    _, d_scf = _total_ao_density(qc)
+    d_scf = d_scf.detach()
+    dm_ao = d_scf + c_all @ dm_mo @ c_all.t()
+    occ_mo = dm_mo.clone()
+    occ_mo.diagonal()[:nf + no] += 2.0
+    occ, u = torch.linalg.eigh(occ_mo)
+    occ, orbs = occ.flip(0), (c_all @ u).flip(1)
+    mol = qc.get_system()
+    r = lib.int1e("r0", h._tab, h.device)
+    pos = mol.atompos.detach().to(h.device)
+    dip = -torch.einsum("dab,ba->d", r, dm_ao) + torch.einsum("ad,a->d", pos, mol.atomzs.to(pos.dtype).to(h.device))
+    return MP2Density(dm_mo, dm_ao, occ, orbs.contiguous(), dip, e_corr, relaxed, z_residual, c_os, c_ss, frozen, b.shape[0], nb)
+
+
+def mp2_density(qc, frozen=0, auxbasis=None, c_os=1.0, c_ss=1.0, relaxed=True, tol=1e-9, block=None):
+    """RI-MP2 one-particle density of the converged restricted HF / KS calculation `qc`: an `MP2Density` (natural orbitals and occupation
+    numbers, dipole moment).  `frozen`, `auxbasis`, `c_os`, `c_ss` as `mp2` takes them.  relaxed=True adds the response of the SCF
+    orbitals (the density whose expectation values are the derivatives of the MP2 energy: a Z-vector solve on the orbital Hessian,
+    `tol` its relative residual) -- for Hartree-Fock on the exact-integral tile store without frozen orbitals; relaxed=False: the
+    occupied-occupied and virtual-virtual blocks alone (any reference `mp2` takes, restricted).  The amplitudes are formed one block of
+    occupied orbitals at a time (csrc/mp2.hip: dqc_mp2_amplitudes) and never held as a whole: only Bov and a tensor of its size stay
+    resident; `block`: occupied orbitals per block (None: as many as the free device memory holds; any value >= 1 gives the same
+    matrices to round-off).  Memoised on the converged state per argument set; nothing is differentiable: the result is detached."""
+    assert qc._has_run, "run() the calculation first"
+    frozen = int(frozen)
+    if frozen < 0:
+        raise ValueError("mp2_density: frozen must be >= 0, got %d" % frozen)
+    eng = qc._engine
+    if eng.polarized:
+        raise NotImplementedError("mp2_density: unrestricted calculations are not supported (restricted closed shell only)")
+    if relaxed and frozen > 0:
+        raise NotImplementedError("mp2_density: the relaxed density with frozen orbitals is not supported (the frozen-active rotations "
+                                  "are not in the Z-vector equations); use frozen=0 or relaxed=False")
+    if relaxed and eng.is_ks:
+        raise NotImplementedError("mp2_density: the relaxed density on a Kohn-Sham reference is not supported (the double-hybrid response "
+                                  "needs exchange-correlation terms in the Lagrangian); use relaxed=False")
+    _unsupported(qc)
+    h = eng.hamilton
+    if relaxed:
+        if h.df is not None or getattr(h, "_direct", False) or getattr(h, "_tiles_store", None) is None:
+            raise NotImplementedError("mp2_density: the relaxed density needs the orbital Hessian over the resident exact integrals, which a "
+                                      "density-fitted or direct-SCF Hamiltonian does not have: pass an exact-integral calculation and "
+                                      "`auxbasis=`, or use relaxed=False")
+    from .response import state_memo
+    memo = state_memo(qc)
+    own = h.df is not None and h.df.exchange
+    key = ("mp2_density", frozen, None if own else (auxbasis if isinstance(auxbasis, str) or auxbasis is None else id(auxbasis)),
+           float(c_os), float(c_ss), bool(relaxed), float(tol) if relaxed else None, None if block is None else int(block))
+    if key not in memo:
+        with torch.no_grad():
+            memo[key] = _density(qc, frozen, auxbasis, float(c_os), float(c_ss), bool(relaxed), float(tol), block)
+    return memo[key]
+
+
 # `dqc_amd.mp2` is this function once the package has imported it: the yardstick stays reachable as dqc_amd.mp2.pair_energies_reference
 mp2.pair_energies_reference = pair_energies_reference
+mp2.density_reference = density_reference
 
-__all__ = ["mp2", "MP2", "pair_energies_reference", "energies_reference", "components", "transform_ov"]
+__all__ = ["mp2", "MP2", "pair_energies_reference", "energies_reference", "components", "transform_ov", "mp2_density", "MP2Density",
+           "density_reference", "unrelaxed_blocks"]

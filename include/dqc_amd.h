@@ -316,6 +316,17 @@ int dqc_mp2_pair_energies(double *d_eos, double *d_ess, const double *d_bi, cons
                           const double *d_eoj, const double *d_eva, const double *d_evb, int noi, int noj, int nva, int nvb,
                           int ldva, int ldvb, int naux, int same, double *d_work, void *stream);
 
+/* RI-MP2 amplitudes of the occupied block i in [i0, i0 + ni) against every occupied j, restricted (one tensor on both sides):
+ *   T[i - i0, j, a, b] = V^{ij}_{ab} / D^{ij}_{ab},   Tt[i - i0, j, a, b] = (c_os + c_ss) T^{ij}_{ab} - c_ss T^{ij}_{ba}
+ * with V and D as above (D formed as (eo[i] + eo[j]) - (ev[a] + ev[b]): T^{ij}_{ab} and T^{ji}_{ba} are bit-equal).  d_bov (nocc, naux,
+ * ldv) as d_bi above; d_eo (nocc), d_ev (nv).  d_t, d_tt: (ni, nocc, ldv, ldv) each, `out_doubles` the capacity of EACH in doubles;
+ * both are overwritten whole -- rows and columns >= nv hold exactly 0.0 whatever the padding columns of d_bov hold.  Every element is
+ * written once: no atomics, bit-reproducible.  ni, nocc or ldv zero: nothing to write; nv or naux zero: zeros (no kernel).  Every
+ * argument is checked before anything is launched (negative counts, ldv no multiple of 16 or < nv, i0 + ni > nocc, out_doubles <
+ * ni nocc ldv^2: DQC_EINVAL).  Only enqueues. */
+int dqc_mp2_amplitudes(double *d_t, double *d_tt, size_t out_doubles, const double *d_bov, const double *d_eo, const double *d_ev,
+                       int nocc, int nv, int ldv, int naux, int i0, int ni, double c_os, double c_ss, void *stream);
+
 /* ---- nuclear gradients of the SCF energy   ------------------------------------
  * The reference differentiates through its "ip" derivative integrals (molintor.py:463-500) and the implicit-function
  * backward of the SCF fixed point (scf_qccalc.py:63-67, 109-113); at convergence that is
