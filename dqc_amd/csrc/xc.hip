@@ -96,6 +96,7 @@ template <class S> DQC_DEV D5T<S> n_cbrt(D5T<S> a) { return cbrt5(a); }
 template <class S> DQC_DEV D5T<S> n_pow(D5T<S> a, double e) { return p5(a, e); }
 template <class S> DQC_DEV D5T<S> n_xasinhx(D5T<S> a) { return xasinhx5(a); }
 template <class S> DQC_DEV D5T<S> n_floor(D5T<S> a, double lo) { return s_val(a.v) < lo ? c5<S>(lo) : a; }
+template <class S> DQC_DEV D5T<S> n_floor_val(D5T<S> a, double lo) { if (s_val(a.v) < lo) s_set_val(a.v, lo); return a; }
 template <class S> DQC_DEV D5T<S> operator*(D5T<S> a, double b) { return b * a; }
 template <class S> DQC_DEV D5T<S> operator+(D5T<S> a, double b) { return b + a; }
 template <class S> DQC_DEV D5T<S> operator-(D5T<S> a, double b) { a.v = a.v - b; return a; }

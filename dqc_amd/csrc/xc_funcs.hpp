@@ -104,6 +104,10 @@ template <class S> DQC_DEV DualT<S> n_cbrt(DualT<S> a) { return dcbrt(a); }
 template <class S> DQC_DEV DualT<S> n_pow(DualT<S> a, double e) { return dpow(a, e); }
 template <class S> DQC_DEV DualT<S> n_xasinhx(DualT<S> a) { return dxasinhx(a); }
 template <class S> DQC_DEV DualT<S> n_floor(DualT<S> a, double lo) { return s_val(a.v) < lo ? mk<S>(lo) : a; }
+// the VALUE raised to lo, the derivatives kept: for a variable that enters through its square root and linearly as well (P86)
+DQC_DEV void s_set_val(double &a, double v) { a = v; }
+DQC_DEV void s_set_val(Tan &a, double v) { a.v = v; }
+template <class S> DQC_DEV DualT<S> n_floor_val(DualT<S> a, double lo) { if (s_val(a.v) < lo) s_set_val(a.v, lo); return a; }
 
 // ---------------------------------------------------------------------------------------------
 // Exchange GGAs as a TABLE of enhancement factors (round 4): e_x = -(3/4)(3/pi)^(1/3) rho^(4/3) F(s^2), s = |grad rho| / (2 k_F rho);
@@ -194,7 +198,9 @@ DQC_DEV T p86_gradient_term(T rho, T sigma, T dz, bool pol) {
     T rs = n_cbrt((3.0 / (4.0 * kPi)) / rho);
     T rs2 = rs * rs;
     T Cn = 0.001667 + (0.002568 + a * rs + b * rs2) / (1.0 + g * rs + d * rs2 + (1.0e4 * b) * (rs2 * rs));
-    T sg = n_floor(sigma, 1e-40);
+    // sigma = 0 keeps its derivative (v_sigma = C(n) / n^(4/3) there, which d v_grad = 2 v_sigma grad d rho needs); the floor only keeps
+    // sqrt'(sigma) finite and is far below any sigma of a density above the cutoff (at 1e-40 it reached 2e-7 of e in the tail)
+    T sg = n_floor_val(sigma, 1e-100);
     T r16 = n_pow(rho, 1.0 / 6.0);
     T phi = (1.745 * ft * cinf) * n_sqrt(sg) / (Cn * (rho * r16));
     T H = n_exp((-1.0) * phi) * Cn * sg / (rho * n_cbrt(rho));

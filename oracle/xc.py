@@ -757,9 +757,11 @@ def _lyp_dual(ra, rb, saa, sab, sbb):
     ir13 = rho.pow(-1.0 / 3)
     den = 1.0 + d * ir13
     delta = c * ir13 + d * ir13 / den
-    omega = (-(c * ir13)).fn(np.exp, np.exp) / den * rho.pow(-11.0 / 3)
+    r113 = rho * rho * rho / (ir13 * ir13)  # rho^(11/3) from the cube root (a power with a rounded exponent costs digits below)
+    omega = (-(c * ir13)).fn(np.exp, np.exp) / (den * r113)
     sig = saa + 2.0 * sab + sbb
-    br = ra * rb * (2.0 ** (11.0 / 3) * CF * (ra.pow(8.0 / 3) + rb.pow(8.0 / 3))
+    ca, cb = ra.pow(1.0 / 3), rb.pow(1.0 / 3)
+    br = ra * rb * (2.0 ** (11.0 / 3) * CF * (ra * ra * ca * ca + rb * rb * cb * cb)
                     + (47.0 / 18 - 7.0 / 18 * delta) * sig
                     - (2.5 - delta / 18.0) * (saa + sbb)
                     - (delta - 11.0) / 9.0 * (ra / rho * saa + rb / rho * sbb))
@@ -956,6 +958,9 @@ def _pz_channel(rs, i):
     return _sel(rs.v >= 1.0, hi, lo)
 
 
+_P86_SIGMA_FLOOR = 1e-100  # keeps sqrt'(sigma) finite (csrc/xc_funcs.hpp: p86_gradient_term)
+
+
 def _pz_p86_dual(u, d, suu, sud, sdd, p86):
     rho, zeta = _safe_zeta(u, d)
     rs = ((3.0 / (4.0 * np.pi)) / rho).pow(1.0 / 3)
@@ -967,8 +972,8 @@ def _pz_p86_dual(u, d, suu, sud, sdd, p86):
         rs2 = rs * rs
         Cn = 0.001667 + (0.002568 + a * rs + b * rs2) / (1.0 + g * rs + dd_ * rs2 + 1e4 * b * rs2 * rs)
         sig = suu + 2.0 * sud + sdd
-        fl = sig.v < _S2_FLOOR
-        sig = _sel(fl, Dual.const(_S2_FLOOR, sig), sig)
+        # the value raised to 1e-100 with the derivatives kept: v_sigma = C(n) / n^(4/3) at sigma = 0, and nothing of e lost in the tail
+        sig = Dual(np.maximum(sig.v, _P86_SIGMA_FLOOR), sig.d)
         phi = 1.745 * ft * cinf * sig.sqrt() / (Cn * rho.pow(7.0 / 6))
         dz = 2.0 ** (1.0 / 3) * ((0.5 * (1.0 + zeta)).pow(5.0 / 3) + (0.5 * (1.0 - zeta)).pow(5.0 / 3)).sqrt()
         e = e + (-phi).fn(np.exp, np.exp) * Cn * sig / (dz * rho.pow(4.0 / 3))
