@@ -104,6 +104,9 @@ def load():
     lib.dqc_mp2_work_doubles.restype = c_sz
     lib.dqc_mp2_pair_energies.argtypes = [c_dp] * 8 + [c_int] * 8 + [c_dp, c_vp]
     lib.dqc_mp2_amplitudes.argtypes = [c_dp, c_dp, c_sz, c_dp, c_dp, c_dp] + [c_int] * 6 + [ctypes.c_double, ctypes.c_double, c_vp]
+    lib.dqc_rpa_work_doubles.argtypes = [c_int] * 4
+    lib.dqc_rpa_work_doubles.restype = c_sz
+    lib.dqc_rpa_response.argtypes = [c_dp] * 5 + [c_int] * 5 + [ctypes.c_double, c_int, c_dp, c_vp]
     lib.dqc_eri_tiles_to_dense.argtypes = [c_dp, c_dp, c_int, c_vp]
     lib.dqc_jk_from_tiles.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_vp]
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
@@ -470,6 +473,42 @@ def mp2_amplitudes(bov, eo, ev, i0, ni, c_os=1.0, c_ss=1.0, out=None):
                                          i0, ni, float(c_os), float(c_ss), st_), "dqc_mp2_amplitudes")
     shape = (ni, nocc, ldv, ldv)
     return t.reshape(-1)[:need].view(shape), tt.reshape(-1)[:need].view(shape)
+
+
+def rpa_response(bov, eo, ev, freq, scale=1.0, out=None, accumulate=False, work=None):
+    """RI-dRPA response matrices (csrc/rpa.hip: dqc_rpa_response): bov (nocc, naux, ldv) as `mp2_pair_energies` takes it, eo (nocc),
+    ev (nv <= ldv), freq (nfreq) imaginary frequencies -> Q (nfreq, naux, naux),
+    Q[k] = scale sum_ia bov[i, :, a] g_ia(w_k) bov[i, :, a]^T, g_ia(w) = D_ia / (D_ia^2 + w^2), D_ia = ev[a] - eo[i]; both triangles,
+    bit-symmetric.  out: the tensor to write into; accumulate=True adds to `out` (the second spin) instead of overwriting it.
+    No atomics: bit-reproducible.  The arguments are checked before anything is launched"""
+    if bov.dim() != 3 or bov.shape[2] % 16:
+        raise DqcAmdError("rpa_response: bov must be (nocc, naux, ldv) with ldv a multiple of 16, got %s" % (tuple(bov.shape),))
+    nocc, naux, ldv = (int(x) for x in bov.shape)
+    nv, nfreq = int(ev.numel()), int(freq.numel())
+    if int(eo.numel()) != nocc:
+        raise DqcAmdError("rpa_response: %d occupied energies for %d slabs" % (eo.numel(), nocc))
+    if nv > ldv:
+        raise DqcAmdError("rpa_response: %d virtual energies for slabs of %d columns" % (nv, ldv))
+    if freq.dim() != 1:
+        raise DqcAmdError("rpa_response: freq must be one-dimensional, got %s" % (tuple(freq.shape),))
+    if bov.data_ptr() % 16:
+        raise DqcAmdError("rpa_response: the tensor must be 16-byte aligned")
+    accumulate = bool(accumulate)
+    if out is None:
+        if accumulate:
+            raise DqcAmdError("rpa_response: accumulate=True needs the tensor to add to (out=)")
+        out = torch.empty((nfreq, naux, naux), dtype=torch.float64, device=bov.device)
+    elif tuple(out.shape) != (nfreq, naux, naux) or out.device != bov.device or out.dtype != torch.float64 or not out.is_contiguous():
+        raise DqcAmdError("rpa_response: out must be a contiguous float64 (%d, %d, %d) tensor on the device of bov, got %s"
+                          % (nfreq, naux, naux, tuple(out.shape)))
+    L = load()
+    need = int(L.dqc_rpa_work_doubles(nocc, nv, naux, nfreq))
+    if need and (work is None or work.numel() < need):
+        work = torch.empty(need, dtype=torch.float64, device=bov.device)
+    with _on(bov.device) as st_:
+        _check(L.dqc_rpa_response(_ptr(out), _ptr(bov), _ptr(eo), _ptr(ev), _ptr(freq), nocc, nv, ldv, naux, nfreq, float(scale),
+                                  int(accumulate), _ptr(work) if need else None, st_), "dqc_rpa_response")
+    return out
 
 
 def cart2sph_matrix(tab, device):

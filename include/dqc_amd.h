@@ -327,6 +327,21 @@ int dqc_mp2_pair_energies(double *d_eos, double *d_ess, const double *d_bi, cons
 int dqc_mp2_amplitudes(double *d_t, double *d_tt, size_t out_doubles, const double *d_bov, const double *d_eo, const double *d_ev,
                        int nocc, int nv, int ldv, int naux, int i0, int ni, double c_os, double c_ss, void *stream);
 
+/* RI-dRPA response matrix on a grid of imaginary frequencies, fused (no frequency-scaled copy of the tensor is stored):
+ *   Q[k, P, R] (+)= scale sum_i sum_{a < nv} Bov[i, P, a] g_ia(w_k) Bov[i, R, a],   g_ia(w) = D_ia / (D_ia^2 + w^2),  D_ia = ev[a] - eo[i].
+ * d_bov (nocc, naux, ldv) as d_bi above (16-byte aligned, ldv a multiple of 16, >= nv; columns >= nv are selected to zero: whatever
+ * they hold contributes exactly zero); d_eo (nocc), d_ev (nv); d_freq (nfreq): w_k >= 0, w = 0 is legal while every D_ia != 0.
+ * d_q (nfreq, naux, naux): accumulate == 0: overwritten whole; accumulate == 1: added to (the second spin of an unrestricted
+ * calculation).  Only the lower triangle is computed and the mirror element is written from the same register: Q[k] is bit-symmetric
+ * (with accumulate: when it was).  nfreq or naux zero: nothing to write; nocc or nv zero: zeros, or d_q untouched with accumulate (no
+ * kernel).  d_work: dqc_rpa_work_doubles doubles -- zero unless the (i, a) sum is split over blocks (few panel pairs), then one slot
+ * of nfreq naux^2 doubles per part, added in slot order: no atomics, bit-reproducible with or without dqc_set_deterministic; may be
+ * null when the size is zero.  Every argument is checked before anything is launched (negative counts, ldv no multiple of 16 or < nv,
+ * accumulate not 0 or 1, null pointers: DQC_EINVAL).  Only enqueues. */
+size_t dqc_rpa_work_doubles(int nocc, int nv, int naux, int nfreq);
+int dqc_rpa_response(double *d_q, const double *d_bov, const double *d_eo, const double *d_ev, const double *d_freq, int nocc, int nv,
+                     int ldv, int naux, int nfreq, double scale, int accumulate, double *d_work, void *stream);
+
 /* ---- nuclear gradients of the SCF energy   ------------------------------------
  * The reference differentiates through its "ip" derivative integrals (molintor.py:463-500) and the implicit-function
  * backward of the SCF fixed point (scf_qccalc.py:63-67, 109-113); at convergence that is
