@@ -107,6 +107,7 @@ def load():
     lib.dqc_rpa_work_doubles.argtypes = [c_int] * 4
     lib.dqc_rpa_work_doubles.restype = c_sz
     lib.dqc_rpa_response.argtypes = [c_dp] * 5 + [c_int] * 5 + [ctypes.c_double, c_int, c_dp, c_vp]
+    lib.dqc_gw_screened_diag.argtypes = [c_dp] * 3 + [c_int] * 5 + [c_vp]
     lib.dqc_eri_tiles_to_dense.argtypes = [c_dp, c_dp, c_int, c_vp]
     lib.dqc_jk_from_tiles.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_vp]
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
@@ -508,6 +509,38 @@ def rpa_response(bov, eo, ev, freq, scale=1.0, out=None, accumulate=False, work=
     with _on(bov.device) as st_:
         _check(L.dqc_rpa_response(_ptr(out), _ptr(bov), _ptr(eo), _ptr(ev), _ptr(freq), nocc, nv, ldv, naux, nfreq, float(scale),
                                   int(accumulate), _ptr(work) if need else None, st_), "dqc_rpa_response")
+    return out
+
+
+def gw_screened_diag(wc, bn, nm, out=None):
+    """diagonal of the screened interaction (csrc/gw.hip: dqc_gw_screened_diag): wc (nfreq, naux, naux) symmetric, of which only the
+    elements P >= R are read; bn (ntarget, naux, ldm) as `mp2.transform_ov` makes it, nm <= ldm real columns ->
+    W (nfreq, ntarget, nm), W[k, n, m] = sum_PR bn[n, P, m] wc[k, P, R] bn[n, R, m].  out: the tensor to write into.
+    No atomics: bit-reproducible.  The arguments are checked before anything is launched"""
+    if bn.dim() != 3 or bn.shape[2] % 16:
+        raise DqcAmdError("gw_screened_diag: bn must be (ntarget, naux, ldm) with ldm a multiple of 16, got %s" % (tuple(bn.shape),))
+    ntarget, naux, ldm = (int(x) for x in bn.shape)
+    nm = int(nm)
+    if nm < 0 or nm > ldm:
+        raise DqcAmdError("gw_screened_diag: %d columns asked of slabs of %d" % (nm, ldm))
+    if wc.dim() != 3 or int(wc.shape[1]) != naux or int(wc.shape[2]) != naux:
+        raise DqcAmdError("gw_screened_diag: wc must be (nfreq, %d, %d) for bn of %d auxiliary functions, got %s"
+                          % (naux, naux, naux, tuple(wc.shape)))
+    nfreq = int(wc.shape[0])
+    for name, t in (("wc", wc), ("bn", bn)):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise DqcAmdError("gw_screened_diag: %s must be a contiguous float64 tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if wc.device != bn.device or bn.device.type != "cuda":
+        raise DqcAmdError("gw_screened_diag: wc and bn must be on one GPU, got %s and %s" % (wc.device, bn.device))
+    if bn.data_ptr() % 16:
+        raise DqcAmdError("gw_screened_diag: the tensor must be 16-byte aligned")
+    if out is None:
+        out = torch.empty((nfreq, ntarget, nm), dtype=torch.float64, device=bn.device)
+    elif tuple(out.shape) != (nfreq, ntarget, nm) or out.device != bn.device or out.dtype != torch.float64 or not out.is_contiguous():
+        raise DqcAmdError("gw_screened_diag: out must be a contiguous float64 (%d, %d, %d) tensor on the device of bn, got %s"
+                          % (nfreq, ntarget, nm, tuple(out.shape)))
+    with _on(bn.device) as st_:
+        _check(load().dqc_gw_screened_diag(_ptr(out), _ptr(wc), _ptr(bn), ntarget, nm, ldm, naux, nfreq, st_), "dqc_gw_screened_diag")
     return out
 
 

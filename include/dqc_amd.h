@@ -342,6 +342,18 @@ size_t dqc_rpa_work_doubles(int nocc, int nv, int naux, int nfreq);
 int dqc_rpa_response(double *d_q, const double *d_bov, const double *d_eo, const double *d_ev, const double *d_freq, int nocc, int nv,
                      int ldv, int naux, int nfreq, double scale, int accumulate, double *d_work, void *stream);
 
+/* Diagonal of the screened interaction between orbital pairs on a grid of imaginary frequencies (G0W0), fused: Y = Wc B is never stored.
+ *   W[k, n, m] = sum_{P, R} Bn[n, P, m] Wc[k][P, R] Bn[n, R, m]          for k < nfreq, n < ntarget, m < nm.
+ * d_bn (ntarget, naux, ldm): one slab per target orbital as d_bi above (16-byte aligned, ldm a multiple of 16, >= nm; columns >= nm are
+ * selected to zero: whatever they hold contributes exactly zero).  d_wc (nfreq, naux, naux): symmetric matrices of which ONLY the
+ * elements P >= R are ever read (the strict upper triangle may hold anything); an element R < P enters with the exact weight 2.
+ * d_w (nfreq, ntarget, nm): overwritten whole, every element by one lane that adds its terms in a fixed order: no atomics,
+ * bit-reproducible.  nfreq, ntarget or nm zero: nothing to write; naux zero: zeros (no kernel).  Every argument is checked before anything
+ * is launched (negative counts, ldm no multiple of 16 or < nm, null pointers, a misaligned tensor, more than 2^31 - 1 blocks of
+ * (frequency, target, 128 columns): DQC_EINVAL).  Only enqueues. */
+int dqc_gw_screened_diag(double *d_w, const double *d_wc, const double *d_bn, int ntarget, int nm, int ldm, int naux, int nfreq,
+                         void *stream);
+
 /* ---- nuclear gradients of the SCF energy   ------------------------------------
  * The reference differentiates through its "ip" derivative integrals (molintor.py:463-500) and the implicit-function
  * backward of the SCF fixed point (scf_qccalc.py:63-67, 109-113); at convergence that is
