@@ -37,7 +37,7 @@
 // route.  This one still does -- 31 to 35 % of the MFMA rate: 1.24 x the library route on ten target orbitals, 0.86 x on all 208 of
 // the 20-atom molecule (docs/LOG_r24.md has the measurements and what is left to try).
 #include "common.hpp"
-#include "grid_common.hpp"
+#include "mfma_tile.hpp"
 
 namespace dqc {
 
@@ -85,7 +85,7 @@ DQC_DEV void gw_chunk(v4d (&acc)[GW_CT], const double *swr, const double *sbc, i
         break;
 
 __global__ __launch_bounds__(GW_NT, 2) void gw_screened_diag_kernel(GwArgs g) {
-    // two buffers each (140 KB of the CU's 160 KB: one block per CU, which the 207 VGPRs of its eight waves allow anyway)
+    // two buffers each (140 KB of the CU's 160 KB: one block per CU, which the 234 VGPRs of its eight waves allow anyway)
     __shared__ __align__(16) double s_w[2 * GW_PW * GW_WS];     // [P][R] of the chunk, weighted; after the sweep: [wave][row group][column]
     __shared__ __align__(16) double s_b[2 * GW_KC * GW_BS];     // [R][column] of the chunk
     static_assert(8 * 4 * GW_CW <= GW_PW * GW_WS, "the partial sums reuse the Wc block");

@@ -8,8 +8,9 @@
 // One block (four waves) owns one occupied pair (i, j) and one 64 x 64 panel pair (Ap, Bp) of the virtual space -- 4 x 4 tiles of
 // 16 x 16; wave w owns tile row A = 4 Ap + w and the four tiles B = 4 Bp + t of it.  The panels Bi[:, Ap], Bj[:, Bp] (and, same mode,
 // Bj[:, Ap], Bi[:, Bp]) are staged in LDS in chunks of MP2_KC auxiliary functions -- each element is read from memory once per block
-// and from LDS by four (A panels: one) waves; the next chunk is asked for before the MFMAs of this one and stored after them.  LDS
-// row stride 80 doubles (== 32 banks mod 64): the two k rows a 32-lane half reads with ds_read_b64 sit 32 banks apart, conflict-free.
+// and from LDS by four (A panels: one) waves; the next chunk is asked for before the MFMAs of this one and stored after them (mp2_sweep,
+// which every kernel of this file calls).  LDS row stride 80 doubles (== 32 banks mod 64): the two k rows a 32-lane half reads with
+// ds_read_b64 sit 32 banks apart, conflict-free.
 //
 // Same mode (restricted, alpha-alpha, beta-beta: Bi == Bj as tensors): only i <= j, only panel pairs Ap <= Bp and in a diagonal panel pair
 // only tiles A <= B.  Per tile pair two accumulators with v_mfma_f64_16x16x4_f64:
@@ -35,21 +36,13 @@
 // The (ldv, ldv) faces are written whole: a >= nv or b >= nv is stored as 0.0 whatever the inputs' padding columns hold (tiles that
 // hold no real virtual skip their MFMAs).  Every element is written once, by one lane: no atomics, bit-reproducible.
 #include "common.hpp"
-#include "grid_common.hpp"
+#include "mfma_tile.hpp"
 
 namespace dqc {
 
 constexpr int MP2_KC = 16;   // auxiliary functions per LDS chunk
 constexpr int MP2_PW = 64;   // panel width (four tiles)
 constexpr int MP2_LS = 80;   // LDS row stride in doubles
-
-DQC_DEV void mp2_tri(long long q, int &i, int &j) {  // q = j (j + 1) / 2 + i, i <= j
-    long long r = (long long)((sqrt(8.0 * (double)q + 1.0) - 1.0) * 0.5);
-    while (r * (r + 1) / 2 > q) r--;
-    while ((r + 1) * (r + 2) / 2 <= q) r++;
-    j = (int)r;
-    i = (int)(q - r * (r + 1) / 2);
-}
 
 struct Mp2Args {
     const double *bi, *bj, *eoi, *eoj, *eva, *evb;
@@ -65,6 +58,69 @@ DQC_DEV double2 mp2_load2(const double *slab, int ld, int naux, int k, int col) 
     return double2{0.0, 0.0};
 }
 
+// The sweep over the auxiliary index of one block, the one copy of it: NP panels of 64 columns (panel p: columns scol[p] ... of the
+// slab src[p] of row length sld[p]), [Bi A][Bj B] and, NP == 4, [Bj A][Bi B], staged in chunks of MP2_KC rows -- 16 rows x 32 double2
+// per panel = 512 double2, two per thread and panel; the next chunk is asked for before the MFMAs of this one and stored after them,
+// two barriers per chunk.  On return acc1[t] (and, NP == 4, acc2[t]) hold the tiles live[t] of wave `wave`; the others are zero.
+// g: the kernel's argument block, of which naux is read (handed on whole, as the kernels read it before the sweep was shared: with
+// naux as a value of the caller the compiler lays mp2_pair_kernel<true> out four bytes shorter in front of the chunk loop, which costs
+// 1.3 % there -- docs/LOG_r25.md).
+template <int NP, class Args>
+DQC_DEV void mp2_sweep(double (&s_p)[NP][MP2_KC][MP2_LS], const double *const (&src)[NP], const int (&sld)[NP], const int (&scol)[NP],
+                       const Args &g, int wave, int l15, int q, const bool (&live)[4], v4d (&acc1)[4], v4d (&acc2)[4]) {
+    const int naux = g.naux;
+    const bool any = live[0] || live[1] || live[2] || live[3];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc1[t] = acc2[t] = v4d{0.0, 0.0, 0.0, 0.0};
+
+    double2 nx[NP][2];
+    auto fetch = [&](int c0) {
+#pragma unroll
+        for (int p = 0; p < NP; p++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
+                nx[p][u] = mp2_load2(src[p], sld[p], naux, c0 + k, scol[p] + c2);
+            }
+    };
+    fetch(0);
+    for (int c0 = 0; c0 < naux; c0 += MP2_KC) {
+        __syncthreads();  // (the previous chunk has been read by every wave)
+#pragma unroll
+        for (int p = 0; p < NP; p++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
+                *reinterpret_cast<double2 *>(&s_p[p][k][c2]) = nx[p][u];
+            }
+        __syncthreads();
+        if (c0 + MP2_KC < naux) fetch(c0 + MP2_KC);
+        if (!any) continue;
+        const int nk = min(MP2_KC, (naux - c0 + 3) & ~3);  // (rows past naux are zero: whole k-steps of them are skipped)
+        for (int k0 = 0; k0 < nk; k0 += 4) {
+            const double ai = s_p[0][k0 + q][16 * wave + l15];
+            double aj = 0.0;
+            if constexpr (NP == 4) aj = s_p[2][k0 + q][16 * wave + l15];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                if (!live[t]) continue;  // (wave-uniform)
+                acc1[t] = mfma_f64(ai, s_p[1][k0 + q][16 * t + l15], acc1[t]);
+                if constexpr (NP == 4) acc2[t] = mfma_f64(aj, s_p[3][k0 + q][16 * t + l15], acc2[t]);
+            }
+        }
+    }
+}
+
+// the rows of a lane in tile row tA, a = 16 tA + q + 4 r: inside the virtual space? and their orbital energies (0.0 outside)
+DQC_DEV void mp2_rows(const double *ev, int nv, int tA, int q, double (&ea)[4], bool (&oka)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int a = 16 * tA + q + 4 * r;
+        oka[r] = a < nv;
+        ea[r] = oka[r] ? ev[a] : 0.0;
+    }
+}
+
 template <bool SAME>
 __global__ __launch_bounds__(256, 2) void mp2_pair_kernel(Mp2Args g) {
     constexpr int NP = SAME ? 4 : 2;  // staged panels: [Bi A][Bj B] ([Bj A][Bi B])
@@ -74,8 +130,8 @@ __global__ __launch_bounds__(256, 2) void mp2_pair_kernel(Mp2Args g) {
     const long long pair = blockIdx.x / g.ntp, tp = blockIdx.x - pair * g.ntp;
     int i, j, pa, pb;
     if (SAME) {
-        mp2_tri(pair, i, j);
-        mp2_tri(tp, pa, pb);
+        tri_index(pair, i, j);
+        tri_index(tp, pa, pb);
     } else {
         i = (int)(pair / g.noj);
         j = (int)(pair - (long long)i * g.noj);
@@ -83,7 +139,6 @@ __global__ __launch_bounds__(256, 2) void mp2_pair_kernel(Mp2Args g) {
         pb = (int)(tp - (long long)pa * g.npb);
     }
     const double *slab_i = g.bi + (size_t)i * g.naux * g.ldva, *slab_j = g.bj + (size_t)j * g.naux * g.ldvb;
-    // the staging map: 16 rows x 32 double2 per panel = 512 double2, two per thread and panel
     const double *src[NP];
     int sld[NP], scol[NP];
     src[0] = slab_i; sld[0] = g.ldva; scol[0] = pa * MP2_PW;
@@ -102,57 +157,14 @@ __global__ __launch_bounds__(256, 2) void mp2_pair_kernel(Mp2Args g) {
     }
     const bool any = live[0] || live[1] || live[2] || live[3];
     v4d acc1[4], acc2[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) acc1[t] = acc2[t] = v4d{0.0, 0.0, 0.0, 0.0};
-
-    double2 nx[NP][2];
-    auto fetch = [&](int c0) {
-#pragma unroll
-        for (int p = 0; p < NP; p++)
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
-                nx[p][u] = mp2_load2(src[p], sld[p], g.naux, c0 + k, scol[p] + c2);
-            }
-    };
-    fetch(0);
-    for (int c0 = 0; c0 < g.naux; c0 += MP2_KC) {
-        __syncthreads();  // (the previous chunk has been read by every wave)
-#pragma unroll
-        for (int p = 0; p < NP; p++)
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
-                *reinterpret_cast<double2 *>(&s_p[p][k][c2]) = nx[p][u];
-            }
-        __syncthreads();
-        if (c0 + MP2_KC < g.naux) fetch(c0 + MP2_KC);
-        if (!any) continue;
-        const int nk = min(MP2_KC, (g.naux - c0 + 3) & ~3);  // (rows past naux are zero: whole k-steps of them are skipped)
-        for (int k0 = 0; k0 < nk; k0 += 4) {
-            const double ai = s_p[0][k0 + q][16 * wave + l15];
-            double aj = 0.0;
-            if constexpr (SAME) aj = s_p[2][k0 + q][16 * wave + l15];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                if (!live[t]) continue;  // (wave-uniform)
-                acc1[t] = mfma_f64(ai, s_p[1][k0 + q][16 * t + l15], acc1[t]);
-                if constexpr (SAME) acc2[t] = mfma_f64(aj, s_p[3][k0 + q][16 * t + l15], acc2[t]);
-            }
-        }
-    }
+    mp2_sweep<NP>(s_p, src, sld, scol, g, wave, l15, q, live, acc1, acc2);
     // epilogue: lane (l15, q), register r holds a = 16 tA + q + 4 r, b = 16 tB + l15
     double eos = 0.0, ess = 0.0;
     if (any) {
         const double eij = g.eoi[i] + g.eoj[j];
         double ea[4];
         bool oka[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int a = 16 * tA + q + 4 * r;
-            oka[r] = a < g.nva;
-            ea[r] = oka[r] ? g.eva[a] : 0.0;
-        }
+        mp2_rows(g.eva, g.nva, tA, q, ea, oka);
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             if (!live[t]) continue;
@@ -200,7 +212,7 @@ __global__ __launch_bounds__(64) void mp2_sum_kernel(double *__restrict__ eos, d
     }
     if (same) {
         int i, j;
-        mp2_tri(pair, i, j);
+        tri_index(pair, i, j);
         eos[(size_t)i * noj + j] = a;
         eos[(size_t)j * noj + i] = a;
         ess[(size_t)i * noj + j] = b;
@@ -218,12 +230,6 @@ struct Mp2AmpArgs {
     long long ntp;       // panel pairs per occupied pair
 };
 
-// a wave's LDS traffic is in order; this keeps the compiler from moving its own accesses of the transpose scratch across the point
-DQC_DEV void mp2_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(256, 2) void mp2_amp_kernel(Mp2AmpArgs g) {
     __shared__ __align__(16) double s_p[4][MP2_KC][MP2_LS];  // [Bi A][Bj B][Bj A][Bi B]
     __shared__ double s_tr[4][16][17];                       // per wave: one tile on its way to the transposed position
@@ -231,9 +237,10 @@ __global__ __launch_bounds__(256, 2) void mp2_amp_kernel(Mp2AmpArgs g) {
     const long long pair = blockIdx.x / g.ntp, tp = blockIdx.x - pair * g.ntp;  // pair = (i - i0) noj + j
     const int il = (int)(pair / g.noj), j = (int)(pair - (long long)il * g.noj), i = g.i0 + il;
     int pa, pb;
-    mp2_tri(tp, pa, pb);
+    tri_index(tp, pa, pb);
     const double *slab_i = g.b + (size_t)i * g.naux * g.ldv, *slab_j = g.b + (size_t)j * g.naux * g.ldv;
     const double *src[4] = {slab_i, slab_j, slab_j, slab_i};
+    const int sld[4] = {g.ldv, g.ldv, g.ldv, g.ldv};
     const int scol[4] = {pa * MP2_PW, pb * MP2_PW, pa * MP2_PW, pb * MP2_PW};
     const int tA = 4 * pa + wave;
     bool inside[4], live[4];  // the tile pair is this wave's to store; it holds a real virtual on both sides
@@ -243,57 +250,15 @@ __global__ __launch_bounds__(256, 2) void mp2_amp_kernel(Mp2AmpArgs g) {
         inside[t] = 16 * tA < g.ldv && 16 * tB < g.ldv && tA <= tB;
         live[t] = inside[t] && 16 * tA < g.nv && 16 * tB < g.nv;
     }
-    const bool any = live[0] || live[1] || live[2] || live[3];
     v4d acc1[4], acc2[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) acc1[t] = acc2[t] = v4d{0.0, 0.0, 0.0, 0.0};
-
-    double2 nx[4][2];
-    auto fetch = [&](int c0) {
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
-                nx[p][u] = mp2_load2(src[p], g.ldv, g.naux, c0 + k, scol[p] + c2);
-            }
-    };
-    fetch(0);
-    for (int c0 = 0; c0 < g.naux; c0 += MP2_KC) {
-        __syncthreads();  // (the previous chunk has been read by every wave)
-#pragma unroll
-        for (int p = 0; p < 4; p++)
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const int e = threadIdx.x + 256 * u, k = e >> 5, c2 = (e & 31) * 2;
-                *reinterpret_cast<double2 *>(&s_p[p][k][c2]) = nx[p][u];
-            }
-        __syncthreads();
-        if (c0 + MP2_KC < g.naux) fetch(c0 + MP2_KC);
-        if (!any) continue;
-        const int nk = min(MP2_KC, (g.naux - c0 + 3) & ~3);
-        for (int k0 = 0; k0 < nk; k0 += 4) {
-            const double ai = s_p[0][k0 + q][16 * wave + l15], aj = s_p[2][k0 + q][16 * wave + l15];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                if (!live[t]) continue;  // (wave-uniform)
-                acc1[t] = mfma_f64(ai, s_p[1][k0 + q][16 * t + l15], acc1[t]);
-                acc2[t] = mfma_f64(aj, s_p[3][k0 + q][16 * t + l15], acc2[t]);
-            }
-        }
-    }
+    mp2_sweep<4>(s_p, src, sld, scol, g, wave, l15, q, live, acc1, acc2);
     // epilogue: lane (l15, q), register r holds a = 16 tA + q + 4 r, b = 16 tB + l15 (acc1: V_ab, acc2: V_ba)
     const size_t ld = (size_t)g.ldv;
     double *ot = g.t + (size_t)pair * ld * ld, *ott = g.tt + (size_t)pair * ld * ld;
     const double eij = g.eo[i] + g.eo[j];
     double ea[4];
     bool oka[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int a = 16 * tA + q + 4 * r;
-        oka[r] = a < g.nv;
-        ea[r] = oka[r] ? g.ev[a] : 0.0;
-    }
+    mp2_rows(g.ev, g.nv, tA, q, ea, oka);
 #pragma unroll
     for (int t = 0; t < 4; t++) {
         if (!inside[t]) continue;  // (wave-uniform)
@@ -313,19 +278,14 @@ __global__ __launch_bounds__(256, 2) void mp2_amp_kernel(Mp2AmpArgs g) {
             yt[r] = ok ? g.c1 * y - g.c2 * x : 0.0;
         }
         if (tA == tB) continue;
-        // (b, a): scratch [b][a] <- the lane's column, then rows b = 16 tB + q + 4 r, 16 consecutive a per 16 lanes
+        // (b, a): through the scratch, then rows b = 16 tB + q + 4 r, 16 consecutive a per 16 lanes
+        double m[4];
+        tile_transpose(s_tr[wave], xt, m);
 #pragma unroll
-        for (int r = 0; r < 4; r++) s_tr[wave][l15][q + 4 * r] = xt[r];
-        mp2_wave_sync();
+        for (int r = 0; r < 4; r++) ot[(size_t)(16 * tB + q + 4 * r) * ld + 16 * tA + l15] = m[r];
+        tile_transpose(s_tr[wave], yt, m);
 #pragma unroll
-        for (int r = 0; r < 4; r++) ot[(size_t)(16 * tB + q + 4 * r) * ld + 16 * tA + l15] = s_tr[wave][q + 4 * r][l15];
-        mp2_wave_sync();
-#pragma unroll
-        for (int r = 0; r < 4; r++) s_tr[wave][l15][q + 4 * r] = yt[r];
-        mp2_wave_sync();
-#pragma unroll
-        for (int r = 0; r < 4; r++) ott[(size_t)(16 * tB + q + 4 * r) * ld + 16 * tA + l15] = s_tr[wave][q + 4 * r][l15];
-        mp2_wave_sync();
+        for (int r = 0; r < 4; r++) ott[(size_t)(16 * tB + q + 4 * r) * ld + 16 * tA + l15] = m[r];
     }
 }
 

@@ -27,8 +27,10 @@
 // No atomics.  slots == 1: every element of Q is written (accumulate: read, added to, written) by one lane.  slots > 1 (few panel pairs:
 // the (i, a) chunks are split over blocks for occupancy): every block writes its raw partial sums to its slot of the work buffer and
 // rpa_sum_kernel adds the slots of an element in slot order, scales, mirrors.  Bit-reproducible as it stands.
+#include <algorithm>
+
 #include "common.hpp"
-#include "grid_common.hpp"
+#include "mfma_tile.hpp"
 
 namespace dqc {
 
@@ -50,20 +52,6 @@ struct RpaArgs {
     long long ntp;       // panel pairs
 };
 
-DQC_DEV void rpa_tri(long long q, int &lo, int &hi) {  // q = hi (hi + 1) / 2 + lo, lo <= hi
-    long long r = (long long)((sqrt(8.0 * (double)q + 1.0) - 1.0) * 0.5);
-    while (r * (r + 1) / 2 > q) r--;
-    while ((r + 1) * (r + 2) / 2 <= q) r++;
-    hi = (int)r;
-    lo = (int)(q - r * (r + 1) / 2);
-}
-
-// a wave's LDS traffic is in order; this keeps the compiler from moving its own accesses of the transpose scratch across the point
-DQC_DEV void rpa_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(256, 2) void rpa_response_kernel(RpaArgs g) {
     __shared__ __align__(16) double s_p[2][RPA_PW][RPA_LS];     // [P panel, R panel][row][a]
     __shared__ __align__(16) double s_g[RPA_KC][RPA_NF];        // the weights of the chunk
@@ -75,7 +63,7 @@ __global__ __launch_bounds__(256, 2) void rpa_response_kernel(RpaArgs g) {
     const long long tp = b % g.ntp;
     const int slot = (int)(b / g.ntp);
     int pr, pp;
-    rpa_tri(tp, pr, pp);   // pr <= pp
+    tri_index(tp, pr, pp);   // pr <= pp
     const int tP = 4 * pp + wave;
     bool live[4];          // tiles this wave forms: inside the matrix, on or below the diagonal
 #pragma unroll
@@ -179,21 +167,18 @@ __global__ __launch_bounds__(256, 2) void rpa_response_kernel(RpaArgs g) {
                     *x = g.accumulate ? *x + v[r] : v[r];
                 }
             }
-            // (rc', p'): scratch [column l15][row q + 4 r] <- the lane's registers, then rows rc' = 16 tR + q + 4 r of the mirror image,
-            // 16 consecutive p' = 16 tP + l15 per 16 lanes; the diagonal itself was written above
-#pragma unroll
-            for (int r = 0; r < 4; r++) s_tr[wave][l15][q + 4 * r] = v[r];
-            rpa_wave_sync();
+            // (rc', p'): through the scratch, then rows rc' = 16 tR + q + 4 r of the mirror image, 16 consecutive p' = 16 tP + l15 per
+            // 16 lanes; the diagonal itself was written above
+            double m[4];
+            tile_transpose(s_tr[wave], v, m);
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int rc2 = 16 * tR + q + 4 * r, p2 = 16 * tP + l15;
-                const double m = s_tr[wave][q + 4 * r][l15];
                 if (p2 < g.naux && rc2 < p2) {
                     double *x = o + (size_t)rc2 * n + p2;
-                    *x = g.accumulate ? *x + m : m;
+                    *x = g.accumulate ? *x + m[r] : m[r];
                 }
             }
-            rpa_wave_sync();
         }
     }
 }

@@ -45,7 +45,7 @@ import math
 import torch
 
 from . import lib
-from .mp2 import _b_tensor, _free_bytes, _orbitals, _unsupported, transform_ov
+from .postscf import aux_key, b_tensor, check_frequency_args, memoised, orbitals, response_batches, transform_ov, unsupported
 from .rpa import frequency_grid
 
 
@@ -324,10 +324,9 @@ def _static_parts(qc, eps, c_orth, bn_occ):
 def _compute(qc, orbs, auxbasis, nfreq, freq_scale, sigma_wmax, batch=None):
     eng = qc._engine
     h = eng.hamilton
-    df = _b_tensor(qc, auxbasis)
+    df = b_tensor(qc, auxbasis)
     b = df._b
-    naux = int(b.shape[0])
-    spins = _orbitals(qc, 0)
+    spins = orbitals(qc, 0)
     focks = (qc._fock[0], qc._fock[1]) if eng.polarized else (qc._fock,)
     c_orth = [eng._eigpairs(f.detach())[1] for f in focks]
     c_all = [torch.cat([co, cv], dim=1) for co, cv, _, _ in spins]
@@ -344,22 +343,13 @@ def _compute(qc, orbs, auxbasis, nfreq, freq_scale, sigma_wmax, batch=None):
     bovs = [transform_ov(b, co, cv) for co, cv, _, _ in spins]
     bns = [transform_ov(b, c[:, orbs].contiguous(), c) for c in c_all]
     # Q, Wc, the Cholesky factor and the solver's copy: four (nk, naux, naux) tensors per batch
-    if batch is None:
-        batch = (_free_bytes(b.device) // 2) // max(4 * 8 * naux * naux, 1)
-    nk = max(1, min(nfreq, int(batch)))
-    scale = 2.0 if eng.polarized else 4.0
+    batches = response_batches(bovs, spins, fd, 2.0 if eng.polarized else 4.0, 4, batch)
     ws = [torch.empty((nfreq, len(orbs), nmo), dtype=b.dtype, device=b.device) for _ in spins]
-    q = torch.empty((nk, naux, naux), dtype=b.dtype, device=b.device)
-    for k0 in range(0, nfreq, nk):
-        n = min(nk, nfreq - k0)
-        qk = q[:n]
-        for s, (bov, (_, _, eo, ev)) in enumerate(zip(bovs, spins)):
-            lib.rpa_response(bov, eo, ev, fd[k0:k0 + n].contiguous(), scale, out=qk, accumulate=s > 0)
+    for k0, n, qk in batches:
         wc = correlation_part(qk).contiguous()
         for w, bn in zip(ws, bns):
             lib.gw_screened_diag(wc, bn, nmo, out=w[k0:k0 + n])
         del wc
-    del q
     bn_occ = None
     if h.df is not None and not h.df.exchange:   # the exchange self-energy of ALL orbitals from the tensor
         bn_occ = [transform_ov(b, c, c[:, :no].contiguous())[:, :, :no] for c, no in zip(c_all, nocc)]
@@ -393,10 +383,7 @@ def gw(qc, orbs=None, auxbasis=None, nfreq=100, freq_scale=1.0, sigma_wmax=2.0, 
     Z instead of the solution of the quasiparticle equation.  Memoised on the converged state per argument set (the two ways to
     solve share everything but the last step); nothing is differentiable: the result is detached."""
     nfreq, freq_scale, sigma_wmax = int(nfreq), float(freq_scale), float(sigma_wmax)
-    if nfreq < 1:
-        raise ValueError("gw: nfreq must be >= 1, got %d" % nfreq)
-    if not freq_scale > 0.0:
-        raise ValueError("gw: freq_scale must be positive, got %g" % freq_scale)
+    check_frequency_args("gw", nfreq, freq_scale)
     if not sigma_wmax > 0.0:
         raise ValueError("gw: sigma_wmax must be positive, got %g" % sigma_wmax)
     if orbs is not None:
@@ -404,18 +391,11 @@ def gw(qc, orbs=None, auxbasis=None, nfreq=100, freq_scale=1.0, sigma_wmax=2.0, 
         nmo = getattr(qc._engine, "shape", (None,))[-1]
         if not orbs or min(orbs) < 0 or len(set(orbs)) != len(orbs) or (nmo is not None and max(orbs) >= int(nmo)):
             raise ValueError("gw: orbs must be distinct orbital indices in [0, %s), got %s" % ("nmo" if nmo is None else int(nmo), orbs))
-    _unsupported(qc)
+    unsupported(qc)
     assert qc._has_run, "run() the calculation first"
-    from .response import state_memo
-    memo = state_memo(qc)
-    h = qc._engine.hamilton
-    own = h.df is not None and h.df.exchange
-    key = ("gw", None if orbs is None else tuple(orbs), None if own else (auxbasis if isinstance(auxbasis, str) or auxbasis is None else id(auxbasis)),
-           nfreq, freq_scale, sigma_wmax)
-    if key not in memo:
-        with torch.no_grad():
-            memo[key] = _compute(qc, orbs, auxbasis, nfreq, freq_scale, sigma_wmax)
-    df, per_spin, orbs, nocc, points, ef, freqs, weights = memo[key]
+    key = ("gw", None if orbs is None else tuple(orbs), aux_key(qc, auxbasis), nfreq, freq_scale, sigma_wmax)
+    df, per_spin, orbs, nocc, points, ef, freqs, weights = memoised(
+        qc, key, lambda: _compute(qc, orbs, auxbasis, nfreq, freq_scale, sigma_wmax))
     return GW(_solve(per_spin, points, ef, bool(linearized)), orbs, nocc, points, ef, freqs, weights, linearized, df)
 
 

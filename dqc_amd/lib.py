@@ -441,24 +441,45 @@ def mp2_pair_energies(bi, bj, eps_oi, eps_oj, eps_va, eps_vb, same, work=None):
     return eos, ess
 
 
+def _aligned16(who, t):
+    if t.data_ptr() % 16:
+        raise DqcAmdError("%s: the tensor must be 16-byte aligned" % who)
+
+
+def _slabs(who, bov, eo, ev):
+    """(nocc, naux, ldv, nv) of an occupied-virtual tensor (one (naux, ldv) slab per occupied orbital) and its orbital energies"""
+    if bov.dim() != 3 or bov.shape[2] % 16:
+        raise DqcAmdError("%s: bov must be (nocc, naux, ldv) with ldv a multiple of 16, got %s" % (who, tuple(bov.shape)))
+    nocc, naux, ldv = (int(x) for x in bov.shape)
+    nv = int(ev.numel())
+    if int(eo.numel()) != nocc:
+        raise DqcAmdError("%s: %d occupied energies for %d slabs" % (who, eo.numel(), nocc))
+    if nv > ldv:
+        raise DqcAmdError("%s: %d virtual energies for slabs of %d columns" % (who, nv, ldv))
+    return nocc, naux, ldv, nv
+
+
+def _out_like(who, out, shape, ref, name):
+    """`out`, or a new float64 tensor of `shape` on the device of `ref` (the argument called `name`)"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=ref.device)
+    if tuple(out.shape) != shape or out.device != ref.device or out.dtype != torch.float64 or not out.is_contiguous():
+        raise DqcAmdError("%s: out must be a contiguous float64 (%d, %d, %d) tensor on the device of %s, got %s"
+                          % ((who,) + shape + (name, tuple(out.shape))))
+    return out
+
+
 def mp2_amplitudes(bov, eo, ev, i0, ni, c_os=1.0, c_ss=1.0, out=None):
     """RI-MP2 amplitudes of the occupied block [i0, i0 + ni) against every occupied orbital (csrc/mp2.hip: dqc_mp2_amplitudes), restricted:
     bov (nocc, naux, ldv) as `mp2_pair_energies` takes it, eo (nocc), ev (nv <= ldv) -> (t, tt), both (ni, nocc, ldv, ldv):
     t[i - i0, j, a, b] = V^{ij}_{ab} / D^{ij}_{ab}, tt = (c_os + c_ss) t - c_ss t^T (2 T - T^T by default).  Rows and columns >= nv are
     written as exactly 0.0.  out: a pair of contiguous float64 device tensors of at least ni * nocc * ldv^2 elements each to write into
     (the results are views of them).  No atomics: bit-reproducible.  The arguments are checked before anything is launched"""
-    if bov.dim() != 3 or bov.shape[2] % 16:
-        raise DqcAmdError("mp2_amplitudes: bov must be (nocc, naux, ldv) with ldv a multiple of 16, got %s" % (tuple(bov.shape),))
-    nocc, naux, ldv = (int(x) for x in bov.shape)
-    nv, i0, ni = int(ev.numel()), int(i0), int(ni)
-    if int(eo.numel()) != nocc:
-        raise DqcAmdError("mp2_amplitudes: %d occupied energies for %d slabs" % (eo.numel(), nocc))
-    if nv > ldv:
-        raise DqcAmdError("mp2_amplitudes: %d virtual energies for slabs of %d columns" % (nv, ldv))
+    nocc, naux, ldv, nv = _slabs("mp2_amplitudes", bov, eo, ev)
+    i0, ni = int(i0), int(ni)
     if i0 < 0 or ni < 0 or i0 + ni > nocc:
         raise DqcAmdError("mp2_amplitudes: the block [%d, %d) is not inside the %d occupied orbitals" % (i0, i0 + ni, nocc))
-    if bov.data_ptr() % 16:
-        raise DqcAmdError("mp2_amplitudes: the tensor must be 16-byte aligned")
+    _aligned16("mp2_amplitudes", bov)
     need = ni * nocc * ldv * ldv
     if out is None:
         out = (torch.empty(need, dtype=torch.float64, device=bov.device), torch.empty(need, dtype=torch.float64, device=bov.device))
@@ -482,26 +503,15 @@ def rpa_response(bov, eo, ev, freq, scale=1.0, out=None, accumulate=False, work=
     Q[k] = scale sum_ia bov[i, :, a] g_ia(w_k) bov[i, :, a]^T, g_ia(w) = D_ia / (D_ia^2 + w^2), D_ia = ev[a] - eo[i]; both triangles,
     bit-symmetric.  out: the tensor to write into; accumulate=True adds to `out` (the second spin) instead of overwriting it.
     No atomics: bit-reproducible.  The arguments are checked before anything is launched"""
-    if bov.dim() != 3 or bov.shape[2] % 16:
-        raise DqcAmdError("rpa_response: bov must be (nocc, naux, ldv) with ldv a multiple of 16, got %s" % (tuple(bov.shape),))
-    nocc, naux, ldv = (int(x) for x in bov.shape)
-    nv, nfreq = int(ev.numel()), int(freq.numel())
-    if int(eo.numel()) != nocc:
-        raise DqcAmdError("rpa_response: %d occupied energies for %d slabs" % (eo.numel(), nocc))
-    if nv > ldv:
-        raise DqcAmdError("rpa_response: %d virtual energies for slabs of %d columns" % (nv, ldv))
+    nocc, naux, ldv, nv = _slabs("rpa_response", bov, eo, ev)
+    nfreq = int(freq.numel())
     if freq.dim() != 1:
         raise DqcAmdError("rpa_response: freq must be one-dimensional, got %s" % (tuple(freq.shape),))
-    if bov.data_ptr() % 16:
-        raise DqcAmdError("rpa_response: the tensor must be 16-byte aligned")
+    _aligned16("rpa_response", bov)
     accumulate = bool(accumulate)
-    if out is None:
-        if accumulate:
-            raise DqcAmdError("rpa_response: accumulate=True needs the tensor to add to (out=)")
-        out = torch.empty((nfreq, naux, naux), dtype=torch.float64, device=bov.device)
-    elif tuple(out.shape) != (nfreq, naux, naux) or out.device != bov.device or out.dtype != torch.float64 or not out.is_contiguous():
-        raise DqcAmdError("rpa_response: out must be a contiguous float64 (%d, %d, %d) tensor on the device of bov, got %s"
-                          % (nfreq, naux, naux, tuple(out.shape)))
+    if out is None and accumulate:
+        raise DqcAmdError("rpa_response: accumulate=True needs the tensor to add to (out=)")
+    out = _out_like("rpa_response", out, (nfreq, naux, naux), bov, "bov")
     L = load()
     need = int(L.dqc_rpa_work_doubles(nocc, nv, naux, nfreq))
     if need and (work is None or work.numel() < need):
@@ -532,13 +542,8 @@ def gw_screened_diag(wc, bn, nm, out=None):
             raise DqcAmdError("gw_screened_diag: %s must be a contiguous float64 tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
     if wc.device != bn.device or bn.device.type != "cuda":
         raise DqcAmdError("gw_screened_diag: wc and bn must be on one GPU, got %s and %s" % (wc.device, bn.device))
-    if bn.data_ptr() % 16:
-        raise DqcAmdError("gw_screened_diag: the tensor must be 16-byte aligned")
-    if out is None:
-        out = torch.empty((nfreq, ntarget, nm), dtype=torch.float64, device=bn.device)
-    elif tuple(out.shape) != (nfreq, ntarget, nm) or out.device != bn.device or out.dtype != torch.float64 or not out.is_contiguous():
-        raise DqcAmdError("gw_screened_diag: out must be a contiguous float64 (%d, %d, %d) tensor on the device of bn, got %s"
-                          % (nfreq, ntarget, nm, tuple(out.shape)))
+    _aligned16("gw_screened_diag", bn)
+    out = _out_like("gw_screened_diag", out, (nfreq, ntarget, nm), bn, "bn")
     with _on(bn.device) as st_:
         _check(load().dqc_gw_screened_diag(_ptr(out), _ptr(wc), _ptr(bn), ntarget, nm, ldm, naux, nfreq, st_), "dqc_gw_screened_diag")
     return out

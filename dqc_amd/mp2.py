@@ -29,6 +29,10 @@ yardstick of that path.  The amplitudes come from dqc_mp2_amplitudes one block o
 import torch
 
 from . import lib
+from .postscf import aux_key, b_tensor, free_bytes, memoised, orbitals, pair_energy_blocks, transform_ov, unsupported
+
+# the names under which tests/test_mp2_cpu.py and tests/test_gpu_mp2_density.py, written when these lived here, import them
+_unsupported, _b_tensor, _orbitals = unsupported, b_tensor, orbitals
 
 
 def pair_energies_reference(bi, bj, eps_oi, eps_oj, eps_va, eps_vb, same):
@@ -93,101 +97,17 @@ def energies_reference(spins, frozen=0):
     return components(pair_os, pair_ss, len(spins) == 2) + (pair_os, pair_ss)
 
 
-def _unsupported(qc):
-    eng = qc._engine
-    h = eng.hamilton
-    if getattr(h, "sharded", False):
-        raise NotImplementedError("mp2: a Hamiltonian sharded over several GPUs (shard_over) is not supported")
-    df = getattr(h, "df", None)
-    if df is not None and df.dfinfo.method == "overlap":
-        raise NotImplementedError("mp2: density fitting with method=\"overlap\" is not supported (the Coulomb metric only)")
-    if getattr(eng.get_system(), "_user_weights", None) is not None:
-        raise NotImplementedError("mp2: user-given occupations (orb_weights) are not supported")
-    full = 1.0 if eng.polarized else 2.0
-    for w in ((eng.orb_weight.u, eng.orb_weight.d) if eng.polarized else (eng.orb_weight,)):
-        occ = w[w != 0]
-        if not bool(torch.all(occ == full)):
-            if not eng.polarized and bool(torch.all((occ == 2.0) | (occ == 1.0))):
-                raise NotImplementedError("mp2: restricted open-shell occupations (2, ..., 2, 1, ..., 1) are not supported; run the "
-                                          "calculation unrestricted")
-            raise NotImplementedError("mp2: fractional occupations are not supported (integer occupations %g only)" % full)
-
-
-def _b_tensor(qc, auxbasis):
-    """the DFMI355 object that holds B[P, mu, nu]: the Hamiltonian's own, or one built here (and remembered per auxiliary basis)"""
-    from .response import state_memo
-    h = qc._engine.hamilton
-    if h.df is not None and h.df.exchange:
-        return h.df
-    key = ("mp2_df", auxbasis if isinstance(auxbasis, str) or auxbasis is None else id(auxbasis))
-    memo = state_memo(qc)
-    if key not in memo:
-        from .basis import make_aux_atombases
-        from .df import DFMI355
-        from .utils.datastruct import DensityFitInfo
-        mol = qc.get_system()
-        # None: the set Mol.densityfit() resolves its default to (the named fitting set when its tables are there, else the generated one)
-        auxbases = make_aux_atombases(mol._atomzs, mol._atompos, "cc-pvtz-jkfit" if auxbasis is None else auxbasis, mol._atombases, {})
-        info = DensityFitInfo(method="coulomb", auxbases=auxbases, exchange=True)
-        memo[key] = DFMI355(info, h.atombases, h._orthozer, h.device).build()
-    return memo[key]
-
-
-def transform_ov(b, co, cv):
-    """Bov[i, P, a] = sum_mu,nu co[mu, i] B[P, mu, nu] cv[nu, a], a padded with zero columns to a multiple of 16: (no, naux, ldv).
-    Library matmuls over chunks of P, occupied index first (the cheaper order); no temporary is larger than the result"""
-    naux, nao = int(b.shape[0]), int(b.shape[1])
-    no, nv = int(co.shape[1]), int(cv.shape[1])
-    ldv = (nv + 15) // 16 * 16
-    need = 8 * no * naux * ldv
-    free, _total = torch.cuda.mem_get_info(b.device)
-    free += torch.cuda.memory_reserved(b.device) - torch.cuda.memory_allocated(b.device)  # (cached blocks are reusable)
-    step = max(1, min(naux, naux * ldv // (4 * max(nao, ldv, 1)))) if naux else 1  # the two temporaries: a quarter of Bov each at most
-    tmp = 8 * step * no * (nao + ldv)
-    if need + tmp > free:
-        raise lib.DqcAmdError(
-            "mp2: the occupied-virtual tensor Bov (nocc = %d, naux = %d, nvir = %d padded to %d) needs %.2f GB and %.2f GB of "
-            "temporaries but only %.2f GB of device memory are free: freeze more orbitals or use a smaller auxiliary basis (there is "
-            "no batching over occupied blocks)" % (no, naux, nv, ldv, need / 1e9, tmp / 1e9, free / 1e9))
-    cvp = torch.zeros((nao, ldv), dtype=b.dtype, device=b.device)
-    cvp[:, :nv] = cv
-    cot = co.t().contiguous()
-    bov = torch.empty((no, naux, ldv), dtype=b.dtype, device=b.device)
-    for p0 in range(0, naux, step):
-        half = torch.matmul(cot, b[p0:p0 + step])                       # (pc, no, nao)
-        bov[:, p0:p0 + step] = torch.matmul(half, cvp).transpose(0, 1)  # (pc, no, ldv) -> [i, P, a]
-    return bov
-
-
-def _orbitals(qc, frozen):
-    """per spin (C_occ (nao, no), C_vir (nao, nv), eps_occ, eps_vir) in the AO basis, the lowest `frozen` occupied ones dropped"""
-    eng = qc._engine
-    h = eng.hamilton
-    focks = (qc._fock[0], qc._fock[1]) if eng.polarized else (qc._fock,)
-    weights = (eng.orb_weight.u, eng.orb_weight.d) if eng.polarized else (eng.orb_weight,)
-    out = []
-    for f, w in zip(focks, weights):
-        e, c = eng._eigpairs(f.detach())
-        c = h._orthozer @ c
-        nocc = int((w != 0).sum())
-        lo = min(frozen, nocc)
-        out.append((c[:, lo:nocc].contiguous(), c[:, nocc:].contiguous(), e[lo:nocc].contiguous(), e[nocc:].contiguous()))
-    return out
-
-
 def _compute(qc, frozen, auxbasis):
     eng = qc._engine
-    df = _b_tensor(qc, auxbasis)
+    df = b_tensor(qc, auxbasis)
     b = df._b
-    spins = _orbitals(qc, frozen)
+    spins = orbitals(qc, frozen)
     bovs = [transform_ov(b, co, cv) for co, cv, _, _ in spins]
+    os_ab, same = pair_energy_blocks(bovs, spins)
     if not eng.polarized:
-        (_, _, eo, ev), bov = spins[0], bovs[0]
-        pair_os, pair_ss = lib.mp2_pair_energies(bov, bov, eo, eo, ev, ev, True)
+        pair_os, pair_ss = same[0]
     else:
-        (_, _, eoa, eva), (_, _, eob, evb) = spins
-        pair_os, _ = lib.mp2_pair_energies(bovs[0], bovs[1], eoa, eob, eva, evb, False)
-        pair_ss = tuple(0.5 * lib.mp2_pair_energies(bov, bov, eo, eo, ev, ev, True)[1] for bov, (_, _, eo, ev) in zip(bovs, spins))
+        pair_os, pair_ss = os_ab, tuple(0.5 * ss for _, ss in same)
     e_os, e_ss = components(pair_os, pair_ss, eng.polarized)
     return df, pair_os, pair_ss, e_os, e_ss
 
@@ -205,16 +125,8 @@ def mp2(qc, frozen=0, auxbasis=None, c_os=1.0, c_ss=1.0):
     frozen = int(frozen)
     if frozen < 0:
         raise ValueError("mp2: frozen must be >= 0, got %d" % frozen)
-    _unsupported(qc)
-    from .response import state_memo
-    memo = state_memo(qc)
-    h = qc._engine.hamilton
-    own = h.df is not None and h.df.exchange
-    key = ("mp2", frozen, None if own else (auxbasis if isinstance(auxbasis, str) or auxbasis is None else id(auxbasis)))
-    if key not in memo:
-        with torch.no_grad():
-            memo[key] = _compute(qc, frozen, auxbasis)
-    df, pair_os, pair_ss, e_os, e_ss = memo[key]
+    unsupported(qc)
+    df, pair_os, pair_ss, e_os, e_ss = memoised(qc, ("mp2", frozen, aux_key(qc, auxbasis)), lambda: _compute(qc, frozen, auxbasis))
     e_scf = qc.energy().detach().reshape(1)
     return MP2(e_scf, e_os, e_ss, pair_os, pair_ss, c_os, c_ss, frozen, df)
 
@@ -286,11 +198,6 @@ class MP2Density:
             "relaxed" if self.relaxed else "unrelaxed", float(self.e_corr), self.c_os, self.c_ss, self.frozen, self.naux)
 
 
-def _free_bytes(dev):
-    free, _total = torch.cuda.mem_get_info(dev)
-    return free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)  # (cached blocks are reusable)
-
-
 def unrelaxed_blocks(bov, eo, ev, c_os=1.0, c_ss=1.0, block=None, amplitudes=None):
     """(P_oo, P_vv (nv, nv), Gamma (no, naux, ldv), occupied orbitals per block) from the amplitude kernel, one occupied block at a
     time: per block lib.mp2_amplitudes, then library GEMMs on the padded shapes -- P_vv += 2 T^T Tt over the rows (k, j, c), split [by
@@ -303,7 +210,7 @@ def unrelaxed_blocks(bov, eo, ev, c_os=1.0, c_ss=1.0, block=None, amplitudes=Non
     per = 2 * 8 * no * ldv * ldv + 8 * ldv * naux          # T and Tt of one occupied orbital, its slab of Gamma^T
     if block is None:
         fixed = 8 * no * naux * ldv * 2 + 8 * ldv * ldv    # Gamma, Bov transposed
-        block = (_free_bytes(bov.device) - fixed) // 2 // max(per, 1)
+        block = (free_bytes(bov.device) - fixed) // 2 // max(per, 1)
     nb = max(1, min(no, int(block)))
     p_oo = torch.zeros((no, no), dtype=bov.dtype, device=bov.device)
     p_vv = torch.zeros((ldv, ldv), dtype=bov.dtype, device=bov.device)
@@ -352,10 +259,10 @@ def _density(qc, frozen, auxbasis, c_os, c_ss, relaxed, tol, block):
     from .properties import _total_ao_density
     from .response import OrbitalHessian
     h = qc._engine.hamilton
-    df = _b_tensor(qc, auxbasis)
+    df = b_tensor(qc, auxbasis)
     b = df._b
-    co, cv, eo, ev = _orbitals(qc, frozen)[0]
-    c_frozen = _orbitals(qc, 0)[0][0][:, :frozen]
+    co, cv, eo, ev = orbitals(qc, frozen)[0]
+    c_frozen = orbitals(qc, 0)[0][0][:, :frozen]
     bov = transform_ov(b, co, cv)
     p_oo, p_vv, gamma, nb = unrelaxed_blocks(bov, eo, ev, c_os, c_ss, block)
     e_corr = (gamma * bov).sum().reshape(1)
@@ -410,22 +317,16 @@ def mp2_density(qc, frozen=0, auxbasis=None, c_os=1.0, c_ss=1.0, relaxed=True, t
     if relaxed and eng.is_ks:
         raise NotImplementedError("mp2_density: the relaxed density on a Kohn-Sham reference is not supported (the double-hybrid response "
                                   "needs exchange-correlation terms in the Lagrangian); use relaxed=False")
-    _unsupported(qc)
+    unsupported(qc)
     h = eng.hamilton
     if relaxed:
         if h.df is not None or getattr(h, "_direct", False) or getattr(h, "_tiles_store", None) is None:
             raise NotImplementedError("mp2_density: the relaxed density needs the orbital Hessian over the resident exact integrals, which a "
                                       "density-fitted or direct-SCF Hamiltonian does not have: pass an exact-integral calculation and "
                                       "`auxbasis=`, or use relaxed=False")
-    from .response import state_memo
-    memo = state_memo(qc)
-    own = h.df is not None and h.df.exchange
-    key = ("mp2_density", frozen, None if own else (auxbasis if isinstance(auxbasis, str) or auxbasis is None else id(auxbasis)),
-           float(c_os), float(c_ss), bool(relaxed), float(tol) if relaxed else None, None if block is None else int(block))
-    if key not in memo:
-        with torch.no_grad():
-            memo[key] = _density(qc, frozen, auxbasis, float(c_os), float(c_ss), bool(relaxed), float(tol), block)
-    return memo[key]
+    key = ("mp2_density", frozen, aux_key(qc, auxbasis), float(c_os), float(c_ss), bool(relaxed), float(tol) if relaxed else None,
+           None if block is None else int(block))
+    return memoised(qc, key, lambda: _density(qc, frozen, auxbasis, float(c_os), float(c_ss), bool(relaxed), float(tol), block))
 
 
 # `dqc_amd.mp2` is this function once the package has imported it: the yardstick stays reachable as dqc_amd.mp2.pair_energies_reference

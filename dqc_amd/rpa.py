@@ -32,8 +32,8 @@ import math
 
 import torch
 
-from . import lib
-from .mp2 import _b_tensor, _free_bytes, _orbitals, _unsupported, transform_ov
+from .postscf import (aux_key, b_tensor, check_frequency_args, memoised, orbitals, pair_energy_blocks, response_batches, transform_ov,
+                      unsupported)
 
 
 def frequency_grid(nfreq, scale=1.0):
@@ -41,10 +41,7 @@ def frequency_grid(nfreq, scale=1.0):
     (0, inf), ascending, with the weights 2 scale w_k / (1 - x)^2"""
     import numpy as np
     nfreq = int(nfreq)
-    if nfreq < 1:
-        raise ValueError("frequency_grid: nfreq must be >= 1, got %d" % nfreq)
-    if not float(scale) > 0.0:
-        raise ValueError("frequency_grid: the scale must be positive, got %g" % float(scale))
+    check_frequency_args("frequency_grid", nfreq, float(scale), "the scale")
     x, w = np.polynomial.legendre.leggauss(nfreq)
     x, w = torch.from_numpy(x), torch.from_numpy(w)
     return float(scale) * (1.0 + x) / (1.0 - x), 2.0 * float(scale) * w / (1.0 - x) ** 2
@@ -178,39 +175,26 @@ def _e_exx(qc):
 
 def _compute(qc, frozen, auxbasis, nfreq, freq_scale, batch=None):
     eng = qc._engine
-    df = _b_tensor(qc, auxbasis)
+    df = b_tensor(qc, auxbasis)
     b = df._b
-    naux = int(b.shape[0])
-    spins = _orbitals(qc, frozen)
+    spins = orbitals(qc, frozen)
     bovs = [transform_ov(b, co, cv) for co, cv, _, _ in spins]
     freqs, weights = frequency_grid(nfreq, freq_scale)
     fd, wd = freqs.to(b.device), weights.to(b.device)
     # Q, the copy the eigenvalue solver works in and its workspace: three (nk, naux, naux) tensors per batch
-    if batch is None:
-        batch = (_free_bytes(b.device) // 2) // max(3 * 8 * naux * naux, 1)
-    nk = max(1, min(nfreq, int(batch)))
-    scale = 2.0 if eng.polarized else 4.0
+    batches = response_batches(bovs, spins, fd, 2.0 if eng.polarized else 4.0, 3, batch)
     e_corr = torch.zeros(1, dtype=b.dtype, device=b.device)
     e_2nd = torch.zeros_like(e_corr)
     integrand = torch.empty(nfreq, dtype=b.dtype, device=b.device)
-    q = torch.empty((nk, naux, naux), dtype=b.dtype, device=b.device)
-    for k0 in range(0, nfreq, nk):
-        n = min(nk, nfreq - k0)
-        qk = q[:n]
-        for s, (bov, (_, _, eo, ev)) in enumerate(zip(bovs, spins)):
-            lib.rpa_response(bov, eo, ev, fd[k0:k0 + n].contiguous(), scale, out=qk, accumulate=s > 0)
+    for k0, n, qk in batches:
         e1, e2, integrand[k0:k0 + n] = energy_from_response(qk, wd[k0:k0 + n])
         e_corr += e1
         e_2nd += e2
-    del q
+    os_ab, same = pair_energy_blocks(bovs, spins)
     if not eng.polarized:
-        (_, _, eo, ev), bov = spins[0], bovs[0]
-        e_dmp2 = dmp2_from_pairs(lib.mp2_pair_energies(bov, bov, eo, eo, ev, ev, True)[0])
+        e_dmp2 = dmp2_from_pairs(same[0][0])
     else:
-        (_, _, eoa, eva), (_, _, eob, evb) = spins
-        os_ab = lib.mp2_pair_energies(bovs[0], bovs[1], eoa, eob, eva, evb, False)[0]
-        os_same = tuple(lib.mp2_pair_energies(bov, bov, eo, eo, ev, ev, True)[0] for bov, (_, _, eo, ev) in zip(bovs, spins))
-        e_dmp2 = dmp2_from_pairs(os_same, os_ab)
+        e_dmp2 = dmp2_from_pairs(tuple(os for os, _ in same), os_ab)
     return df, e_corr, e_2nd, e_dmp2, freqs, weights, integrand
 
 
@@ -223,21 +207,12 @@ def rpa(qc, frozen=0, auxbasis=None, nfreq=48, freq_scale=1.0):
     frozen, nfreq, freq_scale = int(frozen), int(nfreq), float(freq_scale)
     if frozen < 0:
         raise ValueError("rpa: frozen must be >= 0, got %d" % frozen)
-    if nfreq < 1:
-        raise ValueError("rpa: nfreq must be >= 1, got %d" % nfreq)
-    if not freq_scale > 0.0:
-        raise ValueError("rpa: freq_scale must be positive, got %g" % freq_scale)
-    _unsupported(qc)
+    check_frequency_args("rpa", nfreq, freq_scale)
+    unsupported(qc)
     assert qc._has_run, "run() the calculation first"
-    from .response import state_memo
-    memo = state_memo(qc)
-    h = qc._engine.hamilton
-    own = h.df is not None and h.df.exchange
-    key = ("rpa", frozen, None if own else (auxbasis if isinstance(auxbasis, str) or auxbasis is None else id(auxbasis)), nfreq, freq_scale)
-    if key not in memo:
-        with torch.no_grad():
-            memo[key] = _compute(qc, frozen, auxbasis, nfreq, freq_scale) + (_e_exx(qc),)
-    df, e_corr, e_2nd, e_dmp2, freqs, weights, integrand, e_exx = memo[key]
+    df, e_corr, e_2nd, e_dmp2, freqs, weights, integrand, e_exx = memoised(
+        qc, ("rpa", frozen, aux_key(qc, auxbasis), nfreq, freq_scale),
+        lambda: _compute(qc, frozen, auxbasis, nfreq, freq_scale) + (_e_exx(qc),))
     return RPA(e_corr, e_2nd, e_dmp2, e_exx, freqs, weights, integrand, frozen, df)
 
 

@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 import dqc_amd  # noqa: E402
 from dqc_amd import lib  # noqa: E402
 from dqc_amd.gw import correlation_part  # noqa: E402
-from dqc_amd.mp2 import _orbitals, transform_ov  # noqa: E402
+from dqc_amd.postscf import orbitals, transform_ov  # noqa: E402
 from dqc_amd.rpa import frequency_grid  # noqa: E402
 from tests import molecules as M  # noqa: E402
 
@@ -77,7 +77,7 @@ def main():
     t_scf = time.time() - t0
     h = qc._engine.hamilton
     b = h.df._b
-    co, cv, eo, ev = _orbitals(qc, 0)[0]
+    co, cv, eo, ev = orbitals(qc, 0)[0]
     c_all = torch.cat([co, cv], dim=1)
     no, nmo, naux, nfreq = int(co.shape[1]), int(c_all.shape[1]), int(b.shape[0]), 100
     freqs, _ = frequency_grid(nfreq, 1.0)

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import dqc_amd  # noqa: E402
 from dqc_amd import lib  # noqa: E402
-from dqc_amd.mp2 import _orbitals, transform_ov  # noqa: E402
+from dqc_amd.postscf import orbitals, transform_ov  # noqa: E402
 from dqc_amd.rpa import frequency_grid  # noqa: E402
 from tests import molecules as M  # noqa: E402
 
@@ -59,7 +59,7 @@ def main():
     qc = dqc_amd.HF(mol).run()
     t_scf = time.time() - t0
     h = qc._engine.hamilton
-    co, cv, eo, ev = _orbitals(qc, 0)[0]
+    co, cv, eo, ev = orbitals(qc, 0)[0]
     bov = transform_ov(h.df._b, co, cv)
     no, naux, ldv = (int(x) for x in bov.shape)
     nv, nfreq = int(ev.numel()), 48
