@@ -14,5 +14,6 @@ from .response import OrbitalHessian  # noqa: F401
 from .mp2 import mp2, MP2, mp2_density, MP2Density  # noqa: F401
 from .rpa import rpa, RPA  # noqa: F401
 from .gw import gw, GW  # noqa: F401
+from .bse import bse, BSE  # noqa: F401
 
 __version__ = "0.1.0"

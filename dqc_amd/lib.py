@@ -108,6 +108,9 @@ def load():
     lib.dqc_rpa_work_doubles.restype = c_sz
     lib.dqc_rpa_response.argtypes = [c_dp] * 5 + [c_int] * 5 + [ctypes.c_double, c_int, c_dp, c_vp]
     lib.dqc_gw_screened_diag.argtypes = [c_dp] * 3 + [c_int] * 5 + [c_vp]
+    lib.dqc_bse_work_doubles.argtypes = [c_int] * 6
+    lib.dqc_bse_work_doubles.restype = c_sz
+    lib.dqc_bse_exchange.argtypes = [c_dp] * 4 + [c_int] * 8 + [c_dp, c_vp]
     lib.dqc_eri_tiles_to_dense.argtypes = [c_dp, c_dp, c_int, c_vp]
     lib.dqc_jk_from_tiles.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_vp]
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
@@ -546,6 +549,43 @@ def gw_screened_diag(wc, bn, nm, out=None):
     out = _out_like("gw_screened_diag", out, (nfreq, ntarget, nm), bn, "bn")
     with _on(bn.device) as st_:
         _check(load().dqc_gw_screened_diag(_ptr(out), _ptr(wc), _ptr(bn), ntarget, nm, ldm, naux, nfreq, st_), "dqc_gw_screened_diag")
+    return out
+
+
+def bse_exchange(l, r, x, nr, ns, out=None, work=None):
+    """product of trial vectors with a four-index quantity in two fitted factors (csrc/bse.hip: dqc_bse_exchange): l (np, naux, ldr) and
+    r (nq, naux, lds) as `mp2.transform_ov` makes them, nr <= ldr and ns <= lds real columns, x (nvec, nr, ns) ->
+    out (nvec, np, nq), out[v, p, q] = sum_P sum_rs l[p, P, r] x[v, r, s] r[q, P, s].  out: the tensor to write into; work: a buffer
+    of at least dqc_bse_work_doubles doubles to reuse (one is allocated when it is missing or too small).
+    No atomics: bit-reproducible.  The arguments are checked before anything is launched"""
+    for name, t in (("l", l), ("r", r)):
+        if t.dim() != 3 or t.shape[2] % 16:
+            raise DqcAmdError("bse_exchange: %s must be (n, naux, ld) with ld a multiple of 16, got %s" % (name, tuple(t.shape)))
+    np_, naux, ldr = (int(n) for n in l.shape)
+    nq, lds = int(r.shape[0]), int(r.shape[2])
+    nr, ns = int(nr), int(ns)
+    if int(r.shape[1]) != naux:
+        raise DqcAmdError("bse_exchange: l holds %d auxiliary functions and r %d" % (naux, int(r.shape[1])))
+    if nr < 0 or nr > ldr or ns < 0 or ns > lds:
+        raise DqcAmdError("bse_exchange: (%d, %d) columns asked of slabs of (%d, %d)" % (nr, ns, ldr, lds))
+    if x.dim() != 3 or int(x.shape[1]) != nr or int(x.shape[2]) != ns:
+        raise DqcAmdError("bse_exchange: x must be (nvec, %d, %d), got %s" % (nr, ns, tuple(x.shape)))
+    nvec = int(x.shape[0])
+    for name, t in (("l", l), ("r", r), ("x", x)):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise DqcAmdError("bse_exchange: %s must be a contiguous float64 tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if l.device != r.device or l.device != x.device or l.device.type != "cuda":
+        raise DqcAmdError("bse_exchange: l, r and x must be on one GPU, got %s, %s and %s" % (l.device, r.device, x.device))
+    _aligned16("bse_exchange", l)
+    _aligned16("bse_exchange", r)
+    out = _out_like("bse_exchange", out, (nvec, np_, nq), l, "l")
+    L = load()
+    need = int(L.dqc_bse_work_doubles(np_, nq, nr, ns, naux, nvec))
+    if need and (work is None or work.numel() < need or work.dtype != torch.float64 or work.device != l.device or not work.is_contiguous()):
+        work = torch.empty(need, dtype=torch.float64, device=l.device)
+    with _on(l.device) as st_:
+        _check(L.dqc_bse_exchange(_ptr(out), _ptr(l), _ptr(r), _ptr(x), np_, nq, nr, ns, ldr, lds, naux, nvec, _ptr(work) if need else None, st_),
+               "dqc_bse_exchange")
     return out
 
 

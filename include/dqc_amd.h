@@ -354,6 +354,20 @@ int dqc_rpa_response(double *d_q, const double *d_bov, const double *d_eo, const
 int dqc_gw_screened_diag(double *d_w, const double *d_wc, const double *d_bn, int ntarget, int nm, int ldm, int naux, int nfreq,
                          void *stream);
 
+/* Product of a block of trial vectors with a four-index quantity held as two density-fitted factors (the screened direct and exchange
+ * terms of the Bethe-Salpeter equation), fused: the intermediate Z_P = X_v R_P^T is never stored.
+ *   out[v, p, q] = sum_P sum_{r < nr} sum_{s < ns} L[p, P, r] X[v, r, s] R[q, P, s]
+ * d_l (np, naux, ldr) and d_r (nq, naux, lds): one slab per p and per q, ldr >= nr and lds >= ns multiples of 16, 16-byte aligned; the
+ * columns past nr and ns are padding: never used, whatever they hold.  d_x (nvec, nr, ns) and d_out (nvec, np, nq): contiguous, no
+ * padding.  nvec, np or nq zero: nothing to write; naux, nr or ns zero: zeros (no kernel).  d_work: dqc_bse_work_doubles doubles --
+ * zero unless the sum over P is split over blocks (few output panels), then one slot of nvec np nq doubles per part, added in slot
+ * order: no atomics, bit-reproducible; may be null when the size is zero.  Every argument is checked before anything is launched
+ * (negative counts, ldr or lds no multiple of 16 or too small, null pointers, a misaligned tensor, more than 2^31 - 1 blocks:
+ * DQC_EINVAL).  Only enqueues. */
+size_t dqc_bse_work_doubles(int np, int nq, int nr, int ns, int naux, int nvec);
+int dqc_bse_exchange(double *d_out, const double *d_l, const double *d_r, const double *d_x, int np, int nq, int nr, int ns, int ldr,
+                     int lds, int naux, int nvec, double *d_work, void *stream);
+
 /* ---- nuclear gradients of the SCF energy   ------------------------------------
  * The reference differentiates through its "ip" derivative integrals (molintor.py:463-500) and the implicit-function
  * backward of the SCF fixed point (scf_qccalc.py:63-67, 109-113); at convergence that is
