@@ -349,6 +349,10 @@ extern "C" int dqc_xc_eval(double *d_edens, double *d_vrho, double *d_vgrad, con
 
 namespace dqc {
 
+// The floor under sigma in the meta-GGA kernels only keeps s^(-1/2) and sqrt'(sigma) finite; the derivatives pass through it.  It is far
+// below any sigma of a density above the cutoff: at 1e-40 it reached 1e-5 of e in the tail (rho = 1e-14, where it meant s = 8e-3).
+constexpr double kMggaSigmaFloor = 1e-100;
+
 __host__ __device__ inline bool xc_id_is_mgga(int id) {
     return id == DQC_XC_MGGA_X_SCAN || id == DQC_XC_MGGA_C_SCAN || id == DQC_XC_MGGA_X_TPSS || id == DQC_XC_MGGA_C_TPSS;
 }
@@ -534,7 +538,7 @@ DQC_DEV D5 tpss_c_core(D5 u, D5 d, D5 suu, D5 sud, D5 sdd, D5 z) {
     D5 zeta = (u - d) / rho;
     zeta.v = fmin(fmax(zeta.v, -1.0 + 1e-10), 1.0 - 1e-10);
     D5 sig = suu + 2.0 * sud + sdd;
-    sig.v = fmax(sig.v, 1e-40);
+    sig.v = fmax(sig.v, kMggaSigmaFloor);
     D5 opz = 1.0 + zeta, omz = 1.0 - zeta;
     D5 phi = 0.5 * (p5(opz, 2.0 / 3.0) + p5(omz, 2.0 / 3.0));
     D5 eps = pbe_c_eps5(rho, pw92_pol_eps(rho, zeta, a3), phi * phi, phi * phi * phi, sig);
@@ -568,13 +572,13 @@ __global__ __launch_bounds__(256) void xc_mgga_pol2_kernel(double *__restrict__ 
         if (ru + rd > 1e-15) {
             ru = fmax(ru, 0.5e-15);
             rd = fmax(rd, 0.5e-15);
-            const double suu = fmax(gu[0] * gu[0] + gu[1] * gu[1] + gu[2] * gu[2], 1e-40);
-            const double sdd = fmax(gd[0] * gd[0] + gd[1] * gd[1] + gd[2] * gd[2], 1e-40);
+            const double suu = fmax(gu[0] * gu[0] + gu[1] * gu[1] + gu[2] * gu[2], kMggaSigmaFloor);
+            const double sdd = fmax(gd[0] * gd[0] + gd[1] * gd[1] + gd[2] * gd[2], kMggaSigmaFloor);
             const double sud = gu[0] * gd[0] + gu[1] * gd[1] + gu[2] * gd[2];
             const double tk = fmax(tu_[i] + td_[i], 1e-20);
             for (int t = 0; t < terms.n; t++) {
                 if (terms.id[t] == DQC_XC_MGGA_C_SCAN) {
-                    const double sig = fmax(suu + 2.0 * sud + sdd, 1e-40);
+                    const double sig = fmax(suu + 2.0 * sud + sdd, kMggaSigmaFloor);
                     const D5 f = f_mgga_c_scan_pol(var5(ru, 0), var5(rd, 1), var5(sig, 2), var5(tk, 3));
                     e += terms.c[t] * f.v;
                     dv[0] += terms.c[t] * f.d[0]; dv[1] += terms.c[t] * f.d[1];
@@ -583,7 +587,7 @@ __global__ __launch_bounds__(256) void xc_mgga_pol2_kernel(double *__restrict__ 
                 } else {  // DQC_XC_MGGA_C_TPSS
                     const D5 u = var5(ru, 0), d = var5(rd, 1), a = var5(suu, 2), b = var5(sud, 3), c = var5(sdd, 4);
                     D5 sg = a + 2.0 * b + c;
-                    sg.v = fmax(sg.v, 1e-40);
+                    sg.v = fmax(sg.v, kMggaSigmaFloor);
                     D5 z = sg / ((8.0 * tk) * (u + d));
                     const bool over = z.v > 1.0;
                     if (over) z = c5(1.0);
@@ -622,7 +626,7 @@ __global__ __launch_bounds__(256) void xc_mgga_pol_kernel(double *__restrict__ e
         if (ru + rd > 1e-15) {
             ru = fmax(ru, 0.5e-15);
             rd = fmax(rd, 0.5e-15);
-            const double sig = fmax(gt[0] * gt[0] + gt[1] * gt[1] + gt[2] * gt[2], 1e-40), tk = fmax(tu_[i] + td_[i], 1e-20);
+            const double sig = fmax(gt[0] * gt[0] + gt[1] * gt[1] + gt[2] * gt[2], kMggaSigmaFloor), tk = fmax(tu_[i] + td_[i], 1e-20);
             for (int t = 0; t < terms.n; t++) {
                 const D5 f = f_mgga_c_scan_pol(var5(ru, 0), var5(rd, 1), var5(sig, 2), var5(tk, 3));
                 e += terms.c[t] * f.v;
@@ -647,7 +651,7 @@ __global__ __launch_bounds__(256) void xc_mgga_kernel(double *__restrict__ edens
         const double gx = grho[i], gy = grho[(size_t)n + i], gz = grho[2 * (size_t)n + i];
         double e = 0, vr = 0, vs = 0, vt = 0;
         if (r > 1e-15) {
-            const double sig = fmax(gx * gx + gy * gy + gz * gz, 1e-40), tk = fmax(tau[i], 1e-20);
+            const double sig = fmax(gx * gx + gy * gy + gz * gz, kMggaSigmaFloor), tk = fmax(tau[i], 1e-20);
             const Dual dr = mk(r, 1.0, 0.0), ds = mk(sig, 0.0, 1.0);
             auto term = [&](const int tid_, double &fv, double &fr, double &fs, double &ft) {
                 ft = 0.0;

@@ -9,6 +9,7 @@ Hybrid functionals: an object may carry `exx_fraction`, the fraction a of exact 
 grid part, F = h + J - a K / 2 + Vxc.  `get_xc` knows "hyb_gga_xc_pbeh" (alias "pbe0"), "hyb_gga_xc_b3lyp5" and the general
 spelling "0.25 * hf + 0.75 * gga_x_pbe + gga_c_pbe", in which the pseudo-term `hf` has no grid part and adds its coefficient to
 the fraction.  The fraction is read ONCE, as a float, when the calculation is set up: it is not a trainable parameter."""
+import math
 import re
 
 import torch
@@ -21,6 +22,8 @@ _FAMILY = {"lda_x": 1, "lda_c_pw": 1, "lda_c_pw_mod": 1, "lda_c_vwn": 1, "gga_x_
            # round 4: exchange GGAs given by an enhancement factor (one table entry each, csrc/xc_funcs.hpp), PZ81, P86
            "gga_x_pw91": 2, "gga_x_b86": 2, "gga_x_g96": 2, "gga_x_pw86": 2, "gga_x_optx": 2, "gga_x_wc": 2, "lda_c_pz": 1, "gga_c_p86": 2}
 
+
+_SPIN_FLOOR = math.nextafter(0.5e-15, 1.0)
 
 # hybrids by name: (terms of the grid part, fraction of exact exchange)
 _HYBRIDS = {
@@ -102,7 +105,9 @@ class LibXC(BaseXC):
         e, pots = 0.0, []
         for d in (densinfo.u, densinfo.d):
             if mx:
-                es, v, vg, vt = lib.xc_eval_mgga(mx, (2.0 * d.value).contiguous(), (2.0 * d.grad).contiguous(),
+                # a spin density is raised to the spin floor 0.5e-15, as in the polarised kernels (the next double above it: the
+                # closed-shell kernel asks for 2 rho_s > 1e-15)
+                es, v, vg, vt = lib.xc_eval_mgga(mx, (2.0 * d.value.clamp(min=_SPIN_FLOOR)).contiguous(), (2.0 * d.grad).contiguous(),
                                                  (2.0 * d.kin).contiguous(), want_e=want_e, want_v=want_v)
                 if want_e:
                     e = e + 0.5 * es
@@ -111,6 +116,12 @@ class LibXC(BaseXC):
             z = torch.zeros_like
             pots.append(ValGrad(value=v if v is not None else z(d.value), grad=vg if vg is not None else z(d.grad), lapl=None,
                                 kin=vt if vt is not None else z(d.value)) if want_v else None)
+        if mx:  # the density cutoff is on rho_u + rho_d, as in the polarised kernels; the unpolarised kernel applied it to 2 rho_s
+            live = (densinfo.u.value + densinfo.d.value) > 1e-15
+            if want_e:
+                e = e * live
+            for p_ in pots if want_v else ():
+                p_.value, p_.grad, p_.kin = p_.value * live, p_.grad * live, p_.kin * live
         if mc:  # correlation: the general polarised form (depends on rho_u, rho_d, |grad rho|^2, tau_u + tau_d)
             u, d = densinfo.u, densinfo.d
             ec, (vu, vd), vgc, vtc = lib.xc_eval_mgga_pol2(mc, u.value.contiguous(), d.value.contiguous(), u.grad.contiguous(),

@@ -386,6 +386,11 @@ def compute_pol(xc, ru, rd, gu=None, gd=None):
     return e, (vr[0], vr[1]), (vgu, vgd), vs
 
 
+# The floor under sigma in the meta-GGAs only keeps s^(-1/2) and sqrt'(sigma) finite; the derivatives pass through it.  It is far below
+# any sigma of a density above the cutoff: at 1e-40 it reached 1e-5 of e in the tail (rho = 1e-14, where it meant s = 8e-3).
+_SIGMA_FLOOR = 1e-100
+
+
 # =====================================================================================================
 # meta-GGA: SCAN exchange (mgga_x_scan), unpolarised.  Closed form = scan_e_true of
 # dqc/test/test_xc.py:427-455 (Sun, Ruzsinszky, Perdew PRL 115, 036402); inputs rho, sigma, tau (the
@@ -403,7 +408,7 @@ def mgga_x_scan(rho, sigma, tau):
     rho, sigma, tau = (np.asarray(a, dtype=np.float64) for a in (rho, sigma, tau))
     mask = rho > DENS_THRESHOLD
     r_ = np.where(mask, rho, 1.0)
-    s_ = np.where(mask, np.maximum(sigma, 1e-40), 1.0)
+    s_ = np.where(mask, np.maximum(sigma, _SIGMA_FLOOR), 1.0)
     t_ = np.where(mask, np.maximum(tau, 1e-20), 1.0)
     r, sg, ta = Dual.var(r_, 0, 3), Dual.var(s_, 1, 3), Dual.var(t_, 2, 3)
     a1, c1x, c2x, dx = 4.9479, 0.667, 0.8, 1.24
@@ -499,7 +504,7 @@ def mgga_c_scan_pol(ru, rd, sigma, tau):
     """-> e (= rho eps_c), (d/drho_u, d/drho_d), d/dsigma_total, d/dtau_total.  In libxc's polarised outputs
     vsigma = (d, 2 d, d)/dsigma_total for (uu, ud, dd) and vtau_u = vtau_d = d/dtau_total."""
     mask, ru_, rd_ = _masked(ru, rd)
-    sg_ = np.where(mask, np.maximum(np.asarray(sigma, float), 1e-40), 1.0)
+    sg_ = np.where(mask, np.maximum(np.asarray(sigma, float), _SIGMA_FLOOR), 1.0)
     ta_ = np.where(mask, np.maximum(np.asarray(tau, float), 1e-20), 1.0)
     u, d, sg, ta = (Dual.var(x, i, 4) for i, x in enumerate((ru_, rd_, sg_, ta_)))
     e = _scan_c_energy(u, d, sg, ta)
@@ -531,7 +536,7 @@ def mgga_x_tpss(rho, sigma, tau):
     rho, sigma, tau = (np.asarray(a, dtype=np.float64) for a in (rho, sigma, tau))
     mask = rho > DENS_THRESHOLD
     r_ = np.where(mask, rho, 1.0)
-    s_ = np.where(mask, np.maximum(sigma, 1e-40), 1.0)
+    s_ = np.where(mask, np.maximum(sigma, _SIGMA_FLOOR), 1.0)
     t_ = np.where(mask, np.maximum(tau, 1e-20), 1.0)
     r, sg, ta = Dual.var(r_, 0, 3), Dual.var(s_, 1, 3), Dual.var(t_, 2, 3)
     k, b, c, e, mu = (_TPSS_X[n] for n in ("kappa", "b", "c", "e", "mu"))
@@ -604,12 +609,12 @@ def mgga_c_tpss_pol(ru, rd, suu, sud, sdd, tau):
     """-> e (= n eps_c), (d/drho_u, d/drho_d), (d/dsigma_uu, d/dsigma_ud, d/dsigma_dd), d/dtau_total"""
     mask, ru_, rd_ = _masked(ru, rd)
     fl = lambda a, lo: np.where(mask, np.maximum(np.asarray(a, float), lo), 1.0)  # noqa: E731
-    suu_, sdd_, ta_ = fl(suu, 1e-40), fl(sdd, 1e-40), fl(tau, 1e-20)
+    suu_, sdd_, ta_ = fl(suu, _SIGMA_FLOOR), fl(sdd, _SIGMA_FLOOR), fl(tau, 1e-20)
     sud_ = np.where(mask, np.asarray(sud, float), 1.0)
     u, d, guu, gud, gdd, ta = (Dual.var(x, i, 6) for i, x in enumerate((ru_, rd_, suu_, sud_, sdd_, ta_)))
     rho, zeta = _safe_zeta(u, d)
     sig = guu + 2.0 * gud + gdd
-    sig.v = np.maximum(sig.v, 1e-40)
+    sig.v = np.maximum(sig.v, _SIGMA_FLOOR)
     eps = _pbe_c_eps(rho, zeta, sig)
     et_u = _dmax(_pbe_c_eps(u, None, guu, ferro=True), eps)
     et_d = _dmax(_pbe_c_eps(d, None, gdd, ferro=True), eps)

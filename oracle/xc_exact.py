@@ -28,6 +28,30 @@ zero where rho_u + rho_d <= 1e-15; a spin density is raised to 0.5e-15; zeta ent
 clamped to 1 -+ 1e-10 with the derivatives of the unclamped zeta (a constant offset `dz`).  `ns.switch(x)` is a series threshold:
 x in double, 0 at 50 digits (the truth never takes a truncated series).  A gradient that is exactly zero is evaluated at a reduced
 gradient of 1e-30, where every functional is smooth (the derivatives by sigma of gga_x_g96 diverge at sigma = 0: see the tests).
+
+THE FOUR META-GGAS (MGGA_NAMES: mgga_x_scan, mgga_c_scan, mgga_x_tpss, mgga_c_tpss; value and first order) are written the same way
+over (rho_u, rho_d, sigma_uu, sigma_ud, sigma_dd, tau_u, tau_d), from Sun, Ruzsinszky, Perdew, PRL 115, 036402 (2015) and Tao,
+Perdew, Staroverov, Scuseria, PRL 91, 146401 (2003) with libxc's constants as dqc_amd/csrc/xc.hip names them.  Both correlation
+functionals see tau_u + tau_d only; the exchange functionals are spin-scaled, one channel per spin at (2 rho_s, 4 sigma_ss, 2 tau_s).
+Additive parts:
+    exchange, per spin      SCAN: e_x^unif h1 g and e_x^unif f(alpha) (h0 - h1) g; TPSS: one part (its F_x has no cancellation)
+    mgga_c_scan             rho eps_LSDA, rho H1, rho f(alpha) eps0, -rho f(alpha) eps1
+    mgga_c_tpss             rho eps_LSDA and rho H of PBE; the same two times C(zeta, xi) z^2; the sum over the spins of
+                            max(eps_PBE(n_s, 0), eps_PBE), again as its LSDA and its gradient part (eps_LSDA + H cancels at large s, and every
+                            term that holds eps_PBE inherits that cancellation); d eps_revPKZB^2 z^3
+Conventions shared with the kernels, part of the functionals' definition here:
+    the density cutoff 1e-15 and the spin floor 0.5e-15, as above
+    tau is raised to TAU_THRESHOLD = 1e-20, libxc's default: each exchange channel sees max(2 tau_s, 1e-20), the correlation
+        functionals max(tau_u + tau_d, 1e-20), and the derivatives are those at the raised value (the offsets of effective_point)
+    where tau_W > tau (z = tau_W / tau > 1) TPSS exchange takes the CONSTANTS z = 1, alpha = 0, TPSS correlation the constant z = 1
+        (d/dtau = 0); SCAN applies no clamp on alpha < 0.  A constant is a branch decided at the point: the steps of the differences
+        (1e-20) never reach from the closest approach sampled (1e-12) to z = 1, so the branch is the same at x + h and x - h
+    these two are the project's own, UNPINNED against libxc as xc.hip says of them: the reference holds no literal of either
+The sigma floor of the kernels is NOT a convention: the truth takes sigma as given, and an exact zero at a reduced gradient of TINY_S.
+The alpha = 1 seam: f(alpha) and all its derivatives vanish from both sides (exp(-0.64e12) at the edge of the 1e-12 window in which
+the kernels and the double backend return 0); a central difference may straddle it and changes nothing (step halving is tested on
+both sides down to |1 - alpha| = 1e-14).  At a point with an exactly zero gradient the scale of every first derivative of a meta-GGA
+is at least TINY_S of scale(e) / |x_k|: d/dtau through z is of the order sigma^2 there and its limit is 0 (mp_eval).
 """
 from fractions import Fraction as Fr
 
@@ -38,6 +62,7 @@ NAMES = ["lda_x", "lda_c_pw", "lda_c_pw_mod", "lda_c_vwn", "lda_c_pz", "gga_x_pb
          "gga_x_optx", "gga_x_wc"]
 DPS = 50
 DENS_THRESHOLD, ZETA_THRESHOLD, TINY_S = 1e-15, 1e-10, 1e-30
+TAU_THRESHOLD = 1e-20  # libxc's default: the kinetic energy density a meta-GGA sees is raised to it
 
 
 # ------------------------------------------------------------------------------------------------ the two backends
@@ -386,7 +411,166 @@ def gga_c_lyp(ns, ru, rd, suu, sud, sdd, dz=0.0):
             om * ((2.0 / 3.0) * r2 - rd * rd) * suu)
 
 
+# ------------------------------------------------------------------------------------------------ meta-GGA
+# e(rho_u, rho_d, sigma_uu, sigma_ud, sigma_dd, tau_u, tau_d); `off` = (dz, dc): the offset of zeta and the offset that turns
+# tau_u + tau_d into what the correlation functionals see (effective_point)
+def _kf2(ns, n):  # (3 pi^2 n)^(2/3)
+    k = ns.cbrt(3.0 * ns.pi * ns.pi * n)
+    return k * k
+
+
+def _mx_parts(ns, F, ru, rd, suu, sdd, tu, td):
+    """spin-scaled meta-GGA exchange: e = sum_s (1/2) e_x^unif(n) F(p, z, alpha) at n = 2 rho_s, |grad n|^2 = 4 sigma_ss, tau = 2 tau_s,
+    with p = s^2 = |grad n|^2 / (4 (3 pi^2)^(2/3) n^(8/3)), z = tau_W / tau, alpha = (tau - tau_W) / tau_unif, tau_W = |grad n|^2 / (8 n),
+    tau_unif = (3/10) (3 pi^2)^(2/3) n^(5/3); F returns the factors of the additive parts"""
+    ax = -0.75 * ns.cbrt(3.0 / ns.pi)
+    out = []
+    for r, s, t in ((ru, suu, tu), (rd, sdd, td)):
+        n, sg, ta = 2.0 * r, 4.0 * s, 2.0 * t
+        kf2 = _kf2(ns, n)
+        tw = sg / (8.0 * n)
+        f = F(sg / (4.0 * kf2 * n * n), tw / ta, (ta - tw) / (0.3 * kf2 * n))
+        out += [0.5 * ax * n * ns.cbrt(n) * v for v in f]
+    return tuple(out)
+
+
+def _scan_switch(ns, alpha, c1, c2, d):
+    """f(alpha) = exp(-c1 alpha / (1 - alpha)) for alpha < 1, -d exp(c2 / (1 - alpha)) for alpha > 1: flat to all orders at alpha = 1, where
+    the double backend takes 0 inside |1 - alpha| < 1e-12 (exp(-0.64e12) at its edge); the truth has no window"""
+    om = 1.0 - alpha
+    near = om * om < ns.switch(1e-24)
+    lo = alpha < 1.0
+    om_lo = ns.where(near, 1.0, ns.where(lo, om, 1.0))
+    om_hi = ns.where(near, -1.0, ns.where(lo, -1.0, om))
+    f_lo = ns.exp(-c1 * ns.where(near, 0.5, ns.where(lo, alpha, 0.5)) / om_lo)
+    f_hi = -d * ns.exp(c2 / om_hi)
+    return ns.where(near, 0.0, ns.where(lo, f_lo, f_hi))
+
+
+def mgga_x_scan(ns, ru, rd, suu, sud, sdd, tu, td, off=(0.0, 0.0)):
+    """Sun, Ruzsinszky, Perdew, PRL 115, 036402 (2015), eqs. 1-8 and the supplementary material; no clamp on alpha < 0.
+    Parts per spin: e_x^unif h1 g and e_x^unif f (h0 - h1) g"""
+    a1, c1x, c2x, dx, k1, h0, b3, mu = 4.9479, 0.667, 0.8, 1.24, 0.065, 1.174, 0.5, 10.0 / 81.0
+    b2 = ns.sqrt(5913.0 / 405000.0)
+    b1 = (511.0 / 13500.0) / (2.0 * b2)
+    b4 = mu * mu / k1 - 1606.0 / 18225.0 - b1 * b1
+
+    def F(p, z, alpha):
+        om = 1.0 - alpha
+        y = b1 * p + b2 * om * ns.exp(-b3 * om * om)
+        x = mu * p * (1.0 + (b4 * p / mu) * ns.exp(-(abs(b4) / mu) * p)) + y * y
+        h1 = 1.0 + k1 * (x / (k1 + x))  # = 1 + k1 - k1 / (1 + x / k1), exactly 1 at x = 0
+        g = -ns.expm1(-a1 / ns.pow(p, Fr(1, 4)))
+        f = _scan_switch(ns, alpha, c1x, c2x, dx)
+        return (h1 * g, f * (h0 - h1) * g)
+    return _mx_parts(ns, F, ru, rd, suu, sdd, tu, td)
+
+
+def mgga_x_tpss(ns, ru, rd, suu, sud, sdd, tu, td, off=(0.0, 0.0)):
+    """Tao, Perdew, Staroverov, Scuseria, PRL 91, 146401 (2003), eqs. 5-10; where tau_W > tau: the constants z = 1, alpha = 0.
+    One part per spin"""
+    kappa, b, c, e, mu = 0.804, 0.40, 1.59096, 1.537, 0.21951
+    se = ns.sqrt(e)
+
+    def F(p, z, alpha):
+        over = z > 1.0
+        z, alpha = ns.where(over, 1.0, z), ns.where(over, 0.0, alpha)
+        qb = (9.0 / 20.0) * (alpha - 1.0) / ns.sqrt(1.0 + b * alpha * (alpha - 1.0)) + 2.0 * p / 3.0
+        z2 = z * z
+        w = 0.36 * z2  # (3 z / 5)^2
+        num = ((10.0 / 81.0 + c * z2 / ((1.0 + z2) * (1.0 + z2))) * p + (146.0 / 2025.0) * qb * qb
+               - (73.0 / 405.0) * qb * ns.sqrt(0.5 * w + 0.5 * p * p) + ((10.0 / 81.0) * (10.0 / 81.0) / kappa) * p * p
+               + 2.0 * se * (10.0 / 81.0) * w + e * mu * p * p * p)
+        x = num / ((1.0 + se * p) * (1.0 + se * p))
+        return (1.0 + kappa * (x / (kappa + x)),)  # = 1 + kappa - kappa / (1 + x / kappa), exactly 1 at x = 0
+    return _mx_parts(ns, F, ru, rd, suu, sdd, tu, td)
+
+
+def mgga_c_scan(ns, ru, rd, suu, sud, sdd, tu, td, off=(0.0, 0.0)):
+    """Sun, Ruzsinszky, Perdew, PRL 115, 036402 (2015), eqs. 9-17 and the supplementary material, libxc's constants; no clamp on
+    alpha < 0.  Parts: rho eps_LSDA, rho H1, rho f eps0, -rho f eps1"""
+    b1c, b2c, b3c, c1c, c2c, dc_, chi_inf, gcnst = 0.0285764, 0.0889, 0.125541, 0.64, 1.5, 0.7, 0.12802585262625815, 2.3631
+    dz, dc = off
+    rho, rs, zeta = _rs_zeta(ns, ru, rd, dz)
+    lda = _pw92_parts(ns, ru, rd, dz, True)
+    eps = (lda[0] + lda[1] + lda[2] + lda[3]) / rho
+    gamma = (1.0 - ns.log(2.0)) / (ns.pi * ns.pi)
+    zp, zm = 1.0 + zeta, 1.0 - zeta
+    cp, cm = ns.cbrt(zp), ns.cbrt(zm)
+    phi = 0.5 * (cp * cp + cm * cm)
+    phi3 = phi * phi * phi
+    dxz = 0.5 * (zp * cp + zm * cm)
+    dsz = 0.5 * (zp * cp * cp + zm * cm * cm)
+    kf = ns.cbrt(3.0 * ns.pi * ns.pi * rho)
+    sig = suu + 2.0 * sud + sdd
+    s2 = sig / (4.0 * kf * kf * rho * rho)
+    alpha = ((tu + td + dc) - sig / (8.0 * rho)) / (0.3 * kf * kf * rho * dsz)
+    f = _scan_switch(ns, alpha, c1c, c2c, dc_)
+    beta = 0.066725 * (1.0 + 0.1 * rs) / (1.0 + 0.1778 * rs)
+    t2 = sig / (4.0 * phi * phi * (4.0 * kf / ns.pi) * rho * rho)
+    w1 = ns.expm1(-eps / (gamma * phi3))
+    # 1 - (1 + y)^(-1/4) without the cancellation at small y
+    h1 = gamma * phi3 * ns.log1p(-w1 * ns.expm1(-0.25 * ns.log1p(4.0 * (beta / (gamma * w1)) * t2)))
+    e0 = -b1c / (1.0 + b2c * ns.sqrt(rs) + b3c * rs)
+    w0 = ns.expm1(-e0 / b1c)
+    z2 = zeta * zeta
+    z6 = z2 * z2 * z2
+    gc = (1.0 - gcnst * (dxz - 1.0)) * (1.0 - z6 * z6)
+    eps0 = (e0 + b1c * ns.log1p(-w0 * ns.expm1(-0.25 * ns.log1p(4.0 * chi_inf * s2)))) * gc
+    return (rho * eps, rho * h1, rho * f * eps0, -(rho * f * (eps + h1)))
+
+
+def _pbe_eps(ns, rho, eps, phi, sig):
+    """(eps_LSDA, H) of PBE correlation (PRL 77, 3865, eqs. 3, 7, 8) of a density rho with the LSDA energy eps and the spin factor phi"""
+    gamma, bg = (1.0 - ns.log(2.0)) / (ns.pi * ns.pi), _BETA_PBE * ns.pi * ns.pi / (1.0 - ns.log(2.0))
+    phi3 = phi * phi * phi
+    kf = ns.cbrt(3.0 * ns.pi * ns.pi * rho)
+    t2 = sig / (4.0 * phi * phi * (4.0 * kf / ns.pi) * rho * rho)
+    at2 = bg / ns.expm1(-eps / (gamma * phi3)) * t2
+    return eps, gamma * phi3 * ns.log1p(bg * t2 * (1.0 + at2) / (1.0 + at2 + at2 * at2))
+
+
+def mgga_c_tpss(ns, ru, rd, suu, sud, sdd, tu, td, off=(0.0, 0.0)):
+    """Tao, Perdew, Staroverov, Scuseria, PRL 91, 146401 (2003), eqs. 11-14:
+        eps_revPKZB = eps_PBE [1 + C z^2] - [1 + C] z^2 sum_s (n_s / n) max(eps_PBE(n_s, 0, grad n_s, 0), eps_PBE),  z = tau_W / tau,
+        e = n eps_revPKZB [1 + d eps_revPKZB z^3],  d = 2.8,  C(zeta, xi) = (0.53 + 0.87 zeta^2 + 0.50 zeta^4 + 2.26 zeta^6)
+        / {1 + xi^2 [(1 + zeta)^(-4/3) + (1 - zeta)^(-4/3)] / 2}^4,  xi = |grad zeta| / (2 (3 pi^2 n)^(1/3));
+    where z > 1: the constant z = 1.  Parts: n eps_LSDA and n H (the two of PBE); the same two times C z^2; the sum of the maxima, again
+    as its LSDA and its gradient part (eps_LSDA + H cancels at large s, and every term that holds eps_PBE inherits that); the d term"""
+    dz, dc = off
+    rho, rs, zeta = _rs_zeta(ns, ru, rd, dz)
+    lda = _pw92_parts(ns, ru, rd, dz, True)
+    zp, zm = 1.0 + zeta, 1.0 - zeta
+    cp, cm = ns.cbrt(zp), ns.cbrt(zm)
+    sig = suu + 2.0 * sud + sdd
+    el, hl = _pbe_eps(ns, rho, (lda[0] + lda[1] + lda[2] + lda[3]) / rho, 0.5 * (cp * cp + cm * cm), sig)
+    eps = el + hl
+    ferro = 1.0 / ns.cbrt(2.0)  # phi(zeta = 1); the LSDA energy there is PW92's ferromagnetic fit
+    a_f = 0.5 * (1.0 - ns.log(2.0)) / (ns.pi * ns.pi)
+    etl, eth = [], []  # the maxima, as their LSDA and gradient parts
+    for r, s in ((ru, suu), (rd, sdd)):
+        e1 = _pbe_eps(ns, r, _pw92_g(ns, ns.cbrt(3.0 / (4.0 * ns.pi * r)), a_f, *_PW92_FIT[1]), ferro, s)
+        one = e1[0] + e1[1] >= eps
+        etl.append(ns.where(one, e1[0], el))
+        eth.append(ns.where(one, e1[1], hl))
+    z2_ = zeta * zeta
+    c0 = 0.53 + 0.87 * z2_ + 0.50 * z2_ * z2_ + 2.26 * z2_ * z2_ * z2_
+    xi2 = (zm * zm * suu - 2.0 * zm * zp * sud + zp * zp * sdd) / (rho * rho) / (4.0 * _kf2(ns, rho))
+    cd = 1.0 + 0.5 * xi2 * (1.0 / (zp * cp) + 1.0 / (zm * cm))
+    C = c0 / (cd * cd * cd * cd)
+    z = sig / (8.0 * rho * (tu + td + dc))
+    z = ns.where(z > 1.0, 1.0, z)
+    zz = z * z
+    czz, mzz = C * zz, -((1.0 + C) * zz)
+    p4l, p4h = mzz * (ru * etl[0] + rd * etl[1]) / rho, mzz * (ru * eth[0] + rd * eth[1]) / rho
+    erev = (el + hl) + (el * czz + hl * czz) + (p4l + p4h)
+    return (rho * el, rho * hl, rho * el * czz, rho * hl * czz, rho * p4l, rho * p4h, rho * 2.8 * erev * erev * zz * z)
+
+
+MGGA_NAMES = ["mgga_x_scan", "mgga_c_scan", "mgga_x_tpss", "mgga_c_tpss"]
 FUNCS = {n: globals()[n] for n in NAMES}
+MGGA_FUNCS = {n: globals()[n] for n in MGGA_NAMES}
+ALL_FUNCS = dict(FUNCS, **MGGA_FUNCS)
 IS_GGA = {n: n.startswith("gga_") for n in NAMES}
 
 
@@ -403,10 +587,35 @@ def _work_dps(rhos, sigmas):
     return DPS + 30 + int(extra)  # 30: a second difference with steps of 1e-20 leaves 40 digits of the function behind
 
 
-def effective_point(ru, rd, suu, sud, sdd):
+def _mgga_dps(rhos, sigmas, taus):
+    """digits to carry at a meta-GGA point: first order only, so the decimal exponent of each ratio is added once"""
+    extra = sum(float(mp.log10(max(v) / min(v))) for v in (rhos, sigmas, taus))
+    s2 = min([mp.mpf(1)] + [sg / mp.power(r, mp.mpf(8) / 3) for r, sg in zip(rhos, sigmas)])
+    return DPS + 30 + int(extra + float(-mp.log10(s2)))
+
+
+def _effective_point_mgga(ru, rd, suu, sud, sdd, tu, td):
+    """effective_point with tau: (rho_u, rho_d, sigma_uu, sigma_ud, sigma_dd, tau_u, tau_d) with each 2 tau_s raised to TAU_THRESHOLD (what
+    the spin-scaled exchange sees), and the offsets (dz, dc): the correlation functionals see tau_u + tau_d + dc = max(tau_u + tau_d,
+    TAU_THRESHOLD) of the taus given"""
+    mp.mp.dps = 4 * DPS
+    if not (float(ru) + float(rd) > DENS_THRESHOLD):
+        return None
+    x, dz, _, zero = effective_point(ru, rd, suu, sud, sdd)
+    mp.mp.dps = 4 * DPS
+    tu, td = mp.mpf(float(tu)), mp.mpf(float(td))
+    thr = mp.mpf(TAU_THRESHOLD)
+    eu, ed = max(2 * tu, thr) / 2, max(2 * td, thr) / 2
+    dc = max(mp.mpf(float(tu) + float(td)), thr) - (eu + ed)  # the kernels add in double
+    return x + (eu, ed), (dz, dc), _mgga_dps(x[:2], (x[2], x[4]), (eu, ed)), zero
+
+
+def effective_point(ru, rd, suu, sud, sdd, tu=None, td=None):
     """the point the functional is evaluated at, the offset of zeta, the digits to carry and the variables that stand for a zero: libxc's thresholds (see the module
     docstring), exact zero gradients replaced by a reduced gradient of TINY_S.  Exact arithmetic on the doubles given; None below
-    the density cutoff."""
+    the density cutoff.  With tu, td: the seven variables of a meta-GGA and the offsets (dz, dc) (_effective_point_mgga)."""
+    if tu is not None:
+        return _effective_point_mgga(ru, rd, suu, sud, sdd, tu, td)
     mp.mp.dps = 4 * DPS
     ru, rd, suu, sud, sdd = (mp.mpf(float(v)) for v in (ru, rd, suu, sud, sdd))
     if not (float(ru) + float(rd) > DENS_THRESHOLD):  # the kernels add in double
@@ -424,13 +633,16 @@ def effective_point(ru, rd, suu, sud, sdd):
     return (ru, rd, suu, sud, sdd), dz, _work_dps((ru, rd), (suu, sdd)), (zero + [3] if len(zero) == 2 else zero)
 
 
-def unpolarised(rho, sigma):
-    """the unpolarised form is the polarised form at rho_u = rho_d = rho / 2, sigma_uu = sigma_ud = sigma_dd = sigma / 4"""
-    return 0.5 * rho, 0.5 * rho, 0.25 * sigma, 0.25 * sigma, 0.25 * sigma
+def unpolarised(rho, sigma, tau=None):
+    """the unpolarised form is the polarised form at rho_u = rho_d = rho / 2, sigma_uu = sigma_ud = sigma_dd = sigma / 4
+    (and tau_u = tau_d = tau / 2 for a meta-GGA)"""
+    x = (0.5 * rho, 0.5 * rho, 0.25 * sigma, 0.25 * sigma, 0.25 * sigma)
+    return x if tau is None else x + (0.5 * tau, 0.5 * tau)
 
 
-def effective_point_unpol(rho, sigma):
-    """(rho, sigma) of a closed-shell point with the same conventions; None below the density cutoff"""
+def effective_point_unpol(rho, sigma, tau=None):
+    """(rho, sigma) of a closed-shell point with the same conventions; None below the density cutoff.  With tau: (rho, sigma, tau)
+    with tau raised to TAU_THRESHOLD, and the offsets (dz, dc) = (0, 0) of a meta-GGA"""
     mp.mp.dps = 4 * DPS
     rho, sigma = mp.mpf(float(rho)), mp.mpf(float(sigma))
     if not (float(rho) > DENS_THRESHOLD):
@@ -438,6 +650,9 @@ def effective_point_unpol(rho, sigma):
     zero = [1] if sigma == 0 else []
     if sigma == 0:
         sigma = mp.mpf(TINY_S) ** 2 * 4 * mp.power(rho / 2, mp.mpf(8) / 3)
+    if tau is not None:
+        tau = max(mp.mpf(float(tau)), mp.mpf(TAU_THRESHOLD))
+        return (rho, sigma, tau), (mp.mpf(0), mp.mpf(0)), _mgga_dps((rho / 2,), (sigma / 4,), (tau,)), zero
     return (rho, sigma), mp.mpf(0), _work_dps((rho / 2,), (sigma / 4,)), zero
 
 
@@ -452,9 +667,9 @@ SCALE_FLOOR = 2.2250738585072014e-308 / 2.220446049250313e-16
 
 def _steps(x):
     """the step of each variable: relative to its own size; sigma_ud (which may vanish or be negative) relative to sigma_uu + sigma_dd"""
-    if len(x) == 2:
-        return [abs(x[0]), abs(x[1])]
-    return [abs(x[0]), abs(x[1]), abs(x[2]), abs(x[2]) + abs(x[4]), abs(x[4])]
+    if len(x) in (2, 3):
+        return [abs(v) for v in x]
+    return [abs(x[0]), abs(x[1]), abs(x[2]), abs(x[2]) + abs(x[4]), abs(x[4])] + [abs(v) for v in x[5:]]
 
 
 def _shift(x, k, h):
@@ -468,7 +683,7 @@ def _re(v):
 
 
 def _embed(y):
-    return y if len(y) == 5 else unpolarised(y[0], y[1])
+    return y if len(y) in (5, 7) else unpolarised(*y)
 
 
 def mp_eval(name, x, dz, delta=None, h_rel=H_REL, variables=None, dps=DPS, number=float, zero=()):
@@ -477,7 +692,7 @@ def mp_eval(name, x, dz, delta=None, h_rel=H_REL, variables=None, dps=DPS, numbe
     -> {"e": (truth, scale), "d1": {k: (truth, scale)}, "d2": {k: (truth, scale)}} as floats (number=mp.mpf: as they are); mpmath central
     differences of every part at once"""
     ns = MP(max(dps, DPS + 30))
-    f = FUNCS[name]
+    f = ALL_FUNCS[name]
     variables = range(len(x)) if variables is None else variables
 
     def parts(y):
@@ -489,7 +704,11 @@ def mp_eval(name, x, dz, delta=None, h_rel=H_REL, variables=None, dps=DPS, numbe
     st = _steps(x)
     out = {"e": combine(parts(x)), "d1": {}, "d2": {}}
     # a variable that stands for an exact zero is TINY_S^2 of its natural size, and the truth there is TINY_S from the limit
-    floor = [mp.mpf(TINY_S ** 3 if k in zero else SCALE_FLOOR) * out["e"][1] for k in range(len(x))]
+    # (TINY_S of the derivative's natural size, scale(e) / sigma at a reduced gradient of 1).  Meta-GGA, len(x) = 3 or 7: the other
+    # derivatives at such a point as well, TINY_S of scale(e) / |x_k| -- d/dtau through z = tau_W / tau is of the order sigma^2 / tau^3
+    # there, its limit is 0, and with tau at its threshold the truth at TINY_S is not yet at that limit
+    near_limit = bool(zero) and len(x) in (3, 7)
+    floor = [mp.mpf(TINY_S ** 3 if k in zero else TINY_S if near_limit else SCALE_FLOOR) * out["e"][1] for k in range(len(x))]
 
     def floored(ts, lo):
         return ts[0], max(ts[1], number(lo))
@@ -522,7 +741,7 @@ def td_eval(name, x, dz, delta=None):
     ns = TD()
     xs = [torch.tensor(np.asarray(v, dtype=np.float64), requires_grad=True) for v in x]
     dzt = torch.tensor(np.asarray(dz, dtype=np.float64))
-    parts = FUNCS[name](ns, *_embed(xs), dzt)
+    parts = ALL_FUNCS[name](ns, *_embed(xs), dzt)
     e = sum(parts[1:], parts[0])
     g = torch.autograd.grad(e.sum(), xs, create_graph=True, allow_unused=True)
     g = [torch.zeros_like(xs[0]) if a is None else a for a in g]
@@ -543,10 +762,16 @@ UNPOL_OUTPUTS = ("e", "vrho", "vgrad", "dvrho", "dvgrad", "t_dvrho", "t_dvgrad")
 POL_OUTPUTS = ("e", "vrho_u", "vrho_d", "vgrad_u", "vgrad_d", "dvrho_u", "dvrho_d", "dvgrad_u", "dvgrad_d")
 
 
+MGGA_UNPOL_OUTPUTS = ("e", "vrho", "vgrad", "vtau")
+MGGA_POL_OUTPUTS = ("e", "vrho_u", "vrho_d", "vgrad_u", "vgrad_d", "vtau_u", "vtau_d")
+
+
 def unpol_excluded(name, p):
     """{output: bool mask over the points} of what a comparison leaves out (p: rho, grho): the d v_grad of gga_x_g96 where grad rho
-    is exactly zero -- its v_sigma ~ sigma^(-1/4) does not exist there (v_grad itself is compared, and is 0)"""
+    is exactly zero -- its v_sigma ~ sigma^(-1/4) does not exist there (v_grad itself is compared, and is 0).  Meta-GGA: nothing"""
     import numpy as np
+    if name in MGGA_FUNCS:
+        return {o: np.zeros(p["rho"].shape[0], dtype=bool) for o in MGGA_UNPOL_OUTPUTS}
     zero_g = (np.abs(p["grho"]).sum(0) == 0.0) & (p["rho"] > DENS_THRESHOLD)
     m = {o: np.zeros(p["rho"].shape[0], dtype=bool) for o in UNPOL_OUTPUTS}
     if name == "gga_x_g96":
@@ -560,6 +785,11 @@ def pol_excluded(name, p):
     import numpy as np
     live = p["rho_u"] + p["rho_d"] > DENS_THRESHOLD
     full = (p["rho_d"] == 0.0) & live
+    if name in MGGA_FUNCS:  # the empty spin only; the v_tau of a correlation functional is one number for both spins and is compared
+        m = {o: np.zeros(p["rho_u"].shape[0], dtype=bool) for o in MGGA_POL_OUTPUTS}
+        for o in ("vrho_d", "vgrad_d") + (("vtau_d",) if name.startswith("mgga_x_") else ()):
+            m[o] = full.copy()
+        return m
     m = {o: np.zeros(p["rho_u"].shape[0], dtype=bool) for o in POL_OUTPUTS}
     for o in ("vrho_d", "vgrad_d", "dvrho_d", "dvgrad_d"):
         m[o] = full.copy()
@@ -578,6 +808,8 @@ def compose_unpol(r, grho, dgrho, absolute=False):
     """rows (10, n): e; e_rho, e_sigma; (H d)_rho, (H d)_sigma; the spin-flip (H d)_rho_u, _sigma_uu, _sigma_ud and e_sigma_uu, e_sigma_ud of
     the polarised form at rho_u = rho_d (grad rho_u = grad rho_d = g / 2, grad d rho_u = -grad d rho_d = dg / 2)"""
     import numpy as np
+    if len(r) == 4:  # meta-GGA, first order: e; e_rho, e_sigma, e_tau
+        return {"e": r[0], "vrho": r[1], "vgrad": 2.0 * r[2] * (np.abs(grho) if absolute else grho), "vtau": r[3]}
     g, dg, sgn = (np.abs(grho), np.abs(dgrho), 1.0) if absolute else (grho, dgrho, -1.0)
     return {"e": r[0], "vrho": r[1], "vgrad": 2.0 * r[2] * g, "dvrho": r[3], "dvgrad": 2.0 * r[4] * g + 2.0 * r[2] * dg, "t_dvrho": r[5],
             "t_dvgrad": r[6] * g + r[8] * dg + 0.5 * r[7] * g + sgn * 0.5 * r[9] * dg}
@@ -586,6 +818,11 @@ def compose_unpol(r, grho, dgrho, absolute=False):
 def compose_pol(r, gu, gd, dgu, dgd, absolute=False):
     """rows (11, n): e; the gradient by (rho_u, rho_d, sigma_uu, sigma_ud, sigma_dd); the Hessian times the response"""
     import numpy as np
+    if len(r) == 8:  # meta-GGA, first order: e; the gradient by (rho_u, rho_d, sigma_uu, sigma_ud, sigma_dd, tau_u, tau_d)
+        if absolute:
+            gu, gd = np.abs(gu), np.abs(gd)
+        return {"e": r[0], "vrho_u": r[1], "vrho_d": r[2], "vgrad_u": 2.0 * r[3] * gu + r[4] * gd, "vgrad_d": 2.0 * r[5] * gd + r[4] * gu,
+                "vtau_u": r[6], "vtau_d": r[7]}
     if absolute:
         gu, gd, dgu, dgd = np.abs(gu), np.abs(gd), np.abs(dgu), np.abs(dgd)
     return {"e": r[0], "vrho_u": r[1], "vrho_d": r[2], "vgrad_u": 2.0 * r[3] * gu + r[4] * gd, "vgrad_d": 2.0 * r[5] * gd + r[4] * gu,
