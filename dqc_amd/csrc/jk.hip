@@ -352,31 +352,64 @@ __global__ void jk_multi_finish_kernel(double *__restrict__ J, int nj, double *_
 // same-address contention of concurrently running neighbouring blocks (grid-stride order made them all hit J[I,J] at once)
 // disappear; D[I,J] is reloaded only when IJ changes.  The column sums J[K,L] += g . D[I,J] change target every tile and
 // take 2 shuffles + a 4-wave LDS combine per tile.
+//
+// The range is WALKED (docs/LOG_r28.md): block indices (I, J, K, L), the tile's address and its stored row count are block-uniform
+// state carried from tile to tile -- inside a bra pair the next tile starts R(IJ) * C(KL) doubles on, (K, L) steps to (K, L + 1)
+// or (K + 1, 0) -- and the closed forms (decode_tri, tile_base) are evaluated for a range's first tile and for a new bra pair
+// only, not in front of every tile's loads.  A thread's patch is 4 rows x the columns {2l, 2l + 1, 32 + 2l, 33 + 2l}, l = t & 15
+// (this kernel only; the others keep 4 consecutive columns): one 16-byte load instruction of a 16-lane group covers 256
+// contiguous bytes of a row, two whole 128-byte lines, where the consecutive-column patch took half of each of four lines
+// twice.  With whole lines per instruction the once-read tiles can go past the caches (ONCE: non-temporal loads of the plain
+// tiles, chosen by the host for a store that cannot stay in the Infinity Cache from one call to the next): 323.6 -> 296.3 us
+// for the 1.895 GB store of the 20-atom molecule, 5.86 -> 6.40 TB/s; on the consecutive-column patch the same policy had
+// cost 9 % (docs/LOG_r18.md).  Tiles with a diagonal ket pair (K == L, 36 stored columns) are gathered into the same patch
+// of the 64-column view through their packed indices, the a < b elements from their a > b twins.
 // ---------------------------------------------------------------------------------------------
+template <bool ONCE>
+DQC_DEV double2 j_tile_load16(const double *p) {  // p 16-byte aligned
+    if constexpr (ONCE) {
+        typedef double v2d_ __attribute__((ext_vector_type(2)));
+        const v2d_ v = __builtin_nontemporal_load(reinterpret_cast<const v2d_ *>(p));
+        return make_double2(v.x, v.y);
+    } else {
+        return *reinterpret_cast<const double2 *>(p);
+    }
+}
+
+template <bool ONCE>
 __global__ __launch_bounds__(256, 1) void j_stream_kernel(const double *__restrict__ dscp, const double *__restrict__ tiles,
                                                          double *__restrict__ work, int npad, long long ntiles, long long per_block,
                                                          long long tbeg, int nao) {
     const TileLay ly(nao);
     // (tiles [tbeg, ntiles): the whole store, or one rank's slice of it -- dqc_jk_from_tiles_part)
     const double dsc = dscp ? *dscp : 0.0;
-    __shared__ double s_col[2][4][64];
+    __shared__ __attribute__((aligned(16))) double s_col[2][4][64];
     const size_t n2 = (size_t)npad * npad;
     const double *Dp = work;
     double *Jacc = work + n2;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r0 = 4 * (t >> 4), c0 = 4 * (t & 15);
-    const int kk = c0 >> 3, l0 = c0 & 7, ii = r0 >> 3, j0 = r0 & 7;
+    const int r0 = 4 * (t >> 4), ii = r0 >> 3, j0 = r0 & 7;
+    const int cA = 2 * (t & 15), cB = 32 + cA;  // view columns cA, cA + 1, cB, cB + 1
     const long long T0 = tbeg + (long long)blockIdx.x * per_block, T1 = min(T0 + per_block, ntiles);
     if (T0 >= T1) return;
     int IJ, KL, I, J, K, L;
     decode_tri(T0, IJ, KL);
     decode_tri(IJ, I, J);
+    decode_tri(KL, K, L);
+    const double *tp = tiles + tile_base(I, J, K, KL, ly);  // first double of tile (IJ, KL)
+    int R = 0;         // stored rows of the tiles of bra pair IJ (tile_rows: 64, 36, or the truncated last block row's)
+    unsigned prow[4];  // stored row of view row r0 + x: exists if prow[x] < R (a diagonal pair's packed index grows with its larger AO)
     double rsacc[4] = {0, 0, 0, 0}, dij[4];
-    {
+    auto enter_pair = [&]() {
+        R = tile_rows(I, J, ly);
         const double *dijp = Dp + (size_t)(I * 8 + ii) * npad + J * 8 + j0;
 #pragma unroll
-        for (int q = 0; q < 4; q++) dij[q] = dijp[q];
-    }
+        for (int q = 0; q < 4; q++) {
+            dij[q] = dijp[q];
+            prow[q] = I == J ? tile_pidx(true, ii, j0 + q) : r0 + q;
+        }
+    };
+    enter_pair();
     auto flush_rows = [&]() {
         const double fI = (I == J ? 0.5 : 1.0);
 #pragma unroll
@@ -388,33 +421,43 @@ __global__ __launch_bounds__(256, 1) void j_stream_kernel(const double *__restri
         }
     };
     int par = 0;
-    for (long long T = T0; T < T1; T++, KL++) {
-        if (KL > IJ) {  // next bra block pair
-            flush_rows();
-            IJ++;
-            KL = 0;
-            decode_tri(IJ, I, J);
-            const double *dijp = Dp + (size_t)(I * 8 + ii) * npad + J * 8 + j0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) dij[q] = dijp[q];
-        }
-        decode_tri(KL, K, L);
+    for (long long T = T0;;) {
+        const bool dc = K == L;
+        const unsigned C = tile_dim(dc);
         // factors of the unique-tile weights: (I == J) is applied at the flush, (K == L) and (IJ == KL) here
-        const double fk = (K == L ? 0.5 : 1.0) * (IJ == KL ? 0.5 : 1.0);
-        const double *dklp = Dp + (size_t)(K * 8 + kk) * npad + L * 8 + l0;
-        double dkl[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) dkl[q] = fk * dklp[q];
+        const double fk = (dc ? 0.5 : 1.0) * (IJ == KL ? 0.5 : 1.0);
+        const double *pa = Dp + (size_t)(K * 8 + (cA >> 3)) * npad + L * 8 + (cA & 7);
+        const double *pb = Dp + (size_t)(K * 8 + (cB >> 3)) * npad + L * 8 + (cB & 7);
+        const double dkl[4] = {fk * pa[0], fk * pa[1], fk * pb[0], fk * pb[1]};
+        const double2 z2 = make_double2(0.0, 0.0);
+        double2 ta0 = z2, tb0 = z2, ta1 = z2, tb1 = z2, ta2 = z2, tb2 = z2, ta3 = z2, tb3 = z2;
+        // rows of the view past the stored prefix of the last block row do not exist in the store: they read as zeros
+        const bool ok0 = prow[0] < (unsigned)R, ok1 = prow[1] < (unsigned)R, ok2 = prow[2] < (unsigned)R, ok3 = prow[3] < (unsigned)R;
+        const double *q0 = tp + prow[0] * C, *q1 = tp + prow[1] * C, *q2 = tp + prow[2] * C, *q3 = tp + prow[3] * C;
+        if (!dc && R == tile_dim(I == J)) {  // all rows stored, 64 columns: the bulk of the store
+            ta0 = j_tile_load16<ONCE>(q0 + cA); tb0 = j_tile_load16<ONCE>(q0 + cB);
+            ta1 = j_tile_load16<ONCE>(q1 + cA); tb1 = j_tile_load16<ONCE>(q1 + cB);
+            ta2 = j_tile_load16<ONCE>(q2 + cA); tb2 = j_tile_load16<ONCE>(q2 + cB);
+            ta3 = j_tile_load16<ONCE>(q3 + cA); tb3 = j_tile_load16<ONCE>(q3 + cB);
+        } else if (!dc) {
+            if (ok0) { ta0 = *reinterpret_cast<const double2 *>(q0 + cA); tb0 = *reinterpret_cast<const double2 *>(q0 + cB); }
+            if (ok1) { ta1 = *reinterpret_cast<const double2 *>(q1 + cA); tb1 = *reinterpret_cast<const double2 *>(q1 + cB); }
+            if (ok2) { ta2 = *reinterpret_cast<const double2 *>(q2 + cA); tb2 = *reinterpret_cast<const double2 *>(q2 + cB); }
+            if (ok3) { ta3 = *reinterpret_cast<const double2 *>(q3 + cA); tb3 = *reinterpret_cast<const double2 *>(q3 + cB); }
+        } else {  // 36 packed columns: every element through its packed index (a line is fetched through both twins: default policy)
+            const int pc0 = tile_pidx(true, cA >> 3, cA & 7), pc1 = tile_pidx(true, cA >> 3, (cA & 7) + 1);
+            const int pc2 = tile_pidx(true, cB >> 3, cB & 7), pc3 = tile_pidx(true, cB >> 3, (cB & 7) + 1);
+            if (ok0) { ta0 = make_double2(q0[pc0], q0[pc1]); tb0 = make_double2(q0[pc2], q0[pc3]); }
+            if (ok1) { ta1 = make_double2(q1[pc0], q1[pc1]); tb1 = make_double2(q1[pc2], q1[pc3]); }
+            if (ok2) { ta2 = make_double2(q2[pc0], q2[pc1]); tb2 = make_double2(q2[pc2], q2[pc3]); }
+            if (ok3) { ta3 = make_double2(q3[pc0], q3[pc1]); tb3 = make_double2(q3[pc2], q3[pc3]); }
+        }
         double cs[4] = {0, 0, 0, 0};
-        {
-            double2 ta0, tb0, ta1, tb1, ta2, tb2, ta3, tb3;
-            tile_load_patch(tiles, IJ, KL, I, J, K, L, r0, c0, ta0, tb0, ta1, tb1, ta2, tb2, ta3, tb3, ly);
 #define DQC_JS_ROW(R_, A_, B_)                                                                           \
     rsacc[R_] += A_.x * dkl[0] + A_.y * dkl[1] + B_.x * dkl[2] + B_.y * dkl[3];                          \
     cs[0] += A_.x * dij[R_]; cs[1] += A_.y * dij[R_]; cs[2] += B_.x * dij[R_]; cs[3] += B_.y * dij[R_];
-            DQC_JS_ROW(0, ta0, tb0) DQC_JS_ROW(1, ta1, tb1) DQC_JS_ROW(2, ta2, tb2) DQC_JS_ROW(3, ta3, tb3)
+        DQC_JS_ROW(0, ta0, tb0) DQC_JS_ROW(1, ta1, tb1) DQC_JS_ROW(2, ta2, tb2) DQC_JS_ROW(3, ta3, tb3)
 #undef DQC_JS_ROW
-        }
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             double v = cs[c];
@@ -422,15 +465,29 @@ __global__ __launch_bounds__(256, 1) void j_stream_kernel(const double *__restri
             cs[c] = v;
         }
         if (lane < 16) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) s_col[par][wave][c0 + c] = cs[c];
+            *reinterpret_cast<double2 *>(&s_col[par][wave][cA]) = make_double2(cs[0], cs[1]);
+            *reinterpret_cast<double2 *>(&s_col[par][wave][cB]) = make_double2(cs[2], cs[3]);
         }
         __syncthreads();  // one barrier per tile: s_col is double-buffered
         if (t < 64) {
             const double v = s_col[par][0][t] + s_col[par][1][t] + s_col[par][2][t] + s_col[par][3][t];
             acc_add(&Jacc[(size_t)(K * 8 + (t >> 3)) * npad + L * 8 + (t & 7)], 2.0 * (I == J ? 0.5 : 1.0) * fk * v, dsc);
         }
+        // ---- next tile of the range
+        if (++T >= T1) break;
         par ^= 1;
+        if (KL == IJ) {  // next bra block pair
+            flush_rows();
+            IJ++;
+            KL = 0; K = 0; L = 0;
+            if (++J > I) { I++; J = 0; }
+            tp = tiles + tile_base(I, J, 0, 0, ly);
+            enter_pair();
+        } else {
+            tp += (unsigned)R * C;
+            KL++;
+            if (++L > K) { K++; L = 0; }
+        }
     }
     flush_rows();
 }
@@ -807,6 +864,10 @@ int dqc_jk_stream_prepared(const double *d_tiles, int nao, double *d_work, int w
     return jk_from_tiles_impl(nullptr, nullptr, d_tiles, nullptr, nao, d_work, 0, (long long)dqc_eri_tile_count(nao), with_k ? 1 : 0, stream);
 }
 
+// j_stream_kernel<ONCE>: the Infinity Cache's 256 MiB.  A smaller store is served from it call after call (benzene / cc-pVDZ,
+// 0.17 GB) and keeps the default policy
+constexpr long long J_ONCE_MIN_BYTES = 256LL << 20;
+
 static int jk_from_tiles_impl(double *d_J, double *d_K, const double *d_tiles_part, const double *d_dm, int nao, double *d_work,
                               long long tile_begin, long long tile_end, int with_k_prepared, void *stream) {
     using namespace dqc;
@@ -855,7 +916,9 @@ static int jk_from_tiles_impl(double *d_J, double *d_K, const double *d_tiles_pa
         // of 2 tiles (benzene with 4096 blocks) lose it again to the per-range prologue and flush: 0.043 ms.
         const long long nblk = std::max<long long>(1, std::min<long long>((nrun + 3) / 4, j_nblk_env > 0 ? j_nblk_env : 65536));
         const long long per = (nrun + nblk - 1) / nblk;
-        hipLaunchKernelGGL(j_stream_kernel, dim3((unsigned)((nrun + per - 1) / per)), dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, per, tbeg, nao);
+        // tiles that cannot stay in the Infinity Cache until the next call reads them again are streamed past the caches
+        const bool once = 8 * (dqc_eri_tile_offset(nao, tile_end) - dqc_eri_tile_offset(nao, tile_begin)) > J_ONCE_MIN_BYTES;
+        hipLaunchKernelGGL(once ? j_stream_kernel<true> : j_stream_kernel<false>, dim3((unsigned)((nrun + per - 1) / per)), dim3(256), 0, st, dscp, d_tiles, d_work, npad, ntiles, per, tbeg, nao);
     }
     DQC_CHECK_LAUNCH();
     if (d_J) {

@@ -155,9 +155,11 @@ class HamiltonMI355(_Base):
         self.xcfamily = 1
         self._fuse_k = False
         # remembered per density matrix (clear_memos): the J / K pair and the unrestricted pair of the last exchange calls, the
-        # two-electron energies of the last build, and the orbital factors of the last two ao_orb2dm results (the spin-up and
-        # spin-down matrices of an unrestricted iteration); per weight tensor: the last two occupation checks
-        self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors = _Memo(), _Memo(), _Memo(), _Memo(2)
+        # two-electron energies of the last two builds (two calculations on one system share this object: each finds the energies of
+        # the build IT made, not a second evaluation by another route that agrees with the build to round-off only), and the orbital
+        # factors of the last two ao_orb2dm results (the spin-up and spin-down matrices of an unrestricted iteration); per weight
+        # tensor: the last two occupation checks
+        self._jk_memo, self._jkpol_memo, self._energy_memo, self._factors = _Memo(), _Memo(), _Memo(2), _Memo(2)
         self._dfk_memo = _Memo(2)  # fitted exchange: K[D] of the last two matrices (the spin pair of an unrestricted iteration)
         self._w_checked = _Memo(2)
         # which density kernel the grid passes took: "factor" (rank-n_occ kernel, D = ao_orb2dm(...) recognised), "dense" (anonymous
@@ -306,6 +308,7 @@ class HamiltonMI355(_Base):
                 self._jk_memo.clear()
             self.xc = xc  # same grid, same derivative level: the AO values are already resident
             return
+        self._energy_memo.clear()  # another grid or derivative level: E_xc of an earlier build is not this quadrature's
         self.xc = xc
         self.xcfamily = family
         self.grid = grid
