@@ -11,7 +11,7 @@ from .grid import get_grid, get_predefined_grid  # noqa: F401
 from .properties import edipole, equadrupole, optimal_geometry, hessian_pos, vibration, ir_spectrum, raman_spectrum  # noqa: F401
 from .properties import lowest_eival_orb_hessian, is_orb_min, polarizability, excitations, Excitations  # noqa: F401
 from .response import OrbitalHessian  # noqa: F401
-from .mp2 import mp2, MP2, mp2_density, MP2Density  # noqa: F401
+from .mp2 import mp2, MP2, mp2_density, MP2Density, mp2_gradient, MP2Gradient  # noqa: F401
 from .rpa import rpa, RPA  # noqa: F401
 from .gw import gw, GW  # noqa: F401
 from .bse import bse, BSE  # noqa: F401

@@ -190,7 +190,11 @@ struct OidxTab {
 //                   matrix-vector passes over the block, see the kernel), so this mode keeps the fill's LDS footprint -- the
 //                   six accumulator blocks of ERI_OUT_JK (294 doubles per quartet for (ff|ff)) halve the occupancy of the
 //                   high-angular-momentum classes
-enum { ERI_OUT_TILES = 0, ERI_OUT_3C = 1, ERI_OUT_2C = 2, ERI_OUT_GRAD = 3, ERI_OUT_JK = 4, ERI_OUT_SCHWARZ = 5, ERI_OUT_J = 6 };
+//   ERI_OUT_GRAD3 : ERI_OUT_GRAD with the general density-fitting contractions (gmode 3 and 4 of EriOut) in place of the products
+//                   of matrices: instantiated for the (LC, 0) density-fitting classes alone (dqc_df_grad3), so that the epilogue
+//                   the four-index classes compile stays as short as it was
+enum { ERI_OUT_TILES = 0, ERI_OUT_3C = 1, ERI_OUT_2C = 2, ERI_OUT_GRAD = 3, ERI_OUT_JK = 4, ERI_OUT_SCHWARZ = 5, ERI_OUT_J = 6, ERI_OUT_GRAD3 = 7 };
+__host__ __device__ constexpr bool eri_grad_mode(int mode) { return mode == ERI_OUT_GRAD || mode == ERI_OUT_GRAD3; }
 
 // lane-group size of a compile-time class by its Cartesian block size (EriCfg::TPQ; the host's screened task maps need it too)
 __host__ __device__ constexpr int eri_tpq(int nout) { return nout <= 9 ? 1 : (nout <= 81 ? 4 : (nout <= 324 ? 16 : (nout <= 1296 ? 64 : 256))); }
@@ -234,6 +238,10 @@ struct EriOut {
     double kscale = 0.0;            // weight of the exchange-type products (1: HF, 0: pure J)
     // density-fitting gradient (gmode 1: (d_A a b|k) D_ab c_k -> +2 to a's atom, -2 to k's atom;
     //                           gmode 2: (d_A k|l) c_k c_l    -> -1 to k's atom); ccart: fit coefficients, Cartesian
+    // ERI_OUT_GRAD3 (dqc_df_grad3), general densities over the Cartesian functions of the two shell ranges, addressed through the 3C
+    // fields above (nao / naux: Cartesian functions of the orbital / auxiliary range, ao0 / aux0: Cartesian offset of its first shell):
+    //                           gmode 3: (d_A a b|k) Z[a, b, k] -> +2 to a's atom, -2 to k's atom; dcart = Z (nao, nao, naux), k fastest
+    //                           gmode 4: (d_A k|l) G[k, l]      -> -1 to k's atom;                 ccart = G (naux, naux)
     int gmode = 0;
     const double *ccart = nullptr;
     // ---- JK mode: symmetric AO density (nao, nao), accumulators A (J = (A + A^T) / 2) and B (K = B + B^T; NULL: J only)
@@ -398,11 +406,11 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
 
     const int tid = threadIdx.x;
     const int q = tid / TPQ, s = tid % TPQ;  // quartet slot in the block, lane inside the quartet group
-    constexpr int REGION = MODE == ERI_OUT_GRAD ? Cfg::REGION_G : Cfg::REGION;  // (the direct modes digest the block in place: the fill's footprint)
+    constexpr int REGION = eri_grad_mode(MODE) ? Cfg::REGION_G : Cfg::REGION;  // (the direct modes digest the block in place: the fill's footprint)
     double *reg = lds + (size_t)q * REGION;
     constexpr bool TAB_LDS = Cfg::TAB_DOUBLES > 0;
     typedef __attribute__((address_space(3))) double lds_double_t;
-    lds_double_t *ltab = (lds_double_t *)lds + (MODE == ERI_OUT_GRAD ? Cfg::REG_DOUBLES_G : Cfg::REG_DOUBLES);
+    lds_double_t *ltab = (lds_double_t *)lds + (eri_grad_mode(MODE) ? Cfg::REG_DOUBLES_G : Cfg::REG_DOUBLES);
     if constexpr (TAB_LDS) {
         if constexpr (Cfg::BOYS01) boys_stage_lds(ltab, tid, 256);
         else rys_stage_lds<NR>(ltab, tid, 256);
@@ -777,7 +785,7 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                     if (o < psl) acc[e][m] += t_;
                 }
     }
-    if constexpr (MODE == ERI_OUT_GRAD) {
+    if constexpr (eri_grad_mode(MODE)) {
         // ---------------- gradient contraction straight from the Cartesian accumulators ----------------
         const int a = ish % og.norig;             // original shell behind the up / down companion
         const int la = LA - og.dirn;
@@ -813,6 +821,13 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                     const double coef = og.dirn >= 0 ? 1.0 : -(double)o[dir];
                     const size_t ia = ca0 + cart_index(la, o[0], o[2]);
                     double f;
+                    if constexpr (MODE == ERI_OUT_GRAD3) {
+                        // (consecutive lanes run over the ket components: neighbouring addresses of Z, whose auxiliary index is fastest)
+                        if (og.gmode == 3)
+                            f = 2.0 * D[((ia - og.ao0) * og.nao + (ib - og.ao0)) * og.naux + (ic - og.aux0)];
+                        else
+                            f = -og.ccart[(ia - og.aux0) * og.naux + (ic - og.aux0)];
+                    } else
                     if (og.gmode == 0) {
                         f = jfac * D[ia * nc + ib] * dcd;
                         if (with_k) f -= og.kscale * (D[ia * nc + ic] * dbd + (same_cd ? 0.0 : D[ia * nc + id] * dbc));
@@ -832,12 +847,13 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
 #pragma unroll
             for (int o = WRED / 2; o > 0; o >>= 1) g[dir] += __shfl_xor(g[dir], o);
         double *gp = og.gpart + ((size_t)(blockIdx.x % og.nslot) * og.natm + og.sh_atom[a]) * 3;
-        double *gk = og.gpart + ((size_t)(blockIdx.x % og.nslot) * og.natm + og.sh_atom[ksh]) * 3;  // gmode 1 only
+        double *gk = og.gpart + ((size_t)(blockIdx.x % og.nslot) * og.natm + og.sh_atom[ksh]) * 3;  // gmode 1 and 3 only: the auxiliary centre
+        constexpr int GK = MODE == ERI_OUT_GRAD3 ? 3 : 1;  // the three-index mode, whose auxiliary centre takes minus the sum
         if (TPQ <= 64) {
             if (s == 0 && active)
                 for (int dir = 0; dir < 3; dir++) {
                     atomicAdd(&gp[dir], g[dir]);
-                    if (og.gmode == 1) atomicAdd(&gk[dir], -g[dir]);
+                    if (og.gmode == GK) atomicAdd(&gk[dir], -g[dir]);
                 }
         } else {  // the whole block is one quartet: combine the four waves through LDS
             __syncthreads();
@@ -848,7 +864,7 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                 for (int dir = 0; dir < 3; dir++) {
                     const double v = lds[dir] + lds[3 + dir] + lds[6 + dir] + lds[9 + dir];
                     atomicAdd(&gp[dir], v);
-                    if (og.gmode == 1) atomicAdd(&gk[dir], -v);
+                    if (og.gmode == GK) atomicAdd(&gk[dir], -v);
                 }
         }
         return;

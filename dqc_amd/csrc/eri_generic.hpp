@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
     const int sa = 2 * la + 1, sb = 2 * lb + 1, sc = 2 * lc + 1, sd = 2 * ld + 1;
     const int nsph = sa * sb * sc * sd;
     double *sphl = reg + hc.off_s;
-    if constexpr (MODE != ERI_OUT_GRAD)
+    if constexpr (!eri_grad_mode(MODE))
         for (int e = s; e < nsph; e += TPQ) sphl[e] = 0.0;
     double gsum[3] = {0.0, 0.0, 0.0};  // GRAD mode
 
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
             eri_group_sync<TPQ>();
         }
 
-        if constexpr (MODE == ERI_OUT_GRAD) {
+        if constexpr (eri_grad_mode(MODE)) {
             // ---------------- gradient contraction of the slice (see eri_core.hpp) ----------------
             const int a = ish % og.norig;
             const int lorig = la - og.dirn;
@@ -312,6 +312,12 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
                         const double coef = og.dirn >= 0 ? 1.0 : -(double)o[dir];
                         const size_t ia = ca0 + cart_index(lorig, o[0], o[2]);
                         double f;
+                        if constexpr (MODE == ERI_OUT_GRAD3) {
+                            if (og.gmode == 3)
+                                f = 2.0 * D[((ia - og.ao0) * og.nao + (ibb - og.ao0)) * og.naux + (ic - og.aux0)];
+                            else
+                                f = -og.ccart[(ia - og.aux0) * og.naux + (ic - og.aux0)];
+                        } else
                         if (og.gmode == 0)
                             f = jfac * D[ia * nc + ibb] * dcd -
                                 og.kscale * (D[ia * nc + ic] * dbd + (same_cd ? 0.0 : D[ia * nc + id] * dbc));
@@ -381,7 +387,7 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
         }
     }
 
-    if constexpr (MODE == ERI_OUT_GRAD) {
+    if constexpr (eri_grad_mode(MODE)) {
         constexpr int WRED = TPQ < 64 ? TPQ : 64;
 #pragma unroll
         for (int dir = 0; dir < 3; dir++)
@@ -389,12 +395,13 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
             for (int o = WRED / 2; o > 0; o >>= 1) gsum[dir] += __shfl_xor(gsum[dir], o);
         const int a = ish % og.norig;
         double *gp = og.gpart + ((size_t)(blockIdx.x % og.nslot) * og.natm + og.sh_atom[a]) * 3;
-        double *gk = og.gpart + ((size_t)(blockIdx.x % og.nslot) * og.natm + og.sh_atom[ksh]) * 3;  // gmode 1 only
+        double *gk = og.gpart + ((size_t)(blockIdx.x % og.nslot) * og.natm + og.sh_atom[ksh]) * 3;  // gmode 1 and 3 only: the auxiliary centre
+        constexpr int GK = MODE == ERI_OUT_GRAD3 ? 3 : 1;  // (eri_core.hpp)
         if (TPQ <= 64) {
             if (s == 0 && active)
                 for (int dir = 0; dir < 3; dir++) {
                     atomicAdd(&gp[dir], gsum[dir]);
-                    if (og.gmode == 1) atomicAdd(&gk[dir], -gsum[dir]);
+                    if (og.gmode == GK) atomicAdd(&gk[dir], -gsum[dir]);
                 }
         } else {
             __syncthreads();
@@ -405,7 +412,7 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
                 for (int dir = 0; dir < 3; dir++) {
                     const double v = lds[dir] + lds[3 + dir] + lds[6 + dir] + lds[9 + dir];
                     atomicAdd(&gp[dir], v);
-                    if (og.gmode == 1) atomicAdd(&gk[dir], -v);
+                    if (og.gmode == GK) atomicAdd(&gk[dir], -v);
                 }
         }
         return;
@@ -486,7 +493,7 @@ inline bool hl_plan(int mode, int la, int lb, int lc, int ld, HlPlan &p) {
     const int nmax = la + lb, mmax = lc + ld, M1 = mmax + 1, nitem = 3 * nr;
     const int nca = ncart(la), ncb = ncart(lb), ncc = ncart(lc), ncd = ncart(ld);
     const int sa = 2 * la + 1, sb = 2 * lb + 1, sc = 2 * lc + 1, sd = 2 * ld + 1;
-    const bool sphm = mode != ERI_OUT_GRAD;
+    const bool sphm = !eri_grad_mode(mode);
     const int nsph = sphm ? sa * sb * sc * sd : 0;
     const int njk = mode == ERI_OUT_JK ? sa * sb + sc * sd + sa * sc + sa * sd + sb * sc + sb * sd : 0;
     for (int full = 1; full >= 0; full--) {
@@ -509,7 +516,7 @@ inline bool hl_plan(int mode, int la, int lb, int lc, int ld, HlPlan &p) {
             if (nouts > HL_NPT * tpq) continue;
             const size_t bytes = sizeof(double) * ((size_t)hc.region * (256 / tpq) + hc.tab_doubles);
             if (bytes > (size_t)HL_LDS_LIMIT) continue;
-            if (mode == ERI_OUT_GRAD && tpq == 256 && hc.region < 16) hc.region = 17;
+            if (eri_grad_mode(mode) && tpq == 256 && hc.region < 16) hc.region = 17;
             p.hc = hc;
             p.tpq = tpq;
             p.lds_bytes = sizeof(double) * ((size_t)hc.region * (256 / tpq) + hc.tab_doubles);

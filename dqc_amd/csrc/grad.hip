@@ -17,8 +17,9 @@
 // The same two contractions by the BASIS parameters of every primitive p (exponent alpha_p, stored coefficient c_p) instead of the
 // centres: dqc_eri_grad_basis / dqc_int1e_grad_basis, with d a / d c_p = g_p and d a / d alpha_p = -c_p r_A^2 g_p (an l + 2 shell) as
 // per-primitive uncontracted companions.  Orbital shells up to f there (f + 2 = h).
-// Host side: dqc_eri_grad, dqc_eri_grad_basis and dqc_df_grad (the same passes over (orbital pair | auxiliary) and (auxiliary |
-// auxiliary) for the density-fitted Coulomb energy) only parse, build their companions and ordered bra pair lists, name their
+// Host side: dqc_eri_grad, dqc_eri_grad_basis, dqc_df_grad (the same passes over (orbital pair | auxiliary) and (auxiliary |
+// auxiliary) for the density-fitted Coulomb energy) and dqc_df_grad3 (those passes against a general three-index density Z[a, b, k]
+// and a general G[k, l] -- the ERI_OUT_GRAD3 instantiations; the non-separable part of the RI-MP2 gradient) only parse, build their companions and ordered bra pair lists, name their
 // passes (bra list, dirn, gmode, launcher) in a GradJob and say how summed rows become output entries; run_grad_job owns the
 // rest -- uploads, the 64 slots of partial sums, the side-stream fork and join, the launches and the host fold.  The two
 // one-electron entry points share int1e_grad_setup in the same way.
@@ -102,7 +103,8 @@ struct GradCtx {
     int wmap_depth = 1 << 30;  // class pairs whose deepest contraction has at least this many primitive quartets take the wave map
 };
 
-template <int LA, int LB, int LC, int LD>
+// MODE: ERI_OUT_GRAD, or ERI_OUT_GRAD3 for the passes of dqc_df_grad3 (gmode 3 and 4)
+template <int LA, int LB, int LC, int LD, int MODE = ERI_OUT_GRAD>
 static int launch_grad_class(const GradCtx &c, hipStream_t st) {
     using Cfg = EriCfg<LA, LB, LC, LD>;
     const int cb = LA * 8 + LB, ck = LC * (LC + 1) / 2 + LD;
@@ -110,7 +112,7 @@ static int launch_grad_class(const GradCtx &c, hipStream_t st) {
     if (nb == 0 || nk == 0 || hl_forced()) return 0;
     const long long ntask = (long long)nb * nk;
     const long long nblk = eri_num_blocks<Cfg>(nb, nk, ntask);
-    auto kern = eri_kernel<LA, LB, LC, LD, ERI_OUT_GRAD>;
+    auto kern = eri_kernel<LA, LB, LC, LD, MODE>;
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES_G);
     if (c.side != nullptr) st = c.side->take();
     // (only where the class pair's deepest contraction -- first pair of each class: the lists are sorted by depth -- is worth splitting)
@@ -149,39 +151,43 @@ static int launch_grad_bra(const GradCtx &c, hipStream_t st) {
 }
 
 // density-fitting gradients: ket pairs are (auxiliary shell, unit), classes (LC, 0), LC up to f
-template <int LA, int LB>
+template <int LA, int LB, int MODE>
 static int launch_grad_bra_df(const GradCtx &c, hipStream_t st) {
     int rc;
 #define DQC_GK(LC) \
-    if ((rc = launch_grad_class<LA, LB, LC, 0>(c, st))) return rc;
+    if ((rc = launch_grad_class<LA, LB, LC, 0, MODE>(c, st))) return rc;
     DQC_GK(0) DQC_GK(1) DQC_GK(2) DQC_GK(3)
 #undef DQC_GK
     return 0;
 }
 
+template <int MODE = ERI_OUT_GRAD>
 static int launch_grad_generic(const GradCtx &c, bool df, int lbmax, hipStream_t st);
 
+template <int MODE = ERI_OUT_GRAD>
 static int launch_grad_df3c(const GradCtx &c, hipStream_t st) {
     int rc;
-    if ((rc = launch_grad_generic(c, true, DQC_LMAX, st))) return rc;
+    if ((rc = launch_grad_generic<MODE>(c, true, DQC_LMAX, st))) return rc;
 #define DQC_GB(LA) \
-    if ((rc = launch_grad_bra_df<LA, 0>(c, st)) || (rc = launch_grad_bra_df<LA, 1>(c, st)) || (rc = launch_grad_bra_df<LA, 2>(c, st)) || (rc = launch_grad_bra_df<LA, 3>(c, st))) return rc;
+    if ((rc = launch_grad_bra_df<LA, 0, MODE>(c, st)) || (rc = launch_grad_bra_df<LA, 1, MODE>(c, st)) || (rc = launch_grad_bra_df<LA, 2, MODE>(c, st)) || (rc = launch_grad_bra_df<LA, 3, MODE>(c, st))) return rc;
     DQC_GB(0) DQC_GB(1) DQC_GB(2) DQC_GB(3) DQC_GB(4)
 #undef DQC_GB
     return 0;
 }
 
+template <int MODE = ERI_OUT_GRAD>
 static int launch_grad_df2c(const GradCtx &c, hipStream_t st) {
     int rc;
-    if ((rc = launch_grad_generic(c, true, 0, st))) return rc;
-    if ((rc = launch_grad_bra_df<0, 0>(c, st)) || (rc = launch_grad_bra_df<1, 0>(c, st)) || (rc = launch_grad_bra_df<2, 0>(c, st)) ||
-        (rc = launch_grad_bra_df<3, 0>(c, st)) || (rc = launch_grad_bra_df<4, 0>(c, st)))
+    if ((rc = launch_grad_generic<MODE>(c, true, 0, st))) return rc;
+    if ((rc = launch_grad_bra_df<0, 0, MODE>(c, st)) || (rc = launch_grad_bra_df<1, 0, MODE>(c, st)) || (rc = launch_grad_bra_df<2, 0, MODE>(c, st)) ||
+        (rc = launch_grad_bra_df<3, 0, MODE>(c, st)) || (rc = launch_grad_bra_df<4, 0, MODE>(c, st)))
         return rc;
     return 0;
 }
 
 // the classes outside the compile-time set (h companions, g shells) through the runtime kernel; ket pairs (lc >= ld), or
 // (auxiliary shell, unit) when `df`
+template <int MODE>
 static int launch_grad_generic(const GradCtx &c, bool df, int lbmax, hipStream_t st) {
     for (int la = 0; la <= DQC_LMAX + 1; la++)
         for (int lb = 0; lb <= lbmax; lb++)
@@ -189,7 +195,7 @@ static int launch_grad_generic(const GradCtx &c, bool df, int lbmax, hipStream_t
                 for (int ld = 0; ld <= (df ? 0 : lc); ld++) {
                     if (!hl_forced() && la <= GRAD_LMAX + 1 && lb <= GRAD_LMAX && lc <= GRAD_LMAX) continue;
                     const int cb = la * 8 + lb, ck = lc * (lc + 1) / 2 + ld;
-                    int rc = launch_hl<ERI_OUT_GRAD>(nullptr, c.ds, c.dbra, c.dket, c.hbra->cls_start[cb], c.hbra->cls_count[cb],
+                    int rc = launch_hl<MODE>(nullptr, c.ds, c.dbra, c.dket, c.hbra->cls_start[cb], c.hbra->cls_count[cb],
                                                      c.hket->cls_start[ck], c.hket->cls_count[ck], 0, c.og, la, lb, lc, ld, st);
                     if (rc) return rc;
                 }
@@ -198,7 +204,7 @@ static int launch_grad_generic(const GradCtx &c, bool df, int lbmax, hipStream_t
 
 static int launch_grad_all(const GradCtx &c, hipStream_t st) {
     int rc;
-    if ((rc = launch_grad_generic(c, false, DQC_LMAX, st))) return rc;
+    if ((rc = launch_grad_generic<>(c, false, DQC_LMAX, st))) return rc;
 #define DQC_GB(LA) \
     if ((rc = launch_grad_bra<LA, 0>(c, st)) || (rc = launch_grad_bra<LA, 1>(c, st)) || (rc = launch_grad_bra<LA, 2>(c, st)) || (rc = launch_grad_bra<LA, 3>(c, st))) return rc;
     DQC_GB(0) DQC_GB(1) DQC_GB(2) DQC_GB(3) DQC_GB(4)
@@ -928,10 +934,63 @@ int dqc_df_grad(double *d_grad, const double *d_dcart, const double *d_ccart, co
     build_pairs_ordered(b, h2up, N + k0, N + k1, unit, unit + 1);
     build_pairs_ordered(b, h2down, 2 * N + k0, 2 * N + k1, unit, unit + 1);
     build_pairs(b, j.hket, k0, k1, unit);
-    j.passes = {{&h3up, +1, 1, launch_grad_df3c}, {&h3down, -1, 1, launch_grad_df3c},
-                {&h2up, +1, 2, launch_grad_df2c}, {&h2down, -1, 2, launch_grad_df2c}};
+    j.passes = {{&h3up, +1, 1, launch_grad_df3c<>}, {&h3down, -1, 1, launch_grad_df3c<>},
+                {&h2up, +1, 2, launch_grad_df2c<>}, {&h2down, -1, 2, launch_grad_df2c<>}};
     j.nrow = natm; j.norig = N; j.og.ccart = d_ccart;
     return run_grad_job(j, d_dcart, d_grad, (size_t)natm * 3, add_rows, st);
+}
+
+int dqc_df_grad3(double *d_grad, const double *d_z, size_t z_doubles, const double *d_g, const int *atm, int natm, const int *bas,
+                 int nbas, const double *env, int nenv, int sh0, int sh1, int k0, int k1, void *stream) {
+    // the expression dqc_df_grad differentiates, with general densities in place of D_ij c_k and c_k c_l:
+    //   d_grad (natm, 3) += sum Z[i, j, k] d(ij|k) - 1/2 sum G[k, l] d(k|l)
+    // over the CONCATENATED tables (orbital shells [sh0, sh1), auxiliary shells [k0, k1)).  d_z (no, no, nk), symmetric in i, j, the
+    // auxiliary index fastest, and d_g (nk, nk), symmetric: over the Cartesian functions of those two shell ranges ALONE (no and nk
+    // of them).  A null d_z or d_g skips its term, so that Z can be walked in blocks of auxiliary shells with G passed once.
+    // z_doubles: the doubles behind d_z (0 with a null d_z); fewer than no * no * nk is refused before anything is launched.
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    GradJob j;
+    j.who = "dqc_df_grad3";
+    Basis &b = j.b;
+    int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, nullptr);
+    if (rc) return rc;
+    if (sh0 < 0 || sh1 > nbas || sh0 > sh1 || k0 < 0 || k1 > nbas || k0 > k1) { set_error("dqc_df_grad3: shell ranges outside the table"); return DQC_EINVAL; }
+    if (sh0 == sh1 || k0 == k1) return DQC_OK;
+    const int N = nbas;
+    cart_offsets(b, N, j.cao, j.ncart);
+    // the kernels address Z and G by the Cartesian offsets of the shells relative to the first shell of each range (EriOut::ao0,
+    // aux0): the functions of [sh0, sh1) and of [k0, k1) are all they can reach
+    const size_t no = (size_t)((sh1 < N ? j.cao[sh1] : j.ncart) - j.cao[sh0]), nk = (size_t)((k1 < N ? j.cao[k1] : j.ncart) - j.cao[k0]);
+    if ((d_z != nullptr || z_doubles != 0) && z_doubles < no * no * nk) {
+        set_error("dqc_df_grad3: Z is smaller than the (orbital, orbital, auxiliary) Cartesian block of the shell ranges");
+        return DQC_EINVAL;
+    }
+    if (d_z == nullptr && d_g == nullptr) return DQC_OK;
+    if (d_grad == nullptr) { set_error("dqc_df_grad3: null output"); return DQC_EINVAL; }
+    const int ao0 = j.cao[sh0], aux0 = j.cao[k0];
+    j.cao.resize(3 * N + 1, 0);
+    j.rows.assign(3 * N + 1, 0);
+    for (int i = 0; i < N; i++) j.rows[i] = b.shells[i].atom;
+    append_centre_companions(b, N);
+    const int unit = append_unit_shell(b, 1.0);  // (the Cartesian s function 1: dqc_df_grad)
+    HostPairs h3up, h3down, h2up, h2down;
+    if (d_z != nullptr) {
+        build_pairs_ordered(b, h3up, N + sh0, N + sh1, sh0, sh1);
+        build_pairs_ordered(b, h3down, 2 * N + sh0, 2 * N + sh1, sh0, sh1);
+        j.passes.push_back({&h3up, +1, 3, launch_grad_df3c<ERI_OUT_GRAD3>});
+        j.passes.push_back({&h3down, -1, 3, launch_grad_df3c<ERI_OUT_GRAD3>});
+    }
+    if (d_g != nullptr) {
+        build_pairs_ordered(b, h2up, N + k0, N + k1, unit, unit + 1);
+        build_pairs_ordered(b, h2down, 2 * N + k0, 2 * N + k1, unit, unit + 1);
+        j.passes.push_back({&h2up, +1, 4, launch_grad_df2c<ERI_OUT_GRAD3>});
+        j.passes.push_back({&h2down, -1, 4, launch_grad_df2c<ERI_OUT_GRAD3>});
+    }
+    build_pairs(b, j.hket, k0, k1, unit);
+    j.nrow = natm; j.norig = N; j.og.ccart = d_g;
+    j.og.nao = (int)no; j.og.naux = (int)nk; j.og.ao0 = ao0; j.og.aux0 = aux0;
+    return run_grad_job(j, d_z, d_grad, (size_t)natm * 3, add_rows, st);
 }
 
 }  // extern "C"

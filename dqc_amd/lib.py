@@ -84,6 +84,7 @@ def load():
     lib.dqc_eri_grad_basis.argtypes = [c_dp, c_dp, ctypes.c_double, ctypes.c_double] + tab + [c_vp]
     lib.dqc_int1e_potential.argtypes = [c_dp, c_dp, c_dp, c_int] + tab + [c_vp]
     lib.dqc_df_grad.argtypes = [c_dp, c_dp, c_dp] + tab + [c_int, c_int, c_int, c_int, c_vp]
+    lib.dqc_df_grad3.argtypes = [c_dp, c_dp, c_sz, c_dp] + tab + [c_int, c_int, c_int, c_int, c_vp]
     lib.dqc_becke_weights.argtypes = [c_dp, c_dp, c_vp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.c_double, c_vp]
     lib.dqc_becke_weights_grad.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_vp, c_dp, c_dp, c_dp, c_int, c_int, ctypes.c_double, c_vp]
     lib.dqc_purify_tc2.argtypes = [c_dp, c_dp, c_int, ctypes.c_double, c_int, ctypes.c_double, c_dp, c_vp]
@@ -789,6 +790,32 @@ def df_grad(grad, dcart, ccart, tab, orb_range, aux_range):
     (s0, s1), (k0, k1) = orb_range, aux_range
     with _on(grad.device) as st_:
         _check(load().dqc_df_grad(_ptr(grad), _ptr(dcart), _ptr(ccart), *tab.args(), s0, s1, k0, k1, st_), "dqc_df_grad")
+    return grad
+
+
+def _ncart_range(tab, rng):
+    l = tab.bas[rng[0]:rng[1], 1].astype(np.int64)
+    return int(((l + 1) * (l + 2) // 2).sum())
+
+
+def df_grad3(grad, z, g, tab, orb_range, aux_range):
+    """grad (natm of the table, 3) += sum Z[i, j, k] d(ij|k) - 1/2 sum G[k, l] d(k|l) (csrc/grad.hip: dqc_df_grad3) over the
+    concatenated table.  z (no, no, nk), symmetric in its first two indices, and g (nk, nk), symmetric: contiguous float64 tensors on
+    the device of grad over the Cartesian functions of the shells `orb_range` and `aux_range` alone; either may be None (that term is
+    skipped: Z is walked in blocks of auxiliary shells with g=None, G passed once with z=None)"""
+    (s0, s1), (k0, k1) = (int(x) for x in orb_range), (int(x) for x in aux_range)
+    if not (0 <= s0 <= s1 <= tab.nbas and 0 <= k0 <= k1 <= tab.nbas):
+        raise DqcAmdError("df_grad3: shell ranges outside the table")
+    no, nk = _ncart_range(tab, (s0, s1)), _ncart_range(tab, (k0, k1))
+    if tuple(grad.shape) != (tab.natm, 3) or grad.dtype != torch.float64 or not grad.is_contiguous():
+        raise DqcAmdError("df_grad3: grad must be a contiguous float64 (%d, 3) tensor, got %s" % (tab.natm, tuple(grad.shape)))
+    for name, m, shape in (("Z", z, (no, no, nk)), ("G", g, (nk, nk))):
+        if m is not None and (tuple(m.shape) != shape or m.dtype != torch.float64 or not m.is_contiguous() or m.device != grad.device):
+            raise DqcAmdError("df_grad3: %s must be a contiguous float64 %s tensor on the device of grad (the Cartesian functions of "
+                              "the shell ranges), got %s %s on %s" % (name, shape, m.dtype, tuple(m.shape), m.device))
+    with _on(grad.device) as st_:
+        _check(load().dqc_df_grad3(_ptr(grad), None if z is None else _ptr(z), 0 if z is None else z.numel(),
+                                   None if g is None else _ptr(g), *tab.args(), s0, s1, k0, k1, st_), "dqc_df_grad3")
     return grad
 
 

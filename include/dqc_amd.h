@@ -411,6 +411,25 @@ int dqc_int1e_potential(double *d_out, const double *d_dcart, const double *d_po
  * table lists the molecule's atoms twice: the caller folds the two halves).  Shells up to g. */
 int dqc_df_grad(double *d_grad, const double *d_dcart, const double *d_ccart, const int *atm, int natm, const int *bas,
                 int nbas, const double *env, int nenv, int sh0, int sh1, int k0, int k1, void *stream);
+/* The expression dqc_df_grad differentiates with GENERAL densities in place of the products D_ij c_k and c_k c_l (the non-separable
+ * part of an RI-MP2 gradient; what a gradient with fitted exchange needs):
+ *   d_grad += sum Z[i, j, k] d(ij|k) - 1/2 sum G[k, l] d(k|l)          at fixed Z and G,
+ * derivatives on orbital centres to the atom of i, the auxiliary centre of the three-index term by translational invariance, the
+ * (d k|l) term to the atom of k; with Z = D (x) c and G = c c^T it is dqc_df_grad.  Same concatenated tables and shell ranges.
+ *   d_z (no, no, nk): symmetric in i, j; the layout of j3c, AUXILIARY INDEX FASTEST (consecutive lanes of a quartet run over the
+ *        ket components first, so this gives neighbouring addresses; [k][i][j] would give a stride of no^2).  Not measured against
+ *        another layout.
+ *   d_g (nk, nk): symmetric.
+ * Both over the Cartesian functions of the shells [sh0, sh1) and [k0, k1) ALONE (no and nk of them: T^T . T with the rows of
+ * dqc_cart2sph_matrix that belong to those ranges) -- not of the whole table as dqc_df_grad takes its operands.
+ * Either of d_z, d_g may be null: that term is skipped.  Z is 8 no^2 nk bytes, so the caller walks it in blocks of auxiliary
+ * shells -- [k0, k1) a sub-range, d_z holding that sub-range only, d_g null -- and passes G once, with d_z null, over the whole
+ * auxiliary range.  z_doubles: the doubles behind d_z (0 with a null d_z).  The entry point computes no^2 nk from the table and
+ * refuses a smaller z_doubles before anything is launched; the kernels address Z from shell offsets of those ranges only.
+ * Empty ranges, or both pointers null: returns 0 and touches nothing.  Shells up to g (ERI_OUT_GRAD3 instantiations of the (l, 0)
+ * ket classes and of the runtime kernel: the ERI_OUT_GRAD kernels of the other entry points are not changed by them). */
+int dqc_df_grad3(double *d_grad, const double *d_z, size_t z_doubles, const double *d_g, const int *atm, int natm, const int *bas,
+                 int nbas, const double *env, int nenv, int sh0, int sh1, int k0, int k1, void *stream);
 
 /* ---- Becke partition weights of the multi-centre grid  (dqc/grid/multiatoms_scheme.py:9-67, becke_grid.py:18-60) ----------
  * d_xyz (ngrid, 3): the atoms' grids one after the other, atom a owning points [d_atom_off[a], d_atom_off[a + 1]) (natm + 1
