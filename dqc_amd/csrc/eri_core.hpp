@@ -193,8 +193,16 @@ struct OidxTab {
 //   ERI_OUT_GRAD3 : ERI_OUT_GRAD with the general density-fitting contractions (gmode 3 and 4 of EriOut) in place of the products
 //                   of matrices: instantiated for the (LC, 0) density-fitting classes alone (dqc_df_grad3), so that the epilogue
 //                   the four-index classes compile stays as short as it was
-enum { ERI_OUT_TILES = 0, ERI_OUT_3C = 1, ERI_OUT_2C = 2, ERI_OUT_GRAD = 3, ERI_OUT_JK = 4, ERI_OUT_SCHWARZ = 5, ERI_OUT_J = 6, ERI_OUT_GRAD3 = 7 };
-__host__ __device__ constexpr bool eri_grad_mode(int mode) { return mode == ERI_OUT_GRAD || mode == ERI_OUT_GRAD3; }
+//   ERI_OUT_GRAD2 : ERI_OUT_GRAD (gmode 0) as the symmetric BILINEAR form of two Cartesian matrices A = dcart and B = ccart, both
+//                   symmetric or both antisymmetric (then jscale = 0):
+//                   sum [jscale (A_ab B_cd + B_ab A_cd) - kscale / 2 (A_ac B_bd + B_ac A_bd)] over ordered (a, b) and all (c, d);
+//                   A = B = D is ERI_OUT_GRAD.  The kernel walks unique c >= d: the exchange part of a quartet is A_ac B_bd + B_ac A_bd
+//                   and, c != d, A_ad B_bc + B_ad A_bc with the indices in THIS order -- the (d, c) image of the first under the
+//                   simultaneous swap the form is invariant to, for either parity, so the kernel needs no parity flag.
+//                   Instantiated for the four-index classes (dqc_eri_grad2: the two-particle densities of an excited-state Lagrangian)
+enum { ERI_OUT_TILES = 0, ERI_OUT_3C = 1, ERI_OUT_2C = 2, ERI_OUT_GRAD = 3, ERI_OUT_JK = 4, ERI_OUT_SCHWARZ = 5, ERI_OUT_J = 6, ERI_OUT_GRAD3 = 7,
+       ERI_OUT_GRAD2 = 8 };
+__host__ __device__ constexpr bool eri_grad_mode(int mode) { return mode == ERI_OUT_GRAD || mode == ERI_OUT_GRAD3 || mode == ERI_OUT_GRAD2; }
 
 // lane-group size of a compile-time class by its Cartesian block size (EriCfg::TPQ; the host's screened task maps need it too)
 __host__ __device__ constexpr int eri_tpq(int nout) { return nout <= 9 ? 1 : (nout <= 81 ? 4 : (nout <= 324 ? 16 : (nout <= 1296 ? 64 : 256))); }
@@ -242,6 +250,7 @@ struct EriOut {
     // fields above (nao / naux: Cartesian functions of the orbital / auxiliary range, ao0 / aux0: Cartesian offset of its first shell):
     //                           gmode 3: (d_A a b|k) Z[a, b, k] -> +2 to a's atom, -2 to k's atom; dcart = Z (nao, nao, naux), k fastest
     //                           gmode 4: (d_A k|l) G[k, l]      -> -1 to k's atom;                 ccart = G (naux, naux)
+    // ERI_OUT_GRAD2 (dqc_eri_grad2), gmode 0: dcart = A, ccart = B, both (ncart, ncart)
     int gmode = 0;
     const double *ccart = nullptr;
     // ---- JK mode: symmetric AO density (nao, nao), accumulators A (J = (A + A^T) / 2) and B (K = B + B^T; NULL: J only)
@@ -805,6 +814,31 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                 int u[3];
                 cart_pow(LA, cu, u[0], u[1], u[2]);
                 const size_t ib = cb0 + cb, ic = cc0 + cc, id = cd0 + cd;
+                if constexpr (MODE == ERI_OUT_GRAD2) {
+                    // the bilinear form of A = dcart and B = ccart: the b-, c-, d-indexed elements of both once per output, outside the
+                    // direction loop; a zero scale leaves its loads out (the antisymmetric pair has no Coulomb part)
+                    const double *B2 = og.ccart;
+                    const bool with_j = og.jscale != 0.0, with_k = og.kscale != 0.0;
+                    const double j2 = (same_cd ? 1.0 : 2.0) * og.jscale, k2 = 0.5 * og.kscale;
+                    double acd = 0.0, bcd = 0.0, abd = 0.0, bbd = 0.0, abc = 0.0, bbc = 0.0;
+                    if (with_j) { acd = D[ic * nc + id]; bcd = B2[ic * nc + id]; }
+                    if (with_k) { abd = D[ib * nc + id]; bbd = B2[ib * nc + id]; abc = D[ib * nc + ic]; bbc = B2[ib * nc + ic]; }
+#pragma unroll
+                    for (int dir = 0; dir < 3; dir++) {
+                        int o[3] = {u[0], u[1], u[2]};
+                        o[dir] -= og.dirn;
+                        if (o[dir] < 0) continue;
+                        const double coef = og.dirn >= 0 ? 1.0 : -(double)o[dir];
+                        const size_t ia = ca0 + cart_index(la, o[0], o[2]);
+                        double f = 0.0;
+                        if (with_j) f = j2 * (D[ia * nc + ib] * bcd + B2[ia * nc + ib] * acd);
+                        if (with_k) {
+                            f -= k2 * (D[ia * nc + ic] * bbd + B2[ia * nc + ic] * abd);
+                            if (!same_cd) f -= k2 * (D[ia * nc + id] * bbc + B2[ia * nc + id] * abc);
+                        }
+                        g[dir] += coef * acc[0][m] * f;
+                    }
+                } else {
                 double dcd = 0.0, dbd = 0.0, dbc = 0.0;
                 const bool with_k = og.kscale != 0.0;  // (Kohn-Sham: Coulomb-type product only -- four density loads per output fewer)
                 if (og.gmode == 0) {
@@ -838,6 +872,7 @@ __global__ __launch_bounds__(256) void eri_kernel(double *__restrict__ tiles, De
                         f = -og.ccart[ia] * og.ccart[ic];
                     g[dir] += coef * acc[0][m] * f;
                 }
+                }  // (not ERI_OUT_GRAD2)
             }
         }
         // reduce over the TPQ lanes of the quartet, one atomic per direction

@@ -300,6 +300,30 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
                     int u[3];
                     cart_pow(la, hc.full ? cal : slice, u[0], u[1], u[2]);
                     const size_t ibb = cb0 + cb, ic = cc0 + cc, id = cd0 + cd;
+                    if constexpr (MODE == ERI_OUT_GRAD2) {
+                        // the bilinear form of A = dcart and B = ccart (eri_core.hpp)
+                        const double *B2 = og.ccart;
+                        const bool with_j = og.jscale != 0.0, with_k = og.kscale != 0.0;
+                        const double j2 = (same_cd ? 1.0 : 2.0) * og.jscale, k2 = 0.5 * og.kscale;
+                        double acd = 0.0, bcd = 0.0, abd = 0.0, bbd = 0.0, abc = 0.0, bbc = 0.0;
+                        if (with_j) { acd = D[ic * nc + id]; bcd = B2[ic * nc + id]; }
+                        if (with_k) { abd = D[ibb * nc + id]; bbd = B2[ibb * nc + id]; abc = D[ibb * nc + ic]; bbc = B2[ibb * nc + ic]; }
+#pragma unroll
+                        for (int dir = 0; dir < 3; dir++) {
+                            int o[3] = {u[0], u[1], u[2]};
+                            o[dir] -= og.dirn;
+                            if (o[dir] < 0) continue;
+                            const double coef = og.dirn >= 0 ? 1.0 : -(double)o[dir];
+                            const size_t ia = ca0 + cart_index(lorig, o[0], o[2]);
+                            double f = 0.0;
+                            if (with_j) f = j2 * (D[ia * nc + ibb] * bcd + B2[ia * nc + ibb] * acd);
+                            if (with_k) {
+                                f -= k2 * (D[ia * nc + ic] * bbd + B2[ia * nc + ic] * abd);
+                                if (!same_cd) f -= k2 * (D[ia * nc + id] * bbc + B2[ia * nc + id] * abc);
+                            }
+                            gsum[dir] += coef * acc[m] * f;
+                        }
+                    } else {
                     double dcd = 0.0, dbd = 0.0, dbc = 0.0;
                     if (og.gmode == 0) { dcd = D[ic * nc + id]; dbd = D[ibb * nc + id]; dbc = D[ibb * nc + ic]; }
 #pragma unroll
@@ -327,6 +351,7 @@ __global__ __launch_bounds__(256) void eri_hl_kernel(double *__restrict__ tiles,
                             f = -og.ccart[ia] * og.ccart[ic];
                         gsum[dir] += coef * acc[m] * f;
                     }
+                    }  // (not ERI_OUT_GRAD2)
                 }
             }
         } else {

@@ -17,13 +17,15 @@
 // The same two contractions by the BASIS parameters of every primitive p (exponent alpha_p, stored coefficient c_p) instead of the
 // centres: dqc_eri_grad_basis / dqc_int1e_grad_basis, with d a / d c_p = g_p and d a / d alpha_p = -c_p r_A^2 g_p (an l + 2 shell) as
 // per-primitive uncontracted companions.  Orbital shells up to f there (f + 2 = h).
-// Host side: dqc_eri_grad, dqc_eri_grad_basis, dqc_df_grad (the same passes over (orbital pair | auxiliary) and (auxiliary |
+// dqc_eri_grad2 is dqc_eri_grad as the symmetric bilinear form of two matrices, both symmetric or both antisymmetric (the ERI_OUT_GRAD2
+// instantiations, compiled in grad2.hip; the two-particle densities of an excited-state Lagrangian).
+// Host side: dqc_eri_grad, dqc_eri_grad2, dqc_eri_grad_basis, dqc_df_grad (the same passes over (orbital pair | auxiliary) and (auxiliary |
 // auxiliary) for the density-fitted Coulomb energy) and dqc_df_grad3 (those passes against a general three-index density Z[a, b, k]
 // and a general G[k, l] -- the ERI_OUT_GRAD3 instantiations; the non-separable part of the RI-MP2 gradient) only parse, build their companions and ordered bra pair lists, name their
 // passes (bra list, dirn, gmode, launcher) in a GradJob and say how summed rows become output entries; run_grad_job owns the
 // rest -- uploads, the 64 slots of partial sums, the side-stream fork and join, the launches and the host fold.  The two
 // one-electron entry points share int1e_grad_setup in the same way.
-#include "eri_generic.hpp"
+#include "grad_launch.hpp"
 
 namespace dqc {
 
@@ -35,8 +37,6 @@ namespace hostc2s {
 #include "cart2sph.inc"
 #undef C2S_QUAL
 }  // namespace hostc2s
-
-constexpr int GRAD_LMAX = 3;  // orbital shells up to f in the compile-time classes (companions up to g); above: eri_generic.hpp
 
 static void cart_offsets(const Basis &b, int nsh, std::vector<int> &cao, int &ncart) {
     cao.resize(nsh);
@@ -93,63 +93,6 @@ static void append_centre_companions(Basis &b, int N) {
         }
 }
 
-struct GradCtx {
-    DevShells ds;
-    DevPairs dbra, dket;
-    const HostPairs *hbra, *hket;
-    EriOut og;
-    DevPool *pool = nullptr;  // stream-ordered pool for the wave tables (nullptr: flat task maps)
-    SideStreams *side = nullptr;  // class launches dealt round-robin to the side streams (common.hpp)
-    int wmap_depth = 1 << 30;  // class pairs whose deepest contraction has at least this many primitive quartets take the wave map
-};
-
-// MODE: ERI_OUT_GRAD, or ERI_OUT_GRAD3 for the passes of dqc_df_grad3 (gmode 3 and 4)
-template <int LA, int LB, int LC, int LD, int MODE = ERI_OUT_GRAD>
-static int launch_grad_class(const GradCtx &c, hipStream_t st) {
-    using Cfg = EriCfg<LA, LB, LC, LD>;
-    const int cb = LA * 8 + LB, ck = LC * (LC + 1) / 2 + LD;
-    const int nb = c.hbra->cls_count[cb], nk = c.hket->cls_count[ck];
-    if (nb == 0 || nk == 0 || hl_forced()) return 0;
-    const long long ntask = (long long)nb * nk;
-    const long long nblk = eri_num_blocks<Cfg>(nb, nk, ntask);
-    auto kern = eri_kernel<LA, LB, LC, LD, MODE>;
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES_G);
-    if (c.side != nullptr) st = c.side->take();
-    // (only where the class pair's deepest contraction -- first pair of each class: the lists are sorted by depth -- is worth splitting)
-    const int dmax = (c.hbra->pp_off[c.hbra->cls_start[cb] + 1] - c.hbra->pp_off[c.hbra->cls_start[cb]]) *
-                     (c.hket->pp_off[c.hket->cls_start[ck] + 1] - c.hket->pp_off[c.hket->cls_start[ck]]);
-    if (Cfg::TPQ <= 16 && c.pool != nullptr && dmax >= c.wmap_depth) {
-        // depth-binned wave map (eri_core.hpp: eri_split_lanes, eri_wave_table): the deep (companion, s) x (s, s) contractions were
-        // serial chains in single lane groups
-        std::vector<WaveRun> runs;
-        EriOut o2 = c.og;
-        const long long nwave = eri_wave_runs(runs, o2.wbin, *c.hbra, c.hbra->cls_start[cb], nb, *c.hket, c.hket->cls_start[ck], nk, Cfg::TPQ);
-        if (nwave == 0) return 0;
-        WaveRun *d_runs = nullptr;
-        if (c.pool->upload(&d_runs, runs, st)) { set_error("dqc_eri_grad: device upload failed"); return DQC_ENOMEM; }
-        o2.wruns = d_runs;
-        o2.nruns = (int)runs.size();
-        hipLaunchKernelGGL(kern, dim3((unsigned)((nwave + 3) / 4)), dim3(256), Cfg::LDS_BYTES_G, st, (double *)nullptr, c.ds, c.dbra, c.dket,
-                           c.hbra->cls_start[cb], nb, c.hket->cls_start[ck], nk, 0, nwave, o2);
-        DQC_CHECK_LAUNCH();
-        return 0;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), Cfg::LDS_BYTES_G, st, (double *)nullptr, c.ds, c.dbra, c.dket,
-                       c.hbra->cls_start[cb], nb, c.hket->cls_start[ck], nk, 0, ntask, c.og);
-    DQC_CHECK_LAUNCH();
-    return 0;
-}
-
-template <int LA, int LB>
-static int launch_grad_bra(const GradCtx &c, hipStream_t st) {
-    int rc;
-#define DQC_GK(LC, LD) \
-    if ((rc = launch_grad_class<LA, LB, LC, LD>(c, st))) return rc;
-    DQC_GK(0, 0) DQC_GK(1, 0) DQC_GK(1, 1) DQC_GK(2, 0) DQC_GK(2, 1) DQC_GK(2, 2) DQC_GK(3, 0) DQC_GK(3, 1) DQC_GK(3, 2) DQC_GK(3, 3)
-#undef DQC_GK
-    return 0;
-}
-
 // density-fitting gradients: ket pairs are (auxiliary shell, unit), classes (LC, 0), LC up to f
 template <int LA, int LB, int MODE>
 static int launch_grad_bra_df(const GradCtx &c, hipStream_t st) {
@@ -160,9 +103,6 @@ static int launch_grad_bra_df(const GradCtx &c, hipStream_t st) {
 #undef DQC_GK
     return 0;
 }
-
-template <int MODE = ERI_OUT_GRAD>
-static int launch_grad_generic(const GradCtx &c, bool df, int lbmax, hipStream_t st);
 
 template <int MODE = ERI_OUT_GRAD>
 static int launch_grad_df3c(const GradCtx &c, hipStream_t st) {
@@ -182,33 +122,6 @@ static int launch_grad_df2c(const GradCtx &c, hipStream_t st) {
     if ((rc = launch_grad_bra_df<0, 0, MODE>(c, st)) || (rc = launch_grad_bra_df<1, 0, MODE>(c, st)) || (rc = launch_grad_bra_df<2, 0, MODE>(c, st)) ||
         (rc = launch_grad_bra_df<3, 0, MODE>(c, st)) || (rc = launch_grad_bra_df<4, 0, MODE>(c, st)))
         return rc;
-    return 0;
-}
-
-// the classes outside the compile-time set (h companions, g shells) through the runtime kernel; ket pairs (lc >= ld), or
-// (auxiliary shell, unit) when `df`
-template <int MODE>
-static int launch_grad_generic(const GradCtx &c, bool df, int lbmax, hipStream_t st) {
-    for (int la = 0; la <= DQC_LMAX + 1; la++)
-        for (int lb = 0; lb <= lbmax; lb++)
-            for (int lc = 0; lc <= DQC_LMAX; lc++)
-                for (int ld = 0; ld <= (df ? 0 : lc); ld++) {
-                    if (!hl_forced() && la <= GRAD_LMAX + 1 && lb <= GRAD_LMAX && lc <= GRAD_LMAX) continue;
-                    const int cb = la * 8 + lb, ck = lc * (lc + 1) / 2 + ld;
-                    int rc = launch_hl<MODE>(nullptr, c.ds, c.dbra, c.dket, c.hbra->cls_start[cb], c.hbra->cls_count[cb],
-                                                     c.hket->cls_start[ck], c.hket->cls_count[ck], 0, c.og, la, lb, lc, ld, st);
-                    if (rc) return rc;
-                }
-    return 0;
-}
-
-static int launch_grad_all(const GradCtx &c, hipStream_t st) {
-    int rc;
-    if ((rc = launch_grad_generic<>(c, false, DQC_LMAX, st))) return rc;
-#define DQC_GB(LA) \
-    if ((rc = launch_grad_bra<LA, 0>(c, st)) || (rc = launch_grad_bra<LA, 1>(c, st)) || (rc = launch_grad_bra<LA, 2>(c, st)) || (rc = launch_grad_bra<LA, 3>(c, st))) return rc;
-    DQC_GB(0) DQC_GB(1) DQC_GB(2) DQC_GB(3) DQC_GB(4)
-#undef DQC_GB
     return 0;
 }
 
@@ -763,7 +676,7 @@ int dqc_eri_grad(double *d_grad, const double *d_dcart, double jscale, double ks
     build_pairs_ordered(b, hup, N, 2 * N, 0, N);
     build_pairs_ordered(b, hdown, 2 * N, 3 * N, 0, N);
     build_pairs(b, j.hket, 0, N);
-    j.passes = {{&hup, +1, 0, launch_grad_all}, {&hdown, -1, 0, launch_grad_all}};
+    j.passes = {{&hup, +1, 0, launch_grad_all<>}, {&hdown, -1, 0, launch_grad_all<>}};
     j.nrow = natm; j.norig = N; j.og.jscale = jscale; j.og.kscale = kscale;
     j.fork = true;
     // the depth-binned wave map of the fill (eri_core.hpp) is OFF here: measured on a 20-atom cc-pVDZ gradient it is slower for every
@@ -772,6 +685,56 @@ int dqc_eri_grad(double *d_grad, const double *d_dcart, double jscale, double ks
     static const int wmap_env = [] { const char *e = getenv("DQC_GRAD_WMAP"); return e ? atoi(e) : 0; }();
     j.wmap_depth = wmap_env;
     return run_grad_job(j, d_dcart, d_grad, (size_t)natm * 3, add_rows, st);
+}
+
+int dqc_eri_grad2(double *d_grad, const double *d_acart, const double *d_bcart, int ncart, int parity_a, int parity_b, double jscale,
+                  double kscale, const int *atm, int natm, const int *bas, int nbas, const double *env, int nenv, void *stream) {
+    // the symmetric bilinear form whose diagonal is dqc_eri_grad (A = B = D):
+    //   d_grad (natm, 3) += sum_{a in A} sum_bcd (d_A a b|c d) [jscale (A_ab B_cd + B_ab A_cd) - kscale / 2 (A_ac B_bd + B_ac A_bd)]
+    // d_acart, d_bcart (ncart, ncart); parity_a, parity_b: +1 for an exactly symmetric matrix, -1 for an exactly antisymmetric one,
+    // as the caller has verified them (the matrices are device memory).  Only for a same-parity pair is "derivative on the first
+    // index" a quarter of the derivative of sum (ab|cd) Gamma_abcd, so every other pair is refused, as is an antisymmetric one with a
+    // Coulomb part (A_ab B_cd summed with (ab| symmetric is zero: a non-zero jscale is a mistake of the caller).
+    // The ERI_OUT_GRAD2 instantiations (grad2.hip); B rides in EriOut::ccart, which gmode 0 does not read otherwise.
+    using namespace dqc;
+    hipStream_t st = (hipStream_t)stream;
+    GradJob j;
+    j.who = "dqc_eri_grad2";
+    Basis &b = j.b;
+    int rc = parse_basis(b, atm, natm, bas, nbas, env, nenv, nullptr);
+    if (rc) return rc;
+    const int N = nbas;
+    cart_offsets(b, N, j.cao, j.ncart);
+    if (ncart != j.ncart) {
+        set_error("dqc_eri_grad2: the matrices are (" + std::to_string(ncart) + ", " + std::to_string(ncart) + "), the table has " +
+                  std::to_string(j.ncart) + " Cartesian functions");
+        return DQC_EINVAL;
+    }
+    if ((parity_a != 1 && parity_a != -1) || (parity_b != 1 && parity_b != -1)) {
+        set_error("dqc_eri_grad2: a parity is +1 (symmetric) or -1 (antisymmetric)");
+        return DQC_EINVAL;
+    }
+    if (parity_a != parity_b) {
+        set_error("dqc_eri_grad2: one matrix is symmetric and the other antisymmetric (the bilinear form needs a same-parity pair)");
+        return DQC_EINVAL;
+    }
+    if (parity_a == -1 && jscale != 0.0) {
+        set_error("dqc_eri_grad2: an antisymmetric pair has no Coulomb part (jscale must be 0)");
+        return DQC_EINVAL;
+    }
+    if (nbas == 0) return DQC_OK;
+    if (d_grad == nullptr || d_acart == nullptr || d_bcart == nullptr) { set_error("dqc_eri_grad2: null pointer"); return DQC_EINVAL; }
+    j.rows.resize(N);
+    for (int i = 0; i < N; i++) j.rows[i] = b.shells[i].atom;
+    append_centre_companions(b, N);
+    HostPairs hup, hdown;
+    build_pairs_ordered(b, hup, N, 2 * N, 0, N);
+    build_pairs_ordered(b, hdown, 2 * N, 3 * N, 0, N);
+    build_pairs(b, j.hket, 0, N);
+    j.passes = {{&hup, +1, 0, launch_grad2_all}, {&hdown, -1, 0, launch_grad2_all}};
+    j.nrow = natm; j.norig = N; j.og.jscale = jscale; j.og.kscale = kscale; j.og.ccart = d_bcart;
+    j.fork = true;
+    return run_grad_job(j, d_acart, d_grad, (size_t)natm * 3, add_rows, st);
 }
 
 int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart, const int *atm, int natm, const int *bas,
@@ -834,7 +797,7 @@ int dqc_eri_grad_basis(double *d_out, const double *d_dcart, double jscale, doub
     build_pairs_ordered(b, hsame, N, N + P, 0, N);
     build_pairs_ordered(b, hup2, N + P, N + 2 * P, 0, N);
     build_pairs(b, j.hket, 0, N);
-    j.passes = {{&hsame, 0, 0, launch_grad_all}, {&hup2, 2, 0, launch_grad_all}};
+    j.passes = {{&hsame, 0, 0, launch_grad_all<>}, {&hup2, 2, 0, launch_grad_all<>}};
     j.nrow = 2 * P; j.norig = N + 2 * P; j.og.jscale = jscale; j.og.kscale = kscale;
     j.fork = true;
     // alpha_p: the three raised powers of row P + p together; c_p: row p holds the same sum three times

@@ -1,0 +1,265 @@
+"""Analytic nuclear gradients and relaxed one-particle properties of CIS and TDHF excited states (restricted closed-shell
+Hartree-Fock reference): d(E_SCF + w) / dR by the Z-vector method (Furche and Ahlrichs, J. Chem. Phys. 117, 7433 (2002), without
+the exchange-correlation terms), with the two-electron part on the bilinear derivative pass dqc_eri_grad2 (csrc/grad.hip, grad2.hip).
+
+Variables: those of dqc_amd/response.py -- spatial orbitals, U = X+Y and V = X-Y as (nocc, nvir) matrices with U . V = 1 (TDA / CIS:
+U = V = X, X . X = 1).  i, j occupied, a, b virtual, p, q any orbital; mu, nu, ... AOs.  The functional
+
+    w[C, U, V] = 1/2 [U^T (A+B) U + V^T (A-B) V]
+    singlet  (A+B)_ia,jb = d_ij F_ab - d_ab F_ij + 4 (ia|jb) - (ib|ja) - (ij|ab)        (A-B)_ia,jb = d_ij F_ab - d_ab F_ij + (ib|ja) - (ij|ab)
+    triplet  the same without 4 (ia|jb)
+
+is stationary in U and V under the normalisation (its value there is the excitation energy) but not in the orbitals.  Written in the
+AO basis with  R+- = C_o (U, V) C_v^T,  S = (R+ + R+^T) / 2  (symmetric),  N = (R- - R-^T) / 2  (antisymmetric):
+
+    w = tr[T F] + E2,     T_ab = 1/2 sum_i (U_ia U_ib + V_ia V_ib),    T_ij = -1/2 sum_a (U_ia U_ja + V_ia V_ja)      (no ov block)
+    E2 = sum (ab|cd) [2 S_ab S_cd - S_ac S_bd - N_ac N_bd]         (triplet: without 2 S S; the cross terms S . N vanish)
+       = 1/2 tr[S G+] + 1/2 tr[N^T G-],      G+ = 4 J[S] - 2 K[S]  (triplet -2 K[S]),   G- = -2 K[N]   (K[M]_pq = (pr|qs) M_rs; G- antisymmetric)
+
+[sum_ijab U_ia U_jb (ia|jb) = sum S S (ab|cd);  sum S_ac S_bd (ab|cd) = 1/2 sum U U [(ij|ab) + (ib|ja)];  sum N_ac N_bd (ab|cd) = 1/2 sum V V
+[(ij|ab) - (ib|ja)].]  F = h + G[D], G[D] = J[D] - K[D] / 2, D = 2 C_o C_o^T, so tr[T F] = tr[Tbar h] + tr[D G[Tbar]], Tbar = C T C^T.
+
+Derivative by the orbitals, as the matrix Gm[p, q] = C_p^T dw / dC_q (canonical orbitals):
+
+    Gm[p, q]  = 2 eps_p T_pq                                                 (the outer orbitals of tr[T C^T F C])
+    Gm[p, i] += 4 (C^T G[Tbar] C_o)_pi                                       (F follows D)
+    Gm[p, i] += sum_a (g+_pa U_ia + g-_pa V_ia)      Gm[p, a] += sum_i (g+_ip U_ia + g-_ip V_ia)      g+- = C^T G+- C     (`coupling`)
+
+(dE2 = sum dR+_ab G+_ab + sum dR-_ab G-_ab: the symmetric / antisymmetric parts select themselves.)  Under a rotation kappa_ai (dC_i =
+sum_a C_a kappa_ai, dC_a = -sum_i C_i kappa_ai: response.OrbitalHessian) w changes by R . kappa with
+
+    R_ai = Gm[a, i] - Gm[i, a] = 4 (C_v^T G[Tbar] C_o)_ai + sum_b (g+_ab U_ib + g-_ab V_ib) - sum_j (g+_ji U_ja + g-_ji V_ja)
+
+The SCF condition 4 F_ai = 0 moves the orbitals with a perturbation; the Lagrangian w + sum_ai z_ai 4 F_ai is stationary in kappa for
+
+    H z = -R      (H = 4 (A+B) of the SINGLET channel -- the orbital Hessian -- for triplet states too: the relaxation is a singlet),
+
+and sum z_ai 4 F_ai = tr[Z F] with Z_ai = Z_ia = 2 z_ai: the relaxed difference density is P = T + Z, and everything above holds for the
+Lagrangian with P in place of T in the first two lines of Gm.  What is left of dC / dR is the re-orthonormalisation dC = -1/2 C (C^T dS C),
+which meets the Lagrangian through W = C 1/4 (Gm + Gm^T) C^T.  With Pbar = C P C^T:
+
+    d w / dR = tr[Pbar dh] - tr[W dS]                                                                          -> lib.int1e_grad
+             + separable       d_integrals tr[Pbar G[D]]    = 2 eri_grad2(D, Pbar, 1, 1)                        -> lib.eri_grad2
+             + non-separable   d_integrals E2               = eri_grad2(S, S, 4, 4) + eri_grad2(N, N, 0, 4)    (triplet: (S, S, 0, 4))
+
+[eri_grad2(A, B, j, k) = sum_{a on the atom} (d a b|c d) [j (A_ab B_cd + B_ab A_cd) - k / 2 (A_ac B_bd + B_ac A_bd)]; a two-particle density
+invariant under (ab) <-> (cd) and a <-> b, c <-> d has a quarter of its derivative on the first index, so sum (ab|cd) Gamma_abcd
+differentiates to 4 sum (d a b|c d) Gamma_abcd: Gamma = 1/2 (P_ab D_cd + D_ab P_cd) - 1/4 (P_ac D_bd + D_ac P_bd) and Gamma = 2 S S - S S - N N
+give the factors above.]  A one-electron perturbation lambda O has d w / d lambda = tr[Pbar O]: the relaxed excited-state dipole moment is
+that of D + Pbar.
+
+The algebra lives in functions of plain tensors (`difference_density`, `transition_densities`, `lagrangian_rhs`, `energy_weighted`) that
+take a callable for J and K, so that tests/test_excited_gradient_cpu.py drives them with dense oracle integrals; the factors are held
+against finite differences there and in tests/test_gpu_excited_gradient.py.  Kohn-Sham references need the third-order
+exchange-correlation kernel, which does not exist here, and are refused."""
+import torch
+
+from . import lib
+from .postscf import memoised
+
+
+# ------------------------------------------------------------------------------------------------ algebra on plain tensors
+def difference_density(u, v):
+    """(T_oo (no, no), T_vv (nv, nv)): the unrelaxed difference density of the module docstring; u = X+Y, v = X-Y as (no, nv)"""
+    return -0.5 * (u @ u.T + v @ v.T), 0.5 * (u.T @ u + v.T @ v)
+
+
+def transition_densities(u, v, co, cv):
+    """(S, N): the symmetric part of R+ = C_o (X+Y) C_v^T and the antisymmetric part of R- = C_o (X-Y) C_v^T, AO basis"""
+    rp, rm = co @ u @ cv.T, co @ v @ cv.T
+    return 0.5 * (rp + rp.T), 0.5 * (rm - rm.T)
+
+
+def lagrangian_rhs(u, v, co, cv, jk, triplet=False):
+    """(R (nv, no), parts): R_ai = dw / dkappa_ai at fixed X, Y, from the Fock-type matrices G+[S], G-[N] and G[Tbar] of ONE call
+    jk(dms_j (nj, nao, nao), dms_k (nk, nao, nao), k_antisym) -> (J, K) -- the contract of lib.jk_multi: plain J and K, the flagged
+    exchange densities antisymmetric.  parts: what the gradient needs again (t_oo, t_vv, tbar, s, n, g_t = G[Tbar], coupling = the
+    (n, n) MO matrix of the g+- terms of Gm)"""
+    no = int(co.shape[1])
+    t_oo, t_vv = difference_density(u, v)
+    tbar = cv @ t_vv @ cv.T + co @ t_oo @ co.T
+    s, n = transition_densities(u, v, co, cv)
+    dms_j = torch.stack([tbar] if triplet else [tbar, s])
+    J, K = jk(dms_j, torch.stack([tbar, s, n]), [0, 0, 1])
+    g_t = J[0] - 0.5 * K[0]
+    g_p = -2.0 * K[1] if triplet else 4.0 * J[1] - 2.0 * K[1]
+    g_m = -2.0 * K[2]
+    c = torch.cat([co, cv], dim=1)
+    gp, gm = c.T @ g_p @ c, c.T @ g_m @ c
+    coupling = torch.cat([gp[:, no:] @ u.T + gm[:, no:] @ v.T, gp[:no, :].T @ u + gm[:no, :].T @ v], dim=1)
+    rhs = 4.0 * (cv.T @ g_t @ co) + coupling[no:, :no] - coupling[:no, no:].T
+    return rhs, dict(t_oo=t_oo, t_vv=t_vv, tbar=tbar, s=s, n=n, g_t=g_t, coupling=coupling)
+
+
+def relaxed_density_mo(t_oo, t_vv, z=None):
+    """P (n, n) in the MO basis: T in its diagonal blocks and, with z (nv, no) the Z-vector, 2 z in the off-diagonal ones"""
+    no, nv = int(t_oo.shape[0]), int(t_vv.shape[0])
+    p = torch.zeros((no + nv, no + nv), dtype=t_oo.dtype, device=t_oo.device)
+    p[:no, :no], p[no:, no:] = t_oo, t_vv
+    if z is not None:
+        p[no:, :no], p[:no, no:] = 2.0 * z, 2.0 * z.T
+    return p
+
+
+def energy_weighted(p, eps, coupling, g_pbar, co, cv):
+    """W (nao, nao) = C 1/4 (Gm + Gm^T) C^T of the module docstring: p the (relaxed) difference density in the MO basis, eps all
+    orbital energies, coupling from `lagrangian_rhs`, g_pbar = G[C p C^T] in the AO basis"""
+    no = int(co.shape[1])
+    c = torch.cat([co, cv], dim=1)
+    gm = 2.0 * eps.unsqueeze(1) * p + coupling
+    gm[:, :no] += 4.0 * (c.T @ g_pbar @ co)
+    return c @ (0.25 * (gm + gm.T)) @ c.T
+
+
+# ------------------------------------------------------------------------------------------------ the calculation
+class ExcitedDensity:
+    """the relaxed difference density of an excited state (detached tensors on the device of the calculation): `dm_mo` (n, n) = P = T + Z
+    in the basis of the canonical orbitals (energy order), `unrelaxed_mo` = T alone, `dm_ao` = the SCF density plus C P C^T;
+    `dipole(unit)`: the relaxed excited-state dipole moment"""
+
+    def __init__(self, dm_mo, unrelaxed_mo, dm_ao, dip_au):
+        self.dm_mo, self.unrelaxed_mo, self.dm_ao, self._dip_au = dm_mo, unrelaxed_mo, dm_ao, dip_au
+
+    def dipole(self, unit="Debye"):
+        """electric dipole moment (3,) of the excited state, nuclear part included: sign and units of `properties.edipole`"""
+        from .properties import _DIPOLE_UNITS, _unit
+        return self._dip_au * _unit(_DIPOLE_UNITS, unit, "dipole")
+
+
+class ExcitedGradient:
+    """what `excited_gradient` returns (detached tensors on the device of the calculation): `gradient` (natm, 3) = d(E_SCF + w) / dR in
+    Hartree / Bohr, `scf` (equal to qc.nuclear_gradient()) and `excitation` = dw / dR; `omega` (one element) and `e_tot` = qc.energy() +
+    omega; `xpy`, `xmy` (nv * no,) as `excitations` returns them (TDA: xmy = xpy = X); `density`: the `ExcitedDensity`; `z_residual` (the
+    relative residual the Z-vector solve stopped at); `state`, `spin`, `tda`"""
+
+    def __init__(self, gradient, scf, omega, e_tot, xpy, xmy, density, z_residual, state, spin, tda):
+        self.gradient, self.scf, self.excitation = gradient, scf, gradient - scf
+        self.omega, self.e_tot, self.xpy, self.xmy, self.density = omega, e_tot, xpy, xmy, density
+        self.z_residual, self.state, self.spin, self.tda = z_residual, int(state), spin, bool(tda)
+
+    def __repr__(self):
+        return "ExcitedGradient(state %d, %s%s, omega=%.8f, max |g| = %.3e, max |dw/dR| = %.3e)" % (
+            self.state, self.spin, ", TDA" if self.tda else "", float(self.omega), float(self.gradient.abs().max()),
+            float(self.excitation.abs().max()))
+
+
+def _refusals(qc, spin):
+    """what `excited_gradient` refuses before anything runs"""
+    from .response import _unsupported
+    if spin not in ("singlet", "triplet"):
+        raise ValueError("excited_gradient: spin is \"singlet\" or \"triplet\", not %r" % (spin,))
+    eng = qc._engine
+    if eng.is_ks:
+        raise NotImplementedError("excited_gradient: a Kohn-Sham reference (hybrid functionals included) is not supported: the TDDFT "
+                                  "Lagrangian needs the third-order exchange-correlation kernel, which is not built")
+    if eng.polarized:
+        raise NotImplementedError("excited_gradient: unrestricted calculations are not supported (the restricted closed-shell "
+                                  "Lagrangian only; the spin-resolved one is not built)")
+    _unsupported(qc)
+
+
+def _gradient(qc, state, spin, tda, nstates, tol, ztol, with_z=True, times=None):
+    """the ExcitedGradient.  with_z=False leaves the Z-vector out of P and W (NOT a gradient of anything:
+    tests/test_gpu_excited_gradient.py shows with it that the relaxation is not skipped); times: a dict that receives the wall time of
+    the stages (tools/gpu_excited_gradient_time.py)"""
+    import time
+    from .gradient import _pulay_densities
+    from .properties import excitations
+    from .response import OrbitalHessian, orbital_hessian
+    h = qc._engine.hamilton
+    dev = h.device
+
+    def clock():
+        if times is not None:
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    scf = qc.nuclear_gradient().detach()     # (raises what nuclear_gradient refuses: a field, vext)
+    tic = clock()
+    ex = excitations(qc, nstates=state + 1 if nstates is None else int(nstates), spin=spin, tda=tda, tol=tol)
+    t_exc = clock() - tic
+    nroots = int(ex.energies.numel())
+    if not 0 <= state < nroots:
+        raise ValueError("excited_gradient: state %d is outside the %d roots found (nstates=%s)" % (state, nroots, nstates))
+    if not ex.residual < tol:
+        raise RuntimeError("excited_gradient: the excitation vectors are not converged (residual %.2e, tol %.1e): the gradient "
+                           "formula needs a stationary excitation energy" % (ex.residual, tol))
+    op = orbital_hessian(qc, spin)           # the operator `excitations` used: its orbitals define the vectors
+    sp = op.spins[0]
+    co, cv, eo, ev = sp.co, sp.cv, sp.eo, sp.ev
+    no, nv, nao = sp.no, sp.nv, int(co.shape[0])
+    xpy = ex.xpy[state]
+    xmy = xpy if ex.xmy is None else ex.xmy[state]
+    u, v = xpy.reshape(nv, no).T, xmy.reshape(nv, no).T
+
+    def jk(dms_j, dms_k, flags):
+        return lib.jk_multi(h._tiles, dms_j.contiguous(), dms_k.contiguous(), h._multi_work(dms_j.shape[0], dms_k.shape[0]), k_antisym=flags)
+
+    tic = clock()
+    rhs, parts = lagrangian_rhs(u, v, co, cv, jk, triplet=spin == "triplet")
+    z, z_residual = None, None
+    # the orbital relaxation is a singlet for either spin; on the orbitals of the vectors (the memoised singlet operator holds the same
+    # ones unless the eigensolver returned the Fock eigenvectors in another phase)
+    ohs = op if spin == "singlet" else orbital_hessian(qc)
+    if not (torch.equal(ohs.spins[0].co, co) and torch.equal(ohs.spins[0].cv, cv)):
+        ohs = OrbitalHessian(qc, orbitals=(torch.cat([co, cv], dim=1), torch.cat([eo, ev])))
+    z = ohs.solve(-rhs.reshape(1, -1), tol=ztol).reshape(nv, no)
+    z_residual = float(ohs.last_residual)
+    t_z = clock() - tic
+    t_mo = relaxed_density_mo(parts["t_oo"], parts["t_vv"])
+    p = relaxed_density_mo(parts["t_oo"], parts["t_vv"], z if with_z else None)
+    c = torch.cat([co, cv], dim=1)
+    pbar = c @ p @ c.T
+    g_pbar = parts["g_t"]
+    if with_z:
+        zbar = (pbar - parts["tbar"]).reshape(1, nao, nao)
+        jz, kz = jk(zbar, zbar, [0])
+        g_pbar = g_pbar + jz[0] - 0.5 * kz[0]
+    w2 = energy_weighted(p, torch.cat([eo, ev]), parts["coupling"], g_pbar, co, cv)
+    _, d_scf, _ = _pulay_densities(qc)
+    d_scf = d_scf.detach()
+    T = lib.cart2sph_matrix(h._tab, dev)
+    sym = lambda m: (0.5 * (T.T @ m @ T + (T.T @ m @ T).T)).contiguous()      # noqa: E731  (exactly symmetric: the gate of eri_grad2)
+    asym = lambda m: (0.5 * (T.T @ m @ T - (T.T @ m @ T).T)).contiguous()    # noqa: E731
+    mol = qc.get_system()
+    natm = len(mol.atomzs)
+    exc = torch.zeros((natm, 3), dtype=torch.float64, device=dev)
+    pc = sym(pbar)
+    lib.int1e_grad(exc, pc, sym(w2), h._tab, h._zs)
+    tic = clock()
+    sc, nc = sym(parts["s"]), asym(parts["n"])
+    lib.eri_grad2(exc, sym(d_scf), pc, 2.0, 2.0, h._tab)                         # separable: 2 eri_grad2(D, Pbar, 1, 1)
+    lib.eri_grad2(exc, sc, sc, 0.0 if spin == "triplet" else 4.0, 4.0, h._tab)   # non-separable, symmetric part
+    lib.eri_grad2(exc, nc, nc, 0.0, 4.0, h._tab)                                 # non-separable, antisymmetric part
+    t_pass = clock() - tic
+    dm_ao = d_scf + pbar
+    r = lib.int1e("r0", h._tab, dev)
+    pos = mol.atompos.detach().to(dev)
+    dip = -torch.einsum("dab,ba->d", r, dm_ao) + torch.einsum("ad,a->d", pos, mol.atomzs.to(pos.dtype).to(dev))
+    if times is not None:
+        times.update(excitations=t_exc, z_vector=t_z, passes=t_pass)
+    omega = ex.energies[state].detach().reshape(1)
+    dens = ExcitedDensity(p, t_mo, dm_ao, dip)
+    return ExcitedGradient(scf + exc, scf, omega, qc.energy().detach().reshape(1) + omega, xpy, xmy, dens, z_residual, state, spin, tda)
+
+
+def excited_gradient(qc, state=0, spin="singlet", tda=False, nstates=None, tol=1e-8, ztol=1e-9):
+    """Analytic nuclear gradient d(E_SCF + w_state) / dR of an excited state of the converged restricted Hartree-Fock calculation `qc`,
+    with its relaxed difference density (module docstring): an `ExcitedGradient`.  tda=True: CIS, False: TDHF; spin: "singlet" or
+    "triplet" excitations; state: index into the roots of `excitations(qc, nstates, spin, tda, tol)` (ascending energies; nstates=None
+    asks for state + 1 of them -- a root is followed by its INDEX, not through crossings); tol: residual norm of the excitation vectors,
+    which must be met (RuntimeError otherwise: the formula needs a stationary w); ztol: relative residual of the Z-vector solve.
+    For what `excitations` and `nuclear_gradient` take, on a Hartree-Fock reference: a Kohn-Sham one (NotImplementedError: the
+    third-order exchange-correlation kernel does not exist) and an unrestricted one are refused.  The two-electron part is three passes
+    of the bilinear derivative kernel (lib.eri_grad2).  Memoised on the converged state per argument set; detached."""
+    assert qc._has_run, "run() the calculation first"
+    state = int(state)
+    if state < 0:
+        raise ValueError("excited_gradient: state must be >= 0, got %d" % state)
+    _refusals(qc, spin)
+    key = ("excited_gradient", state, spin, bool(tda), None if nstates is None else int(nstates), float(tol), float(ztol))
+    return memoised(qc, key, lambda: _gradient(qc, state, spin, bool(tda), nstates, float(tol), float(ztol)))
+
+
+__all__ = ["excited_gradient", "ExcitedGradient", "ExcitedDensity", "difference_density", "transition_densities", "lagrangian_rhs",
+           "relaxed_density_mo", "energy_weighted"]

@@ -80,6 +80,7 @@ def load():
     lib.dqc_cart2sph_matrix.argtypes = [dp, ip, c_int]
     lib.dqc_int1e_grad.argtypes = [c_dp, c_dp, c_dp] + tab + [dp, c_vp]
     lib.dqc_eri_grad.argtypes = [c_dp, c_dp, ctypes.c_double, ctypes.c_double] + tab + [c_vp]
+    lib.dqc_eri_grad2.argtypes = [c_dp, c_dp, c_dp, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double] + tab + [c_vp]
     lib.dqc_int1e_grad_basis.argtypes = [c_dp, c_dp, c_dp] + tab + [dp, c_vp]
     lib.dqc_eri_grad_basis.argtypes = [c_dp, c_dp, ctypes.c_double, ctypes.c_double] + tab + [c_vp]
     lib.dqc_int1e_potential.argtypes = [c_dp, c_dp, c_dp, c_int] + tab + [c_vp]
@@ -626,6 +627,42 @@ def eri_grad(grad, dcart, kscale, tab, jscale=1.0):
     """grad (natm, 3) += two-electron derivative term  sum (d_A a b|c d) [2 jscale D_ab D_cd - kscale D_ac D_bd]"""
     with _on(grad.device) as st_:
         _check(load().dqc_eri_grad(_ptr(grad), _ptr(dcart), float(jscale), float(kscale), *tab.args(), st_), "dqc_eri_grad")
+    return grad
+
+
+def _parity(m):
+    """+1 for an exactly symmetric matrix, -1 for an exactly antisymmetric one (a zero matrix counts as symmetric), else 0"""
+    t = m.t()
+    return 1 if torch.equal(m, t) else (-1 if torch.equal(m, -t) else 0)
+
+
+def eri_grad2(grad, acart, bcart, jscale, kscale, tab):
+    """grad (natm, 3) += sum_{a on atom A} sum_bcd (d_A a b|c d) [jscale (A_ab B_cd + B_ab A_cd) - kscale / 2 (A_ac B_bd + B_ac A_bd)]
+    (csrc/grad.hip: dqc_eri_grad2, the ERI_OUT_GRAD2 kernels of csrc/grad2.hip): the symmetric bilinear form whose diagonal is
+    `eri_grad` -- eri_grad2(D, D, j, k) = eri_grad(D, k, jscale=j), and Q(D + P) - Q(D) - Q(P) = 2 eri_grad2(D, P) for the quadratic
+    form Q.  acart, bcart (ncart, ncart): contiguous float64 Cartesian-basis matrices on the device of grad, both EXACTLY symmetric
+    or both EXACTLY antisymmetric (symmetrise explicitly: torch.equal with +- the transpose is the test), the antisymmetric pair
+    with jscale == 0.  Everything is checked before anything is uploaded or launched: DqcAmdError."""
+    ncart = int(((tab.bas[:, 1].astype(np.int64) + 1) * (tab.bas[:, 1].astype(np.int64) + 2) // 2).sum())
+    if tuple(grad.shape) != (tab.natm, 3) or grad.dtype != torch.float64 or not grad.is_contiguous():
+        raise DqcAmdError("eri_grad2: grad must be a contiguous float64 (%d, 3) tensor, got %s %s" % (tab.natm, grad.dtype, tuple(grad.shape)))
+    for name, m in (("A", acart), ("B", bcart)):
+        if tuple(m.shape) != (ncart, ncart) or m.dtype != torch.float64 or not m.is_contiguous() or m.device != grad.device:
+            raise DqcAmdError("eri_grad2: %s must be a contiguous float64 (%d, %d) tensor on the device of grad (the Cartesian "
+                              "functions of the table), got %s %s on %s" % (name, ncart, ncart, m.dtype, tuple(m.shape), m.device))
+    pa, pb = _parity(acart), _parity(bcart)
+    if pa == 0 or pb == 0:
+        raise DqcAmdError("eri_grad2: %s is neither exactly symmetric nor exactly antisymmetric (symmetrise it explicitly: "
+                          "(M + M^T) / 2 or (M - M^T) / 2)" % ("A" if pa == 0 else "B"))
+    if pa != pb and bool(acart.any()) and bool(bcart.any()):
+        raise DqcAmdError("eri_grad2: one matrix is symmetric and the other antisymmetric (the bilinear form needs a same-parity pair)")
+    if pa != pb:  # (a zero matrix is both: it takes the parity of its partner)
+        pa = pb = pb if bool(bcart.any()) else pa
+    if pa == -1 and float(jscale) != 0.0:
+        raise DqcAmdError("eri_grad2: an antisymmetric pair has no Coulomb part (jscale must be 0)")
+    with _on(grad.device) as st_:
+        _check(load().dqc_eri_grad2(_ptr(grad), _ptr(acart), _ptr(bcart), ncart, pa, pb, float(jscale), float(kscale), *tab.args(), st_),
+               "dqc_eri_grad2")
     return grad
 
 

@@ -385,6 +385,20 @@ int dqc_int1e_grad(double *d_grad, const double *d_dcart, const double *d_wcart,
                    const int *bas, int nbas, const double *env, int nenv, const double *zs, void *stream);
 int dqc_eri_grad(double *d_grad, const double *d_dcart, double jscale, double kscale, const int *atm, int natm, const int *bas,
                  int nbas, const double *env, int nenv, void *stream);
+/* dqc_eri_grad as the symmetric BILINEAR form of two Cartesian matrices (the two-particle densities of an excited-state Lagrangian
+ * are products of different matrices: the SCF density with a relaxed difference density, transition densities with themselves):
+ *   d_grad += sum_{a in A} sum_bcd (d_A a b|c d) [jscale (A_ab B_cd + B_ab A_cd) - kscale / 2 (A_ac B_bd + B_ac A_bd)]
+ * so that dqc_eri_grad2(D, D, j, k) = dqc_eri_grad(D, j, k), and Q(D + P) - Q(D) - Q(P) = 2 dqc_eri_grad2(D, P) for the quadratic form
+ * Q of dqc_eri_grad.  d_acart, d_bcart (ncart, ncart), ncart the caller's dimension (refused unless it is dqc_ncart of the table);
+ * parity_a, parity_b: +1 for an EXACTLY symmetric matrix, -1 for an exactly antisymmetric one, verified by the caller (the matrices
+ * are device memory; dqc_amd.lib.eri_grad2 tests torch.equal with +- the transpose).  "Derivative on the first index over all
+ * ordered index tuples" is a quarter of the derivative of sum (ab|cd) Gamma_abcd only when Gamma is invariant under (ab) <-> (cd)
+ * and under the simultaneous swap a <-> b, c <-> d: a same-parity pair.  Refused with DQC_EINVAL before anything is uploaded or
+ * launched: a wrong ncart, a parity other than +-1, a mixed-parity pair, an antisymmetric pair with jscale != 0 (its Coulomb part
+ * vanishes identically).  ADDS into d_grad (natm, 3) and synchronises the stream.  Shells up to g: the ERI_OUT_GRAD2 instantiations
+ * (csrc/grad2.hip); the ERI_OUT_GRAD and ERI_OUT_GRAD3 kernels of the other entry points are not changed by them. */
+int dqc_eri_grad2(double *d_grad, const double *d_acart, const double *d_bcart, int ncart, int parity_a, int parity_b, double jscale,
+                  double kscale, const int *atm, int natm, const int *bas, int nbas, const double *env, int nenv, void *stream);
 /* the same two contractions differentiated by the BASIS-SET parameters instead of the centres: theta = the exponent alpha_p or
  * the stored (normalised) coefficient c_p of one primitive.  For a shell a = sum_p c_p g_p:  d a / d c_p = g_p,
  * d a / d alpha_p = -c_p r_A^2 g_p (an l + 2 Cartesian shell), so the Pulay terms are the same shell-pair and shell-quartet

@@ -1,10 +1,11 @@
 """Register table of the gradient instantiations of the Rys quartet kernels, from code-object metadata alone.
-usage: python tools/grad_kernel_registers.py grad.o [grad_before.o] [out.txt]        (CPU only)
+usage: python tools/grad_kernel_registers.py grad.o [grad_before.o] [grad2.o] [out.txt]        (CPU only)
 
 Unbundles the gfx950 code object of a compiled csrc/grad.hip (dqc_amd/csrc/_obj/grad.o after a build) and reads, for every
 eri_kernel<LA, LB, LC, LD, MODE> and eri_hl_kernel<TPQ, MODE> in it, the VGPR count, SGPR count and private-segment size from the
 AMDGPU metadata note.  With a second object (the same source compiled at another commit) the ERI_OUT_GRAD rows (MODE 3) of the two are
-compared and the differing ones listed; the ERI_OUT_GRAD3 rows (MODE 7) are listed beside the ERI_OUT_GRAD row of the same class."""
+compared and the differing ones listed, and so are the ERI_OUT_GRAD3 rows (MODE 7); those are listed beside the ERI_OUT_GRAD row of the
+same class, with the ERI_OUT_GRAD2 rows (MODE 8) of csrc/grad2.hip when its object (a file named grad2*.o) is given too."""
 import os
 import re
 import subprocess
@@ -31,7 +32,7 @@ def kernels(obj):
         targs = tuple(int(x) for x in re.findall(r"Li(\d+)E", m.group(1)))
         hl = "eri_hl_kernel" in name
         mode = targs[1] if hl else targs[4]
-        if mode not in (3, 7):
+        if mode not in (3, 7, 8):
             continue
         g = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, e).group(1))  # noqa: E731
         out[("hl" if hl else "eri", targs)] = (g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"))
@@ -50,9 +51,12 @@ def with_mode(key, mode):
 
 def main():
     args = sys.argv[1:]
-    objs = [a for a in args if a.endswith(".o")]
+    second = [a for a in args if a.endswith(".o") and os.path.basename(a).startswith("grad2")]
+    objs = [a for a in args if a.endswith(".o") and a not in second]
     outs = [a for a in args if not a.endswith(".o")]
     now = kernels(objs[0])
+    for a in second:
+        now.update(kernels(a))
     lines = []
     grad = sorted(k for k in now if with_mode(k, 3) == k)
     if len(objs) > 1:
@@ -62,10 +66,19 @@ def main():
         lines.append("ERI_OUT_GRAD instantiations: %d before, %d now, %d differ in (vgpr, sgpr, private segment)" % (len(gb), len(grad), len(changed)))
         for k in changed:
             lines.append("  DIFFERS %-12s before %s now %s" % (label(k), before.get(k), now.get(k)))
-    lines.append("%-12s %-20s %-20s" % ("class", "GRAD vgpr/sgpr/priv", "GRAD3 vgpr/sgpr/priv"))
+        g3b = sorted(k for k in before if with_mode(k, 7) == k)
+        g3n = sorted(k for k in now if with_mode(k, 7) == k)
+        changed3 = [k for k in g3n if before.get(k) != now[k]] + [k for k in g3b if k not in now]
+        lines.append("ERI_OUT_GRAD3 instantiations: %d before, %d now, %d differ in (vgpr, sgpr, private segment)" % (len(g3b), len(g3n), len(changed3)))
+        for k in changed3:
+            lines.append("  DIFFERS %-12s before %s now %s" % (label(k), before.get(k), now.get(k)))
+    cell = lambda k: "%d / %d / %d" % now[k] if k in now else "-"  # noqa: E731
+    priv = [k for k in grad if with_mode(k, 8) in now and now[with_mode(k, 8)][2] > 0 and now[k][2] == 0]
+    lines.append("ERI_OUT_GRAD2 instantiations with a private segment where the ERI_OUT_GRAD one has none: %d%s"
+                 % (len(priv), "".join(" " + label(k) for k in priv)))
+    lines.append("%-12s %-20s %-20s %-20s" % ("class", "GRAD vgpr/sgpr/priv", "GRAD3 vgpr/sgpr/priv", "GRAD2 vgpr/sgpr/priv"))
     for k in grad:
-        k3 = with_mode(k, 7)
-        lines.append("%-12s %-20s %-20s" % (label(k), "%d / %d / %d" % now[k], "%d / %d / %d" % now[k3] if k3 in now else "-"))
+        lines.append("%-12s %-20s %-20s %-20s" % (label(k), cell(k), cell(with_mode(k, 7)), cell(with_mode(k, 8))))
     txt = "\n".join(lines)
     print(txt)
     if outs:
