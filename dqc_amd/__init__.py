@@ -12,7 +12,7 @@ from .properties import edipole, equadrupole, optimal_geometry, hessian_pos, vib
 from .properties import lowest_eival_orb_hessian, is_orb_min, polarizability, excitations, Excitations  # noqa: F401
 from .response import OrbitalHessian  # noqa: F401
 from .mp2 import mp2, MP2, mp2_density, MP2Density, mp2_gradient, MP2Gradient  # noqa: F401
-from .excited import excited_gradient, ExcitedGradient, ExcitedDensity  # noqa: F401
+from .excited import excited_gradient, tddft_gradient, ExcitedGradient, ExcitedDensity  # noqa: F401
 from .rpa import rpa, RPA  # noqa: F401
 from .gw import gw, GW  # noqa: F401
 from .bse import bse, BSE  # noqa: F401

@@ -891,6 +891,64 @@ __global__ __launch_bounds__(256) void xc_fxc_kernel(double *__restrict__ dvrho,
     }
 }
 
+// Third functional derivatives (the kernel of the TDDFT excited-state gradient, dqc_amd/excited.py): the SECOND-order change of the
+// potentials of xc_kernel under two responses (d rho_1, grad d rho_1), (d rho_2, grad d rho_2), restricted closed shell, for npair
+// pairs.  With d sigma_k = 2 grad rho . grad d rho_k and d2 sigma = 2 grad d rho_1 . grad d rho_2 (the density is linear in the
+// response, sigma is not):
+//   d2 v_rho              = e_rrr dr1 dr2 + e_rrs (dr1 ds2 + ds1 dr2) + e_rss ds1 ds2 + e_rs d2s
+//   d2 v_sigma            = e_rrs dr1 dr2 + e_rss (dr1 ds2 + ds1 dr2) + e_sss ds1 ds2 + e_ss d2s
+//   d2 (2 v_sigma grad rho) = 2 d2 v_sigma grad rho + 2 (e_rs dr1 + e_ss ds1) grad d rho_2 + 2 (e_rs dr2 + e_ss ds2) grad d rho_1
+// The functional bodies run on DualT<Tan2>: both tangents seeded on rho give (e_rr, e_rs) in the tangents and (e_rrr, e_rrs) in the
+// mixed tangent of the gradient slots, both seeded on sigma (e_rs, e_ss) and (e_rss, e_sss) -- two evaluations per point and term,
+// one for an LDA term, built once and contracted with the npair pairs.  A number is 12 doubles: the two seedings stay in a loop
+// that is NOT unrolled (the polarised f_xc kernel spilled when its direction loop was), and the functional is fixed at compile
+// time as in xc_fxc_kernel.  Same cutoff: nothing is added where rho <= 1e-15.
+template <int ID>
+__global__ __launch_bounds__(256) void xc_kxc_kernel(double *__restrict__ d2vrho, double *__restrict__ d2vgrad, const double *__restrict__ rho,
+                                                     const double *__restrict__ grho, const double *__restrict__ drho1,
+                                                     const double *__restrict__ dgrho1, const double *__restrict__ drho2,
+                                                     const double *__restrict__ dgrho2, int n, int npair, int id_rt, double coef) {
+    constexpr bool GGA = ID < 0 || xc_id_is_gga(ID);
+    constexpr bool EXT = ID < 0 || xc_id_is_ext(ID);
+    const int id = ID < 0 ? id_rt : ID;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const double r = rho[i];
+        if (!(r > 1e-15)) continue;
+        double g[3] = {0.0, 0.0, 0.0};
+        if constexpr (GGA)
+            for (int k = 0; k < 3; k++) g[k] = grho[(size_t)k * n + i];
+        const double sigma = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
+        double ers = 0.0, ess = 0.0, errr = 0.0, errs = 0.0, erss = 0.0, esss = 0.0;  // (scalars, not arrays indexed by dir: no scratch)
+#pragma unroll 1
+        for (int dir = 0; dir < (GGA ? 2 : 1); dir++) {
+            const double tr = dir == 0 ? 1.0 : 0.0, ts = 1.0 - tr;
+            const DualT<Tan2> dr{Tan2{r, tr, tr, 0.0}, Tan2{1.0, 0.0, 0.0, 0.0}, Tan2{0.0, 0.0, 0.0, 0.0}};
+            const DualT<Tan2> ds{Tan2{sigma, ts, ts, 0.0}, Tan2{0.0, 0.0, 0.0, 0.0}, Tan2{1.0, 0.0, 0.0, 0.0}};
+            const DualT<Tan2> f = f_lda_gga<EXT, Tan2>(id, dr, ds);
+            if (dir == 0) { ers = f.s.t1; errr = f.r.t12; errs = f.s.t12; }
+            else { ess = f.s.t1; erss = f.r.t12; esss = f.s.t12; }
+        }
+        for (int v = 0; v < npair; v++) {
+            const double dr1 = drho1[(size_t)v * n + i], dr2 = drho2[(size_t)v * n + i];
+            if constexpr (GGA) {
+                const double *p1 = dgrho1 + (size_t)v * 3 * n + i, *p2 = dgrho2 + (size_t)v * 3 * n + i;
+                double *out = d2vgrad + (size_t)v * 3 * n + i;
+                const double a1[3] = {p1[0], p1[n], p1[2 * (size_t)n]}, a2[3] = {p2[0], p2[n], p2[2 * (size_t)n]};
+                const double ds1 = 2.0 * (g[0] * a1[0] + g[1] * a1[1] + g[2] * a1[2]);
+                const double ds2 = 2.0 * (g[0] * a2[0] + g[1] * a2[1] + g[2] * a2[2]);
+                const double dds = 2.0 * (a1[0] * a2[0] + a1[1] * a2[1] + a1[2] * a2[2]);
+                const double rr = dr1 * dr2, rs = dr1 * ds2 + ds1 * dr2, ss = ds1 * ds2;
+                d2vrho[(size_t)v * n + i] += coef * (errr * rr + errs * rs + erss * ss + ers * dds);
+                const double d2vs = errs * rr + erss * rs + esss * ss + ess * dds;
+                const double dvs1 = ers * dr1 + ess * ds1, dvs2 = ers * dr2 + ess * ds2;
+                for (int k = 0; k < 3; k++) out[(size_t)k * n] += coef * (2.0 * d2vs * g[k] + 2.0 * (dvs1 * a2[k] + dvs2 * a1[k]));
+            } else {
+                d2vrho[(size_t)v * n + i] += coef * (errr * (dr1 * dr2));
+            }
+        }
+    }
+}
+
 // TRIPLET: the spin-flip response of a CLOSED shell.  ru_ / gu_ / dru_ / dgu_ then hold the TOTAL rho, grad rho, d rho, grad d rho
 // (the restricted kernel's inputs; the *_d pointers are not read): the ground state is rho_u = rho_d = rho / 2, the response
 // d rho_u = -d rho_d = d rho / 2, halved in registers, and only the spin-up potentials dvu / dvgu are written (d v_d = -d v_u).
@@ -1034,6 +1092,32 @@ extern "C" int dqc_xc_eval_fxc(double *d_dvrho, double *d_dvgrad, const double *
         DQC_FXC_IDS(X)
 #undef X
         default: hipLaunchKernelGGL(xc_fxc_kernel<-1>, dim3(blocks), dim3(256), 0, st, d_dvrho, d_dvgrad, d_rho, d_grho, d_drho, d_dgrho, n, nvec, ids[t], coefs[t]); break;
+        }
+        DQC_CHECK_LAUNCH();
+    }
+    return DQC_OK;
+}
+
+extern "C" int dqc_xc_eval_kxc(double *d_d2vrho, double *d_d2vgrad, const double *d_rho, const double *d_grho, const double *d_drho1,
+                               const double *d_dgrho1, const double *d_drho2, const double *d_dgrho2, int n, int npair, const int *ids,
+                               const double *coefs, int nterm, void *stream) {
+    // third order, restricted: outputs (npair, n) and (npair, 3, n) in the layout of dqc_xc_eval_fxc, zeroed here; the gates of the
+    // second-order entries (fxc_check_terms) before any launch
+    using namespace dqc;
+    const bool grad = d_grho && d_dgrho1 && d_dgrho2 && d_d2vgrad;
+    if (int rc = fxc_check_terms("dqc_xc_eval_kxc", ids, nterm, grad, npair)) return rc;
+    if (n <= 0 || npair == 0) return DQC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DQC_HIP(hipMemsetAsync(d_d2vrho, 0, sizeof(double) * (size_t)npair * n, st));
+    if (d_d2vgrad) DQC_HIP(hipMemsetAsync(d_d2vgrad, 0, sizeof(double) * (size_t)npair * 3 * n, st));
+    int blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    for (int t = 0; t < nterm; t++) {
+        switch (ids[t]) {
+#define X(ID_) case ID_: hipLaunchKernelGGL(xc_kxc_kernel<ID_>, dim3(blocks), dim3(256), 0, st, d_d2vrho, d_d2vgrad, d_rho, d_grho, d_drho1, d_dgrho1, d_drho2, d_dgrho2, n, npair, ids[t], coefs[t]); break;
+        DQC_FXC_IDS(X)
+#undef X
+        default: hipLaunchKernelGGL(xc_kxc_kernel<-1>, dim3(blocks), dim3(256), 0, st, d_d2vrho, d_d2vgrad, d_rho, d_grho, d_drho1, d_dgrho1, d_drho2, d_dgrho2, n, npair, ids[t], coefs[t]); break;
         }
         DQC_CHECK_LAUNCH();
     }

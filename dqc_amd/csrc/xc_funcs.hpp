@@ -50,6 +50,43 @@ DQC_DEV Tan s_atan(Tan a) { return {atan(a.v), a.t / (1.0 + a.v * a.v)}; }
 DQC_DEV Tan s_asinh(Tan a) { return {asinh(a.v), a.t / sqrt(1.0 + a.v * a.v)}; }
 DQC_DEV Tan s_pow(Tan a, double e) { const double f = pow(a.v, e); return {f, a.t * e * f / a.v}; }
 
+// `Tan2` (value, TWO tangents and their mixed second tangent) for the third-order kernel of xc.hip: with both tangents seeded on one
+// input the mixed tangent of the gradient slots of a DualT<Tan2> is a third derivative of e(rho, sigma), and the plain tangents are the
+// second derivatives next to it.  An elementary function f maps a to (f, f' a.t1, f' a.t2, f'' a.t1 a.t2 + f' a.t12): `tan2_chain`.
+struct Tan2 {  // value, tangent 1, tangent 2, mixed second tangent
+    double v, t1, t2, t12;
+};
+DQC_DEV Tan2 tan2_chain(Tan2 a, double f, double d1, double d2) { return {f, d1 * a.t1, d1 * a.t2, d2 * a.t1 * a.t2 + d1 * a.t12}; }
+DQC_DEV Tan2 operator+(Tan2 a, Tan2 b) { return {a.v + b.v, a.t1 + b.t1, a.t2 + b.t2, a.t12 + b.t12}; }
+DQC_DEV Tan2 operator-(Tan2 a, Tan2 b) { return {a.v - b.v, a.t1 - b.t1, a.t2 - b.t2, a.t12 - b.t12}; }
+DQC_DEV Tan2 operator*(Tan2 a, Tan2 b) {
+    return {a.v * b.v, a.t1 * b.v + a.v * b.t1, a.t2 * b.v + a.v * b.t2, a.t12 * b.v + a.t1 * b.t2 + a.t2 * b.t1 + a.v * b.t12};
+}
+DQC_DEV Tan2 operator/(Tan2 a, Tan2 b) {  // a = q b differentiated twice
+    const double ib = 1.0 / b.v, q = a.v * ib, q1 = (a.t1 - q * b.t1) * ib, q2 = (a.t2 - q * b.t2) * ib;
+    return {q, q1, q2, (a.t12 - q1 * b.t2 - q2 * b.t1 - q * b.t12) * ib};
+}
+DQC_DEV Tan2 operator-(Tan2 a) { return {-a.v, -a.t1, -a.t2, -a.t12}; }
+DQC_DEV Tan2 operator+(double a, Tan2 b) { return {a + b.v, b.t1, b.t2, b.t12}; }
+DQC_DEV Tan2 operator+(Tan2 a, double b) { return {a.v + b, a.t1, a.t2, a.t12}; }
+DQC_DEV Tan2 operator-(double a, Tan2 b) { return {a - b.v, -b.t1, -b.t2, -b.t12}; }
+DQC_DEV Tan2 operator-(Tan2 a, double b) { return {a.v - b, a.t1, a.t2, a.t12}; }
+DQC_DEV Tan2 operator*(double a, Tan2 b) { return {a * b.v, a * b.t1, a * b.t2, a * b.t12}; }
+DQC_DEV Tan2 operator*(Tan2 a, double b) { return {a.v * b, a.t1 * b, a.t2 * b, a.t12 * b}; }
+DQC_DEV Tan2 operator/(Tan2 a, double b) { const double ib = 1.0 / b; return {a.v * ib, a.t1 * ib, a.t2 * ib, a.t12 * ib}; }
+DQC_DEV Tan2 operator/(double a, Tan2 b) { return Tan2{a, 0.0, 0.0, 0.0} / b; }
+DQC_DEV double s_val(Tan2 a) { return a.v; }
+template <> DQC_DEV Tan2 s_const<Tan2>(double c) { return {c, 0.0, 0.0, 0.0}; }
+DQC_DEV Tan2 s_cbrt(Tan2 a) { const double q = cbrt(a.v), d = q / (3.0 * a.v); return tan2_chain(a, q, d, -2.0 * d / (3.0 * a.v)); }
+DQC_DEV Tan2 s_sqrt(Tan2 a) { const double q = sqrt(a.v), d = 0.5 / q; return tan2_chain(a, q, d, -0.5 * d / a.v); }
+DQC_DEV Tan2 s_log(Tan2 a) { const double d = 1.0 / a.v; return tan2_chain(a, log(a.v), d, -d * d); }
+DQC_DEV Tan2 s_log1p(Tan2 a) { const double d = 1.0 / (1.0 + a.v); return tan2_chain(a, log1p(a.v), d, -d * d); }
+DQC_DEV Tan2 s_exp(Tan2 a) { const double e = exp(a.v); return tan2_chain(a, e, e, e); }
+DQC_DEV Tan2 s_expm1(Tan2 a) { const double e = exp(a.v); return tan2_chain(a, expm1(a.v), e, e); }
+DQC_DEV Tan2 s_atan(Tan2 a) { const double d = 1.0 / (1.0 + a.v * a.v); return tan2_chain(a, atan(a.v), d, -2.0 * a.v * d * d); }
+DQC_DEV Tan2 s_asinh(Tan2 a) { const double d = 1.0 / sqrt(1.0 + a.v * a.v); return tan2_chain(a, asinh(a.v), d, -a.v * d * d * d); }
+DQC_DEV Tan2 s_pow(Tan2 a, double e) { const double f = pow(a.v, e), d = e * f / a.v; return tan2_chain(a, f, d, (e - 1.0) * d / a.v); }
+
 template <class S>
 struct DualT {  // value, d/drho, d/dsigma
     S v, r, s;
@@ -88,6 +125,19 @@ DQC_DEV S xasinhx_val(S y, S &dg) {
     dg = 0.5 * (ax + 1.0 / s_sqrt(1.0 + y));
     return y * ax;
 }
+// Tan2: the quotient asinh(x) / x differentiated twice in y through x = sqrt(y) cancels to eps / x^4 of its value, so the series takes
+// over at x = 1e-2 already and runs to y^6 (the first term left out, y^7, has a second derivative below 1e-22 there)
+DQC_DEV Tan2 xasinhx_val(Tan2 y, Tan2 &dg) {
+    Tan2 ax;
+    if (y.v > 1e-4) {
+        const Tan2 x = s_sqrt(y);
+        ax = s_asinh(x) / x;
+    } else {
+        ax = 1.0 + y * (-1.0 / 6.0 + y * (3.0 / 40.0 + y * (-5.0 / 112.0 + y * (35.0 / 1152.0 + y * (-63.0 / 2816.0 + y * (231.0 / 13312.0))))));
+    }
+    dg = 0.5 * (ax + 1.0 / s_sqrt(1.0 + y));
+    return y * ax;
+}
 template <class S> DQC_DEV DualT<S> dxasinhx(DualT<S> y) { S dg; const S v = xasinhx_val(y.v, dg); return {v, y.r * dg, y.s * dg}; }
 
 constexpr double kPi = 3.14159265358979323846;
@@ -107,6 +157,7 @@ template <class S> DQC_DEV DualT<S> n_floor(DualT<S> a, double lo) { return s_va
 // the VALUE raised to lo, the derivatives kept: for a variable that enters through its square root and linearly as well (P86)
 DQC_DEV void s_set_val(double &a, double v) { a = v; }
 DQC_DEV void s_set_val(Tan &a, double v) { a.v = v; }
+DQC_DEV void s_set_val(Tan2 &a, double v) { a.v = v; }
 template <class S> DQC_DEV DualT<S> n_floor_val(DualT<S> a, double lo) { if (s_val(a.v) < lo) s_set_val(a.v, lo); return a; }
 
 // ---------------------------------------------------------------------------------------------

@@ -350,6 +350,71 @@ def _xc_gradient(eng, d_aos):
     return g + torch.autograd.grad(loss, pos)[0]
 
 
+def _full_grid(h, x):
+    """per-point rows on the live points of the Hamiltonian -> rows on the caller's grid (zero elsewhere), as in _xc_gradient"""
+    live = getattr(h, "live_index", None)
+    if live is None:
+        return x
+    o = torch.zeros((h.ngrid_full,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    o[live] = x
+    return o
+
+
+def _xc_potential_gradient(eng, ao, m_ao, vrho, u, fused=None):
+    """G(M; a, b) = sum_g w [a d rho_M + b . d grad rho_M] at fixed M (natm, 3), the AO centres and the grid points riding on their
+    atoms: the terms (ii) and (iii) of the module docstring for ANY symmetric AO matrix M = m_ao and ANY per-point pair a = vrho
+    (ngrid,), b = u (3, ngrid) or None (LDA) -- with M = D and the ground-state potentials they are those of _xc_gradient.  ao: the
+    deriv-3 AO array (10, ngrid, ld) for a GGA pair, deriv-1 (4, ngrid, ld) for LDA, evaluated once by the caller for all its calls
+    (dqc_amd/excited.py makes three).  fused: None = the one-pass kernel dqc_grid_xc_gradient_terms for a GGA pair with nao <= 512
+    and the torch passes otherwise, as _xc_gradient chooses; False forces the torch passes."""
+    h = eng.hamilton
+    mol = eng.get_system()
+    dev = h.device
+    nao, ld = h._nao_ao, h._ld
+    gga = u is not None
+    w = h.dvolume
+    lda = ao.shape[-1]
+    dq = lib.pad_matrix(m_ao, ld)[:lda, :lda]
+    b = ao[0] @ dq
+    c = [ao[1 + i] @ dq for i in range(3)] if gga else None
+    if fused is None:
+        fused = gga and ao.shape[0] == 10 and nao <= 512
+    if fused:
+        grho = torch.stack([_grad_rho(ao, b, j) for j in range(3)])
+        q, per_ao = lib.grid_xc_gradient_terms(ao, nao, b, c, w, vrho, u, grho, None)
+    else:
+        q = torch.empty((h.rgrid.shape[0], 3), dtype=torch.float64, device=dev)
+        per_ao = torch.empty((nao, 3), dtype=torch.float64, device=dev)
+        t1 = vrho.unsqueeze(-1) * b
+        if gga:
+            t1 = t1 + sum(u[i].unsqueeze(-1) * c[i] for i in range(3))
+            ugphi = sum(u[i].unsqueeze(-1) * ao[1 + i] for i in range(3))      # u . grad phi
+        for j in range(3):
+            if gga:
+                bsj = b * sum(u[i].unsqueeze(-1) * ao[_HESS[i][j]] for i in range(3))
+                q[:, j] = w * (vrho * _grad_rho(ao, b, j) + 2.0 * (bsj.sum(1) + (c[j] * ugphi).sum(1)))
+                per_ao[:, j] = ((ao[1 + j] * t1 + bsj) * w.unsqueeze(-1)).sum(0)[:nao]
+            else:
+                q[:, j] = w * vrho * _grad_rho(ao, b, j)
+                per_ao[:, j] = (ao[1 + j] * t1 * w.unsqueeze(-1)).sum(0)[:nao]
+    g = _sum_by_owner(mol, _full_grid(h, q))                 # (ii)
+    g.index_add_(0, _ao_owner(h, dev), -2.0 * per_ao)        # (iii)
+    return g
+
+
+def _xc_weight_gradient(eng, per_point):
+    """sum_g (d w_g / dR) x_g (natm, 3) for a fixed per-point factor x = per_point (ngrid,) on the live points: torch autograd through
+    the grid construction, the term (i) of _xc_gradient (which has the energy density as x)"""
+    h = eng.hamilton
+    mol = eng.get_system()
+    dev = h.device
+    with torch.enable_grad():  # (a caller may run under no_grad: the derivative is by the positions of this function's own copy)
+        pos = mol.atompos.detach().to(dtype=torch.float64, device=dev).clone().requires_grad_(True)
+        grid = get_predefined_grid(mol._grid_inp, mol.atomzs.tolist(), pos, dtype=torch.float64, device=dev)
+        loss = (grid.get_dvolume() * _full_grid(h, per_point.detach())).sum()
+        return torch.autograd.grad(loss, pos)[0]
+
+
 def _grad_rho(ao, b, j):
     """d_j rho = 2 sum_mu (D phi)_mu d_j phi_mu"""
     return 2.0 * (b * ao[1 + j]).sum(1)

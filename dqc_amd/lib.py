@@ -125,6 +125,7 @@ def load():
     lib.dqc_xc_eval_quad.argtypes = [c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_pol.argtypes = [c_dp] * 9 + [c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_fxc.argtypes = [c_dp] * 6 + [c_int, c_int, ip, dp, c_int, c_vp]
+    lib.dqc_xc_eval_kxc.argtypes = [c_dp] * 8 + [c_int, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_fxc_pol.argtypes = [c_dp] * 12 + [c_int, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_fxc_triplet.argtypes = [c_dp] * 6 + [c_int, c_int, ip, dp, c_int, c_vp]
     lib.dqc_xc_eval_mgga.argtypes = [c_dp] * 7 + [c_int, ip, dp, c_int, c_vp]
@@ -1298,6 +1299,26 @@ def xc_eval_fxc(terms, rho, grho, drho, dgrho):
         _check(load().dqc_xc_eval_fxc(_ptr(dv), _ptr(dvg), _ptr(rho), _ptr(grho), _ptr(drho), _ptr(dgrho), n, nvec, ids, cfs,
                                       len(terms), st_), "dqc_xc_eval_fxc")
     return dv, dvg
+
+
+def xc_eval_kxc(terms, rho, grho, drho1, dgrho1, drho2, dgrho2):
+    """third functional derivatives contracted with npair PAIRS of responses (restricted closed shell): rho (n,), grho (3, n) or None
+    (LDA); drho1, drho2 (npair, n), dgrho1, dgrho2 (npair, 3, n) or None -> d2vrho (npair, n), d2vgrad (npair, 3, n) or None = the
+    second-order change of (v_rho, 2 vsigma grad rho), the layout of xc_eval_fxc; symmetric in the two responses"""
+    ids, cfs = _fxc_terms(terms, "xc_eval_kxc")
+    npair, n = drho1.shape
+    gga = grho is not None and dgrho1 is not None and dgrho2 is not None
+    if tuple(rho.shape) != (n,) or tuple(drho2.shape) != (npair, n) or (gga and not (
+            tuple(grho.shape) == (3, n) and tuple(dgrho1.shape) == (npair, 3, n) and tuple(dgrho2.shape) == (npair, 3, n))):
+        raise DqcAmdError("xc_eval_kxc: rho (n,), grho (3, n), drho1 / drho2 (npair, n), dgrho1 / dgrho2 (npair, 3, n) do not fit together")
+    rho, drho1, drho2 = rho.contiguous(), drho1.contiguous(), drho2.contiguous()
+    grho, dgrho1, dgrho2 = (grho.contiguous(), dgrho1.contiguous(), dgrho2.contiguous()) if gga else (None, None, None)
+    d2v = torch.empty_like(drho1)
+    d2vg = torch.empty((npair, 3, n), dtype=torch.float64, device=rho.device) if gga else None
+    with _on(rho.device) as st_:
+        _check(load().dqc_xc_eval_kxc(_ptr(d2v), _ptr(d2vg), _ptr(rho), _ptr(grho), _ptr(drho1), _ptr(dgrho1), _ptr(drho2), _ptr(dgrho2),
+                                      n, npair, ids, cfs, len(terms), st_), "dqc_xc_eval_kxc")
+    return d2v, d2vg
 
 
 def xc_eval_fxc_triplet(terms, rho, grho, drho, dgrho):

@@ -242,6 +242,14 @@ int dqc_xc_eval_mgga(double *d_edens, double *d_vrho, double *d_vgrad, double *d
  * (a DQC_XC_MGGA_* id is DQC_EINVAL). */
 int dqc_xc_eval_fxc(double *d_dvrho, double *d_dvgrad, const double *d_rho, const double *d_grho, const double *d_drho,
                     const double *d_dgrho, int n, int nvec, const int *ids, const double *coefs, int nterm, void *stream);
+/* THIRD functional derivatives, restricted closed shell (the kernel of the TDDFT excited-state gradient): the second-order change
+ * of the same potentials under npair PAIRS of responses, d_drho1 / d_drho2 (npair, n), d_dgrho1 / d_dgrho2 (npair, 3, n).  Outputs
+ * d_d2vrho (npair, n) and d_d2vgrad (npair, 3, n) = d2 (2 v_sigma grad rho) = 2 d2 v_sigma grad rho + 2 d v_sigma[1] grad d rho_2 +
+ * 2 d v_sigma[2] grad d rho_1, with d2 sigma = 2 grad d rho_1 . grad d rho_2 inside d2 v; symmetric in the two responses.  Layout,
+ * NULL gradient arguments for LDA-only lists, cutoff and gates of dqc_xc_eval_fxc (npair in the place of nvec). */
+int dqc_xc_eval_kxc(double *d_d2vrho, double *d_d2vgrad, const double *d_rho, const double *d_grho, const double *d_drho1,
+                    const double *d_dgrho1, const double *d_drho2, const double *d_dgrho2, int n, int npair, const int *ids,
+                    const double *coefs, int nterm, void *stream);
 /* spin-polarised: d v_rho,s and d v_grad,u = 2 d v_uu grad rho_u + 2 v_uu grad d rho_u + d v_ud grad rho_d + v_ud grad d rho_d
  * (u <-> d for the other spin), every derivative with the sigma_ud cross terms */
 int dqc_xc_eval_fxc_pol(double *d_dvrho_u, double *d_dvrho_d, double *d_dvgrad_u, double *d_dvgrad_d, const double *d_rho_u,
