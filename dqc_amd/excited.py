@@ -48,9 +48,10 @@ differentiates to 4 sum (d a b|c d) Gamma_abcd: Gamma = 1/2 (P_ab D_cd + D_ab P_
 give the factors above.]  A one-electron perturbation lambda O has d w / d lambda = tr[Pbar O]: the relaxed excited-state dipole moment is
 that of D + Pbar.
 
-The algebra lives in functions of plain tensors (`difference_density`, `transition_densities`, `lagrangian_rhs`, `energy_weighted`) that
-take a callable for J and K, so that tests/test_excited_gradient_cpu.py drives them with dense oracle integrals; the factors are held
-against finite differences there and in tests/test_gpu_excited_gradient.py.
+The algebra lives in functions of plain tensors (`difference_density`, `transition_densities`, `lagrangian_rhs` here; `relaxed_density_mo`
+and `energy_weighted` in dqc_amd/postscf.py, which the MP2 gradient shares with this one, as it does the Z-vector solve and the terms of
+a relaxed density) that take a callable for J and K, so that tests/test_excited_gradient_cpu.py drives them with dense oracle integrals;
+the factors are held against finite differences there and in tests/test_gpu_excited_gradient.py.
 
 KOHN-SHAM references (LDA, GGA, global hybrids; singlet states; `tddft_gradient`).  a = the exact-exchange fraction; on the grid, with
 (v, u) the potentials of the ground state (v_rho, 2 v_sigma grad rho), V1[M] = the f_xc matrix of rho_M (OrbitalHessian._vxc_response;
@@ -74,7 +75,7 @@ reference need the spin-polarised third-order kernel, meta-GGAs an orbital respo
 import torch
 
 from . import lib
-from .postscf import memoised
+from .postscf import cart_part, energy_weighted, memoised, relaxed_density_mo, relaxed_terms, stage_clock, z_vector  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ algebra on plain tensors
@@ -119,27 +120,6 @@ def lagrangian_rhs(u, v, co, cv, jk, triplet=False, xc=None, kfrac=1.0):
     return rhs, dict(t_oo=t_oo, t_vv=t_vv, tbar=tbar, s=s, n=n, g_t=g_t, coupling=coupling, v2=v2)
 
 
-def relaxed_density_mo(t_oo, t_vv, z=None):
-    """P (n, n) in the MO basis: T in its diagonal blocks and, with z (nv, no) the Z-vector, 2 z in the off-diagonal ones"""
-    no, nv = int(t_oo.shape[0]), int(t_vv.shape[0])
-    p = torch.zeros((no + nv, no + nv), dtype=t_oo.dtype, device=t_oo.device)
-    p[:no, :no], p[no:, no:] = t_oo, t_vv
-    if z is not None:
-        p[no:, :no], p[:no, no:] = 2.0 * z, 2.0 * z.T
-    return p
-
-
-def energy_weighted(p, eps, coupling, g_pbar, co, cv):
-    """W (nao, nao) = C 1/4 (Gm + Gm^T) C^T of the module docstring: p the (relaxed) difference density in the MO basis, eps all
-    orbital energies, coupling from `lagrangian_rhs`, g_pbar = G[C p C^T] in the AO basis (Kohn-Sham: G of the module docstring's last
-    section, J - a / 2 K + V1, plus 2 V2[S, S] -- `parts["g_t"]` of lagrangian_rhs(..., xc=...) already holds both for Tbar)"""
-    no = int(co.shape[1])
-    c = torch.cat([co, cv], dim=1)
-    gm = 2.0 * eps.unsqueeze(1) * p + coupling
-    gm[:, :no] += 4.0 * (c.T @ g_pbar @ co)
-    return c @ (0.25 * (gm + gm.T)) @ c.T
-
-
 # ------------------------------------------------------------------------------------------------ the calculation
 class ExcitedDensity:
     """the relaxed difference density of an excited state (detached tensors on the device of the calculation): `dm_mo` (n, n) = P = T + Z
@@ -172,18 +152,25 @@ class ExcitedGradient:
             float(self.excitation.abs().max()))
 
 
-def _refusals(qc, spin):
-    """what `excited_gradient` refuses before anything runs"""
+def _refusals(qc, who, spin, kohn_sham):
+    """what `who` (excited_gradient, tddft_gradient) refuses before anything runs; kohn_sham: whether it takes a Kohn-Sham reference"""
     from .response import _unsupported
     if spin not in ("singlet", "triplet"):
-        raise ValueError("excited_gradient: spin is \"singlet\" or \"triplet\", not %r" % (spin,))
+        raise ValueError("%s: spin is \"singlet\" or \"triplet\", not %r" % (who, spin))
     eng = qc._engine
-    if eng.is_ks:
-        raise NotImplementedError("excited_gradient: a Kohn-Sham reference (hybrid functionals included) is not taken here: the TDDFT "
+    if eng.is_ks and not kohn_sham:
+        raise NotImplementedError(who + ": a Kohn-Sham reference (hybrid functionals included) is not taken here: the TDDFT "
                                   "Lagrangian with the third-order exchange-correlation kernel is behind its own name -- use tddft_gradient")
     if eng.polarized:
-        raise NotImplementedError("excited_gradient: unrestricted calculations are not supported (the restricted closed-shell "
+        raise NotImplementedError(who + ": unrestricted calculations are not supported (the restricted closed-shell "
                                   "Lagrangian only; the spin-resolved one is not built)")
+    if eng.is_ks:
+        if spin == "triplet":
+            raise NotImplementedError(who + ": triplet states of a Kohn-Sham reference are not supported: they need the "
+                                      "spin-polarised third-order exchange-correlation kernel, which is not built (singlets only)")
+        if any(name.startswith("mgga_") for _, name in getattr(eng.xc, "terms", ())):
+            raise NotImplementedError(who + ": meta-GGA functionals are not supported (they have no orbital response: "
+                                      "no second- or third-order kernel)")
     _unsupported(qc)
 
 
@@ -243,23 +230,16 @@ def _gradient(qc, state, spin, tda, nstates, tol, ztol, with_z=True, times=None,
     exchange-correlation kernel out of a Kohn-Sham gradient in the same way (tests/test_gpu_tddft_gradient.py); times: a dict that
     receives the wall time of the stages (tools/gpu_excited_gradient_time.py, tools/gpu_tddft_gradient_time.py); who: the public
     function that asks, for the messages"""
-    import time
     from .gradient import _pulay_densities
-    from .properties import excitations
-    from .response import OrbitalHessian, orbital_hessian
+    from .properties import dipole_au, excitations
+    from .response import orbital_hessian
     eng = qc._engine
     h = eng.hamilton
     dev = h.device
     ks = bool(eng.is_ks)
     a = float(eng.exx) if ks else 1.0         # the exact-exchange fraction on every K
-
-    def clock():
-        if times is not None:
-            torch.cuda.synchronize(dev)
-        return time.perf_counter()
-
-    with torch.enable_grad():                # (the memo runs this without autograd; a Kohn-Sham gradient differentiates the grid weights)
-        scf = qc.nuclear_gradient().detach()     # (raises what nuclear_gradient refuses: a field, vext)
+    clock = stage_clock(times, dev)
+    scf = qc.nuclear_gradient().detach()     # (raises what nuclear_gradient refuses: a field, vext)
     tic = clock()
     ex = excitations(qc, nstates=state + 1 if nstates is None else int(nstates), spin=spin, tda=tda, tol=tol)
     t_exc = clock() - tic
@@ -288,14 +268,9 @@ def _gradient(qc, state, spin, tda, nstates, tol, ztol, with_z=True, times=None,
         rhs, parts = lagrangian_rhs(u, v, co, cv, jk, xc=_xc_matrices(op, with_kxc), kfrac=a)
     else:
         rhs, parts = lagrangian_rhs(u, v, co, cv, jk, triplet=spin == "triplet")
-    z, z_residual = None, None
     # the orbital relaxation is a singlet for either spin; on the orbitals of the vectors (the memoised singlet operator holds the same
     # ones unless the eigensolver returned the Fock eigenvectors in another phase)
-    ohs = op if spin == "singlet" else orbital_hessian(qc)
-    if not (torch.equal(ohs.spins[0].co, co) and torch.equal(ohs.spins[0].cv, cv)):
-        ohs = OrbitalHessian(qc, orbitals=(torch.cat([co, cv], dim=1), torch.cat([eo, ev])))
-    z = ohs.solve(-rhs.reshape(1, -1), tol=ztol).reshape(nv, no)
-    z_residual = float(ohs.last_residual)
+    z, z_residual = z_vector(qc, (co, cv, eo, ev), rhs, ztol, op if spin == "singlet" else orbital_hessian(qc))
     t_z = clock() - tic
     t_mo = relaxed_density_mo(parts["t_oo"], parts["t_vv"])
     p = relaxed_density_mo(parts["t_oo"], parts["t_vv"], z if with_z else None)
@@ -312,16 +287,9 @@ def _gradient(qc, state, spin, tda, nstates, tol, ztol, with_z=True, times=None,
     _, d_scf, _ = _pulay_densities(qc)
     d_scf = d_scf.detach()
     T = lib.cart2sph_matrix(h._tab, dev)
-    sym = lambda m: (0.5 * (T.T @ m @ T + (T.T @ m @ T).T)).contiguous()      # noqa: E731  (exactly symmetric: the gate of eri_grad2)
-    asym = lambda m: (0.5 * (T.T @ m @ T - (T.T @ m @ T).T)).contiguous()    # noqa: E731
-    mol = qc.get_system()
-    natm = len(mol.atomzs)
-    exc = torch.zeros((natm, 3), dtype=torch.float64, device=dev)
-    pc = sym(pbar)
-    lib.int1e_grad(exc, pc, sym(w2), h._tab, h._zs)
     tic = clock()
-    sc, nc = sym(parts["s"]), asym(parts["n"])
-    lib.eri_grad2(exc, sym(d_scf), pc, 2.0, 2.0 * a, h._tab)                         # separable: 2 eri_grad2(D, Pbar, 1, a)
+    exc = relaxed_terms(h, T, d_scf, pbar, w2, a)                                    # one-electron and separable: 2 eri_grad2(D, Pbar, 1, a)
+    sc, nc = cart_part(T, parts["s"]), cart_part(T, parts["n"], -1.0)
     lib.eri_grad2(exc, sc, sc, 0.0 if spin == "triplet" else 4.0, 4.0 * a, h._tab)   # non-separable, symmetric part
     if a != 0.0:
         lib.eri_grad2(exc, nc, nc, 0.0, 4.0 * a, h._tab)                             # non-separable, antisymmetric part: exchange only
@@ -331,9 +299,7 @@ def _gradient(qc, state, spin, tda, nstates, tol, ztol, with_z=True, times=None,
         gxc, t_grid, t_wts = _xc_gradient_terms(qc, op, pbar, parts["s"], d_scf, with_kxc, clock)
         exc += gxc
     dm_ao = d_scf + pbar
-    r = lib.int1e("r0", h._tab, dev)
-    pos = mol.atompos.detach().to(dev)
-    dip = -torch.einsum("dab,ba->d", r, dm_ao) + torch.einsum("ad,a->d", pos, mol.atomzs.to(pos.dtype).to(dev))
+    dip = dipole_au(h, qc.get_system(), dm_ao).detach()
     if times is not None:
         times.update(excitations=t_exc, z_vector=t_z, passes=t_pass)
         if ks:
@@ -341,6 +307,17 @@ def _gradient(qc, state, spin, tda, nstates, tol, ztol, with_z=True, times=None,
     omega = ex.energies[state].detach().reshape(1)
     dens = ExcitedDensity(p, t_mo, dm_ao, dip)
     return ExcitedGradient(scf + exc, scf, omega, qc.energy().detach().reshape(1) + omega, xpy, xmy, dens, z_residual, state, spin, tda)
+
+
+def _entry(who, kohn_sham, qc, state, spin, tda, nstates, tol, ztol):
+    """the memoised `_gradient` behind both public names, under the key of `who`; refuses before anything reaches the library"""
+    assert qc._has_run, "run() the calculation first"
+    state = int(state)
+    if state < 0:
+        raise ValueError("%s: state must be >= 0, got %d" % (who, state))
+    _refusals(qc, who, spin, kohn_sham)
+    key = (who, state, spin, bool(tda), None if nstates is None else int(nstates), float(tol), float(ztol))
+    return memoised(qc, key, lambda: _gradient(qc, state, spin, bool(tda), nstates, float(tol), float(ztol), who=who))
 
 
 def excited_gradient(qc, state=0, spin="singlet", tda=False, nstates=None, tol=1e-8, ztol=1e-9):
@@ -351,35 +328,8 @@ def excited_gradient(qc, state=0, spin="singlet", tda=False, nstates=None, tol=1
     which must be met (RuntimeError otherwise: the formula needs a stationary w); ztol: relative residual of the Z-vector solve.
     For what `excitations` and `nuclear_gradient` take, on a Hartree-Fock reference: a Kohn-Sham one (NotImplementedError: it is taken by
     `tddft_gradient`, which has the third-order exchange-correlation kernel) and an unrestricted one are refused.  The two-electron part
-    is three passes of the bilinear derivative kernel (lib.eri_grad2).  Memoised on the converged state per argument set; detached.
-    This and `tddft_gradient` run the same `_gradient`; the refusal of Kohn-Sham stays only because tests/test_gpu_excited_gradient.py
-    pins it -- folding the two names into one is a one-line change once that test may be edited."""
-    assert qc._has_run, "run() the calculation first"
-    state = int(state)
-    if state < 0:
-        raise ValueError("excited_gradient: state must be >= 0, got %d" % state)
-    _refusals(qc, spin)
-    key = ("excited_gradient", state, spin, bool(tda), None if nstates is None else int(nstates), float(tol), float(ztol))
-    return memoised(qc, key, lambda: _gradient(qc, state, spin, bool(tda), nstates, float(tol), float(ztol)))
-
-
-def _tddft_refusals(qc, spin):
-    """what `tddft_gradient` refuses before anything runs"""
-    from .response import _unsupported
-    if spin not in ("singlet", "triplet"):
-        raise ValueError("tddft_gradient: spin is \"singlet\" or \"triplet\", not %r" % (spin,))
-    eng = qc._engine
-    if eng.polarized:
-        raise NotImplementedError("tddft_gradient: unrestricted calculations are not supported (the restricted closed-shell "
-                                  "Lagrangian only; the spin-resolved one is not built)")
-    if eng.is_ks:
-        if spin == "triplet":
-            raise NotImplementedError("tddft_gradient: triplet states of a Kohn-Sham reference are not supported: they need the "
-                                      "spin-polarised third-order exchange-correlation kernel, which is not built (singlets only)")
-        if any(name.startswith("mgga_") for _, name in getattr(eng.xc, "terms", ())):
-            raise NotImplementedError("tddft_gradient: meta-GGA functionals are not supported (they have no orbital response: "
-                                      "no second- or third-order kernel)")
-    _unsupported(qc)
+    is three passes of the bilinear derivative kernel (lib.eri_grad2).  Memoised on the converged state per argument set; detached."""
+    return _entry("excited_gradient", False, qc, state, spin, tda, nstates, tol, ztol)
 
 
 def tddft_gradient(qc, state=0, spin="singlet", tda=False, nstates=None, tol=1e-8, ztol=1e-9):
@@ -389,16 +339,8 @@ def tddft_gradient(qc, state=0, spin="singlet", tda=False, nstates=None, tol=1e-
     (module docstring, last section) on the third-order kernel lib.xc_eval_kxc, the Becke-weight derivative included; two passes of
     lib.eri_grad2 for a pure functional, three for a hybrid.  Hartree-Fock: both spins, the path and the numbers of `excited_gradient`.
     Refused before anything runs: Kohn-Sham triplets (the polarised third-order kernel is not built), meta-GGA functionals,
-    unrestricted references, and what `OrbitalHessian` and `nuclear_gradient` refuse.  Memoised under its own key; detached.
-    This and `excited_gradient` run the same `_gradient`; `excited_gradient` keeps refusing a Kohn-Sham reference only because its test
-    pins that refusal -- folding the two names into one is a one-line change once that test may be edited."""
-    assert qc._has_run, "run() the calculation first"
-    state = int(state)
-    if state < 0:
-        raise ValueError("tddft_gradient: state must be >= 0, got %d" % state)
-    _tddft_refusals(qc, spin)
-    key = ("tddft_gradient", state, spin, bool(tda), None if nstates is None else int(nstates), float(tol), float(ztol))
-    return memoised(qc, key, lambda: _gradient(qc, state, spin, bool(tda), nstates, float(tol), float(ztol), who="tddft_gradient"))
+    unrestricted references, and what `OrbitalHessian` and `nuclear_gradient` refuse.  Memoised under its own key; detached."""
+    return _entry("tddft_gradient", True, qc, state, spin, tda, nstates, tol, ztol)
 
 
 __all__ = ["excited_gradient", "tddft_gradient", "ExcitedGradient", "ExcitedDensity", "difference_density", "transition_densities", "lagrangian_rhs",

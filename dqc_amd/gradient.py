@@ -17,8 +17,9 @@ differentiates the discretised functional E_xc = sum_g w_g(R) e(rho_s(r_g(R))) e
 with b = Phi D_s, c_i = d_i Phi D_s, u = the gradient part of the potential (`vgrad` of dqc_xc_eval*), S_j = sum_i u_i d_i d_j Phi:
 (ii)  grid points riding on atom A:  sum_{g in A} w [v_rho d_j rho + 2 sum_mu (b S_j + c_j (u . grad phi))]
 (iii) centres of the AOs on A:       -2 sum_g w sum_{mu in A} [d_j phi (v_rho b + u . c) + b S_j]
-((ii) + (iii) summed over atoms cancel identically; LDA: u = 0; meta-GGA: the tau terms of _xc_gradient).  With density
-fitting the two-electron term is _df_coulomb_gradient (dqc_df_grad).
+((ii) + (iii) summed over atoms cancel identically; LDA: u = 0; meta-GGA: the tau terms).  (ii) and (iii) are _xc_grid_terms, for the
+ground state (_xc_gradient) and for any other matrix and potentials (_xc_potential_gradient); (i) is _xc_weight_gradient.  With
+density fitting the two-electron term is _df_coulomb_gradient (dqc_df_grad).
 """
 import torch
 
@@ -273,28 +274,22 @@ def _nuclei_gradient(mol):
     return -(f.unsqueeze(-1) * d).sum(1)
 
 
-def _xc_gradient(eng, d_aos):
+def _xc_gradient(eng, d_aos, fused=None):
     """d_aos: [D] (restricted) or [D_u, D_d]; LDA (deriv-1 AOs), GGA / meta-GGA (deriv-3 AOs).  The potentials come from
     the functional object itself (BaseXC.get_vxc on ValGrad / SpinParam densities), so every functional the Hamiltonian
-    can run has a gradient.  Meta-GGA adds, with tau = 1/2 sum_d d_d Phi D d_d Phi and c_d = d_d Phi D:
-        (ii)  + w v_tau sum_mu sum_d (d_d d_j phi_mu) c_{mu,d}        (iii)  - the same restricted to mu on A
-    (v_lapl = 0 for every functional of the kernel set)."""
+    can run has a gradient: the terms (ii) and (iii) of the module docstring spin by spin (_xc_grid_terms; fused as it takes
+    it) plus the Becke-weight term (i) on the energy density (_xc_weight_gradient)."""
     from .utils.datastruct import ValGrad
     h = eng.hamilton
-    mol = eng.get_system()
-    dev = h.device
-    nao, ld = h._nao_ao, h._ld
+    nao = h._nao_ao
     fam = h.xcfamily
     gga = fam >= 2
     ao = lib.eval_gto(h._tab, h.rgrid, 3 if gga else 1)                        # (10 | 4, ngrid, ld)
-    dpads = [lib.pad_matrix(d, ld) for d in d_aos]
-    lda = ao.shape[-1]  # row stride of the AO arrays (>= nao, zero padding columns)
     bs, cs_, infos = [], [], []
-    for dp in dpads:
+    for d in d_aos:
+        dp = lib.pad_matrix(d, h._ld)
         rho_s, grho_s = lib.grid_density(ao[:4], nao, dp, True)
-        dq = dp[:lda, :lda]
-        b = ao[0] @ dq                                                         # (ngrid, lda)
-        c = [ao[1 + i] @ dq for i in range(3)] if gga else None
+        b, c = _phi_m(ao, dp, gga)
         tau = 0.5 * sum((c[i] * ao[1 + i]).sum(1) for i in range(3)) if fam == 4 else None
         bs.append(b)
         cs_.append(c)
@@ -303,85 +298,38 @@ def _xc_gradient(eng, d_aos):
     edens = h.xc.get_edensityxc(dens)
     pot = h.xc.get_vxc(dens)
     pots = [pot] if len(infos) == 1 else [pot.u, pot.d]
-    w = h.dvolume
-    natm = len(mol.atomzs)
-    ao_atom = _ao_owner(h, dev)
-    g = torch.zeros((natm, 3), dtype=torch.float64, device=dev)
-    live = getattr(h, "live_index", None)  # the Hamiltonian keeps the points of non-zero weight only (setup_grid)
-
-    def full(x):  # per-point rows on the live points -> rows on the caller's grid (zero elsewhere: zero weight, zero derivative)
-        if live is None:
-            return x
-        o = torch.zeros((h.ngrid_full,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-        o[live] = x
-        return o
-
-    for info, b, c, pt in zip(infos, bs, cs_, pots):
-        vrho, u, vtau = pt.value, pt.grad, pt.kin
-        if gga and ao.shape[0] == 10 and nao <= 512:
-            # one fused pass over the ten derivative arrays (dqc_grid_xc_gradient_terms) instead of ~40 element-wise passes
-            q, per_ao = lib.grid_xc_gradient_terms(ao, nao, b, c, w, vrho, u, info.grad, vtau if fam == 4 else None)
-            g += _sum_by_owner(mol, full(q))       # (ii)
-            g.index_add_(0, ao_atom, -2.0 * per_ao)  # (iii)
-            continue
-        q = torch.empty((h.rgrid.shape[0], 3), dtype=torch.float64, device=dev)
-        per_ao = torch.empty((nao, 3), dtype=torch.float64, device=dev)
-        if gga:
-            t1 = vrho.unsqueeze(-1) * b + sum(u[i].unsqueeze(-1) * c[i] for i in range(3))
-            ugphi = sum(u[i].unsqueeze(-1) * ao[1 + i] for i in range(3))      # u . grad phi
-        else:
-            t1 = vrho.unsqueeze(-1) * b
-        for j in range(3):
-            if gga:
-                bsj = b * sum(u[i].unsqueeze(-1) * ao[_HESS[i][j]] for i in range(3))
-                if fam == 4:  # tau terms: v_tau sum_d (d_d d_j phi) c_d; same form in (ii) and (iii), without the factor 2
-                    bsj = bsj + 0.5 * vtau.unsqueeze(-1) * sum(ao[_HESS[d][j]] * c[d] for d in range(3))
-                q[:, j] = w * (vrho * info.grad[j] + 2.0 * (bsj.sum(1) + (c[j] * ugphi).sum(1)))
-                per_ao[:, j] = ((ao[1 + j] * t1 + bsj) * w.unsqueeze(-1)).sum(0)[:nao]
-            else:
-                q[:, j] = w * vrho * _grad_rho(ao, b, j)
-                per_ao[:, j] = (ao[1 + j] * t1 * w.unsqueeze(-1)).sum(0)[:nao]
-        g += _sum_by_owner(mol, full(q))       # (ii)
-        g.index_add_(0, ao_atom, -2.0 * per_ao)  # (iii)
-    # (i) Becke-weight derivative, energy density held fixed
-    pos = mol.atompos.to(dtype=torch.float64, device=dev).clone().requires_grad_(True)
-    grid = get_predefined_grid(mol._grid_inp, mol.atomzs.tolist(), pos, dtype=torch.float64, device=dev)
-    loss = (grid.get_dvolume() * full(edens.detach())).sum()
-    return g + torch.autograd.grad(loss, pos)[0]
+    g = sum(_xc_grid_terms(eng, ao, b, c, info.grad, pt.value, pt.grad, pt.kin if fam == 4 else None, fused)
+            for info, b, c, pt in zip(infos, bs, cs_, pots))
+    return g + _xc_weight_gradient(eng, edens)
 
 
-def _full_grid(h, x):
-    """per-point rows on the live points of the Hamiltonian -> rows on the caller's grid (zero elsewhere), as in _xc_gradient"""
-    live = getattr(h, "live_index", None)
-    if live is None:
-        return x
-    o = torch.zeros((h.ngrid_full,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-    o[live] = x
-    return o
+def _phi_m(ao, mpad, gga):
+    """(b = Phi M (ngrid, lda), c = [d_i Phi M] or None without gga) for a symmetric AO matrix M, padded by lib.pad_matrix"""
+    lda = ao.shape[-1]  # row stride of the AO arrays (>= nao, zero padding columns)
+    dq = mpad[:lda, :lda]
+    return ao[0] @ dq, [ao[1 + i] @ dq for i in range(3)] if gga else None
 
 
-def _xc_potential_gradient(eng, ao, m_ao, vrho, u, fused=None):
-    """G(M; a, b) = sum_g w [a d rho_M + b . d grad rho_M] at fixed M (natm, 3), the AO centres and the grid points riding on their
-    atoms: the terms (ii) and (iii) of the module docstring for ANY symmetric AO matrix M = m_ao and ANY per-point pair a = vrho
-    (ngrid,), b = u (3, ngrid) or None (LDA) -- with M = D and the ground-state potentials they are those of _xc_gradient.  ao: the
-    deriv-3 AO array (10, ngrid, ld) for a GGA pair, deriv-1 (4, ngrid, ld) for LDA, evaluated once by the caller for all its calls
-    (dqc_amd/excited.py makes three).  fused: None = the one-pass kernel dqc_grid_xc_gradient_terms for a GGA pair with nao <= 512
-    and the torch passes otherwise, as _xc_gradient chooses; False forces the torch passes."""
+def _xc_grid_terms(eng, ao, b, c, grho, vrho, u, vtau=None, fused=None):
+    """The terms (ii) and (iii) of the module docstring, summed to (natm, 3), for ONE symmetric AO matrix M and ONE set of per-point
+    factors: b = Phi M, c = [d_i Phi M] (None: LDA, u unused), grho = grad rho_M (3, ngrid) (None: formed here from b), vrho
+    (ngrid,), u (3, ngrid), vtau (ngrid,) or None.  Meta-GGA (vtau) adds, with tau = 1/2 sum_d d_d Phi M d_d Phi:
+        (ii)  + w v_tau sum_mu sum_d (d_d d_j phi_mu) c_{mu,d}        (iii)  - the same restricted to mu on A
+    (v_lapl = 0 for every functional of the kernel set).  fused: None = one pass over the ten derivative arrays
+    (dqc_grid_xc_gradient_terms, instead of ~40 element-wise passes) for a GGA / meta-GGA on the deriv-3 array with nao <= 512 and
+    the torch passes otherwise; False forces the torch passes."""
     h = eng.hamilton
     mol = eng.get_system()
     dev = h.device
-    nao, ld = h._nao_ao, h._ld
-    gga = u is not None
+    nao = h._nao_ao
+    gga = c is not None
     w = h.dvolume
-    lda = ao.shape[-1]
-    dq = lib.pad_matrix(m_ao, ld)[:lda, :lda]
-    b = ao[0] @ dq
-    c = [ao[1 + i] @ dq for i in range(3)] if gga else None
+    if grho is None:
+        grho = torch.stack([_grad_rho(ao, b, j) for j in range(3)])
     if fused is None:
         fused = gga and ao.shape[0] == 10 and nao <= 512
     if fused:
-        grho = torch.stack([_grad_rho(ao, b, j) for j in range(3)])
-        q, per_ao = lib.grid_xc_gradient_terms(ao, nao, b, c, w, vrho, u, grho, None)
+        q, per_ao = lib.grid_xc_gradient_terms(ao, nao, b, c, w, vrho, u, grho, vtau)
     else:
         q = torch.empty((h.rgrid.shape[0], 3), dtype=torch.float64, device=dev)
         per_ao = torch.empty((nao, 3), dtype=torch.float64, device=dev)
@@ -392,19 +340,42 @@ def _xc_potential_gradient(eng, ao, m_ao, vrho, u, fused=None):
         for j in range(3):
             if gga:
                 bsj = b * sum(u[i].unsqueeze(-1) * ao[_HESS[i][j]] for i in range(3))
-                q[:, j] = w * (vrho * _grad_rho(ao, b, j) + 2.0 * (bsj.sum(1) + (c[j] * ugphi).sum(1)))
+                if vtau is not None:  # tau terms: v_tau sum_d (d_d d_j phi) c_d; same form in (ii) and (iii), without the factor 2
+                    bsj = bsj + 0.5 * vtau.unsqueeze(-1) * sum(ao[_HESS[d][j]] * c[d] for d in range(3))
+                q[:, j] = w * (vrho * grho[j] + 2.0 * (bsj.sum(1) + (c[j] * ugphi).sum(1)))
                 per_ao[:, j] = ((ao[1 + j] * t1 + bsj) * w.unsqueeze(-1)).sum(0)[:nao]
             else:
-                q[:, j] = w * vrho * _grad_rho(ao, b, j)
+                q[:, j] = w * vrho * grho[j]
                 per_ao[:, j] = (ao[1 + j] * t1 * w.unsqueeze(-1)).sum(0)[:nao]
     g = _sum_by_owner(mol, _full_grid(h, q))                 # (ii)
     g.index_add_(0, _ao_owner(h, dev), -2.0 * per_ao)        # (iii)
     return g
 
 
+def _full_grid(h, x):
+    """per-point rows on the live points of the Hamiltonian (it keeps the points of non-zero weight only: setup_grid) -> rows on the
+    caller's grid (zero elsewhere: zero weight, zero derivative)"""
+    live = getattr(h, "live_index", None)
+    if live is None:
+        return x
+    o = torch.zeros((h.ngrid_full,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    o[live] = x
+    return o
+
+
+def _xc_potential_gradient(eng, ao, m_ao, vrho, u, fused=None):
+    """G(M; a, b) = sum_g w [a d rho_M + b . d grad rho_M] at fixed M (natm, 3), the AO centres and the grid points riding on their
+    atoms: the terms (ii) and (iii) of the module docstring (_xc_grid_terms) for ANY symmetric AO matrix M = m_ao and ANY per-point
+    pair a = vrho (ngrid,), b = u (3, ngrid) or None (LDA).  ao: the deriv-3 AO array (10, ngrid, ld) for a GGA pair, deriv-1
+    (4, ngrid, ld) for LDA, evaluated once by the caller for all its calls (dqc_amd/excited.py makes three).  fused: as
+    _xc_grid_terms takes it."""
+    b, c = _phi_m(ao, lib.pad_matrix(m_ao, eng.hamilton._ld), u is not None)
+    return _xc_grid_terms(eng, ao, b, c, None, vrho, u, None, fused)
+
+
 def _xc_weight_gradient(eng, per_point):
     """sum_g (d w_g / dR) x_g (natm, 3) for a fixed per-point factor x = per_point (ngrid,) on the live points: torch autograd through
-    the grid construction, the term (i) of _xc_gradient (which has the energy density as x)"""
+    the grid construction, the term (i) of the module docstring (_xc_gradient has the energy density as x)"""
     h = eng.hamilton
     mol = eng.get_system()
     dev = h.device

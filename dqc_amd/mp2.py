@@ -32,7 +32,8 @@ non-separable part runs through the three-index-density derivative pass dqc_df_g
 import torch
 
 from . import lib
-from .postscf import aux_key, b_tensor, free_bytes, memoised, orbitals, pair_energy_blocks, transform_ov, unsupported
+from .postscf import (aux_key, b_tensor, energy_weighted, free_bytes, memoised, orbitals, pair_energy_blocks, relaxed_density_mo,
+                      relaxed_terms, stage_clock, transform_ov, unsupported, z_vector)
 
 # the names under which tests/test_mp2_cpu.py and tests/test_gpu_mp2_density.py, written when these lived here, import them
 _unsupported, _b_tensor, _orbitals = unsupported, b_tensor, orbitals
@@ -264,8 +265,7 @@ def _lagrangian(h, b, co, cv, p_oo, p_vv, gamma, parts=None):
 def _density(qc, frozen, auxbasis, c_os, c_ss, relaxed, tol, block, parts=None):
     """the MP2Density; parts: a dict that receives what the nuclear gradient takes from this build (df, co, cv, eo, ev, bov, gamma,
     p_oo, p_vv and, relaxed, z, x, y), so that nothing of it is computed twice"""
-    from .properties import _total_ao_density
-    from .response import OrbitalHessian
+    from .properties import _total_ao_density, dipole_au
     h = qc._engine.hamilton
     df = b_tensor(qc, auxbasis)
     b = df._b
@@ -278,20 +278,13 @@ def _density(qc, frozen, auxbasis, c_os, c_ss, relaxed, tol, block, parts=None):
         parts.update(df=df, co=co, cv=cv, eo=eo, ev=ev, bov=bov, gamma=gamma, p_oo=p_oo, p_vv=p_vv)
     nf, no, nv = int(c_frozen.shape[1]), int(co.shape[1]), int(cv.shape[1])
     n = nf + no + nv
-    dm_mo = torch.zeros((n, n), dtype=b.dtype, device=b.device)
-    dm_mo[nf:nf + no, nf:nf + no] = p_oo
-    dm_mo[nf + no:, nf + no:] = p_vv
-    z_residual = None
+    z = z_residual = None
     if relaxed:
-        lag = _lagrangian(h, b, co, cv, p_oo, p_vv, gamma, parts)
-        c_all, e_all = torch.cat([co, cv], dim=1), torch.cat([eo, ev])
-        oh = OrbitalHessian(qc, orbitals=(c_all, e_all))
-        z = oh.solve(-lag.reshape(1, -1), tol=tol).reshape(nv, no)
-        z_residual = float(oh.last_residual)
+        z, z_residual = z_vector(qc, (co, cv, eo, ev), _lagrangian(h, b, co, cv, p_oo, p_vv, gamma, parts), tol)
         if parts is not None:
             parts.update(z=z)
-        dm_mo[nf + no:, nf:nf + no] = 2.0 * z
-        dm_mo[nf:nf + no, nf + no:] = 2.0 * z.t()
+    dm_mo = torch.zeros((n, n), dtype=b.dtype, device=b.device)
+    dm_mo[nf:, nf:] = relaxed_density_mo(p_oo, p_vv, z)
     c_all = torch.cat([c_frozen, co, cv], dim=1)
     _, d_scf = _total_ao_density(qc)
     d_scf = d_scf.detach()
@@ -300,10 +293,7 @@ def _density(qc, frozen, auxbasis, c_os, c_ss, relaxed, tol, block, parts=None):
     occ_mo.diagonal()[:nf + no] += 2.0
     occ, u = torch.linalg.eigh(occ_mo)
     occ, orbs = occ.flip(0), (c_all @ u).flip(1)
-    mol = qc.get_system()
-    r = lib.int1e("r0", h._tab, h.device)
-    pos = mol.atompos.detach().to(h.device)
-    dip = -torch.einsum("dab,ba->d", r, dm_ao) + torch.einsum("ad,a->d", pos, mol.atomzs.to(pos.dtype).to(h.device))
+    dip = dipole_au(h, qc.get_system(), dm_ao).detach()
     return MP2Density(dm_mo, dm_ao, occ, orbs.contiguous(), dip, e_corr, relaxed, z_residual, c_os, c_ss, frozen, b.shape[0], nb)
 
 
@@ -356,20 +346,20 @@ def mp2_density(qc, frozen=0, auxbasis=None, c_os=1.0, c_ss=1.0, relaxed=True, t
 # which meets the functional through the symmetric part of C^T dLagrangian / dC: an energy-weighted density.  Terms, (p, q) over all
 # orbitals, P the relaxed `dm_mo`, Pbar = C P C^T, D the SCF density:
 #
-#   one-electron   tr[(D + Pbar) dh] - tr[(W_SCF + W2) dS]                                               -> lib.int1e_grad
-#       W2 = C 1/4 (Gm + Gm^T) C^T,   Gm[p, q] = C_p^T dLagrangian / dC_q  (correlation part):
+#   the SCF energy   qc.nuclear_gradient(): tr[D dh] - tr[W_SCF dS] + Q(D) + nuclear repulsion,
+#       Q(D) = sum (d a b|c d) [2 D_ab D_cd - D_ac D_bd] = d[1/2 D.G.D]
+#   one-electron   tr[Pbar dh] - tr[W2 dS]                                                               -> postscf.relaxed_terms
+#       W2 = C 1/4 (Gm + Gm^T) C^T,   Gm[p, q] = C_p^T dLagrangian / dC_q  (correlation part; postscf.energy_weighted):
 #       Gm[p, q] = 2 eps_p P_pq                       (the outer orbitals of tr[P C^T F C])
 #       Gm[p, i] += 4 (C^T G[Pbar] C_o)_pi            (F follows D = 2 C_o C_o^T)
-#       Gm[k, i] += 4 sum_Pa Bov[k, P, a] Gamma[i, P, a]     Gm[c, i] += 4 X_ci
+#       Gm[k, i] += 4 sum_Pa Bov[k, P, a] Gamma[i, P, a]     Gm[c, i] += 4 X_ci                           (`orbital_coupling`)
 #       Gm[k, a] += 4 Y_ak                                    Gm[c, a] += 4 sum_iP Bov[i, P, c] Gamma[i, P, a]
-#   separable two-electron   Q(D) + [Q(D + Pbar) - Q(D) - Q(Pbar)] = Q(D + Pbar) - Q(Pbar),
-#       Q(D) = sum (d a b|c d) [2 D_ab D_cd - D_ac D_bd] = d[1/2 D.G.D]                                   -> lib.eri_grad, two calls
+#   separable two-electron   Q(D + Pbar) - Q(D) - Q(Pbar) = 2 eri_grad2(D, Pbar, 1, 1): one bilinear pass   -> postscf.relaxed_terms
 #   non-separable   4 sum Gamma d Bov at fixed orbitals, Bov = C^-1 (Q|ia), (P|Q) = C C^T  (`chol` below is this C):
 #       sum Z[mu, nu, Q] d(mu nu|Q) - 1/2 sum G[P, Q] d(P|Q)                                              -> lib.df_grad3
 #       Gt = C^-T Gamma,  Bt = C^-T Bov  (triangular solves over the auxiliary index),  gam[P, Q] = sum_ia Bt[i, P, a] Gt[i, Q, a]
 #       Z = 4 sym_mu,nu (C_o Gt C_v^T),   G = 4 sym(gam)
 #       (d C^-1 = -C^-1 dC C^-1, and N = sum Gamma Bov^T is symmetric, so tr[N C^-1 dC] = 1/2 tr[C^-T N C^-1 d(P|Q)])
-#   nuclear repulsion   as in nuclear_gradient
 #
 # tests/test_mp2_gradient_cpu.py and tests/test_gpu_mp2_gradient.py hold the factors against finite differences.
 
@@ -447,59 +437,41 @@ def _nonseparable_gradient(df, gamma, bov, co, cv, natm, block, times=None):
     return gbig[:natm] + gbig[natm:]
 
 
+def orbital_coupling(bov, gamma, x, y, nv):
+    """the (n, n) MO matrix of the four Gamma blocks of Gm in the comment above (the `coupling` of postscf.energy_weighted), in plain
+    torch on the device of the inputs: bov, gamma (no, naux, >= nv) -- columns past nv (padding) are ignored -- and X, Y (nv, no)"""
+    oo = torch.einsum("kpa,ipa->ki", bov, gamma)
+    vv = torch.einsum("ipc,ipa->ca", bov, gamma)[:nv, :nv]
+    return 4.0 * torch.cat([torch.cat([oo, y.t()], dim=1), torch.cat([x, vv], dim=1)], dim=0)
+
+
 def _gradient(qc, auxbasis, c_os, c_ss, tol, block, with_z=True, times=None):
     """(MP2Density, scf (natm, 3), total (natm, 3)) of the comment above.  with_z=False leaves the Z-vector blocks out of P (NOT a
     gradient of anything: tests/test_gpu_mp2_gradient.py shows with it that the relaxation is not skipped); times: a dict that receives
     the wall time of the stages (tools/gpu_mp2_gradient_time.py)"""
-    import time
-    from .gradient import _nuclei_gradient, _pulay_densities
+    from .gradient import _pulay_densities
     h = qc._engine.hamilton
     dev = h.device
-
-    def clock():
-        if times is not None:
-            torch.cuda.synchronize(dev)
-        return time.perf_counter()
-
+    clock = stage_clock(times, dev)
     scf = qc.nuclear_gradient().detach()     # (raises what nuclear_gradient refuses: a field, vext)
     tic = clock()
     parts = {}
     dens = _density(qc, 0, auxbasis, c_os, c_ss, True, tol, block, parts)
     t_density = clock() - tic
     co, cv, eo, ev, bov, gamma = (parts[k] for k in ("co", "cv", "eo", "ev", "bov", "gamma"))
-    no, nv, nao = int(co.shape[1]), int(cv.shape[1]), int(co.shape[0])
-    c_all, e_all = torch.cat([co, cv], dim=1), torch.cat([eo, ev])
-    p = dens.dm_mo.clone()
-    if not with_z:
-        p[no:, :no] = 0.0
-        p[:no, no:] = 0.0
+    nv, nao = int(cv.shape[1]), int(co.shape[0])
+    c_all = torch.cat([co, cv], dim=1)
+    p = dens.dm_mo if with_z else relaxed_density_mo(parts["p_oo"], parts["p_vv"])
     pbar = c_all @ p @ c_all.t()
     pb = pbar.reshape(1, nao, nao).contiguous()
     jm, km = lib.jk_multi(h._tiles, pb, pb, h._multi_work(1, 1))
-    gm = 2.0 * e_all.unsqueeze(1) * p
-    gm[:, :no] += 4.0 * (c_all.t() @ (jm[0] - 0.5 * km[0]) @ co)
-    gm[:no, :no] += 4.0 * torch.einsum("kpa,ipa->ki", bov, gamma)
-    gm[no:, :no] += 4.0 * parts["x"]
-    gm[:no, no:] += 4.0 * parts["y"].t()
-    gm[no:, no:] += 4.0 * torch.einsum("ipc,ipa->ca", bov, gamma)[:nv, :nv]
-    w2 = c_all @ (0.25 * (gm + gm.t())) @ c_all.t()
-    _, d_scf, w_scf = _pulay_densities(qc)
-    d_scf, w_scf = d_scf.detach(), w_scf.detach()
-    T = lib.cart2sph_matrix(h._tab, dev)
-    tocart = lambda m: (T.T @ m @ T).contiguous()  # noqa: E731
-    mol = qc.get_system()
-    natm = len(mol.atomzs)
-    grad = torch.zeros((natm, 3), dtype=torch.float64, device=dev)
-    lib.int1e_grad(grad, tocart(d_scf + pbar), tocart(w_scf + w2), h._tab, h._zs)
+    w2 = energy_weighted(p, torch.cat([eo, ev]), orbital_coupling(bov, gamma, parts["x"], parts["y"], nv), jm[0] - 0.5 * km[0], co, cv)
+    _, d_scf, _ = _pulay_densities(qc)
     tic = clock()
-    lib.eri_grad(grad, tocart(d_scf + pbar), 1.0, h._tab)
-    sub = torch.zeros_like(grad)
-    lib.eri_grad(sub, tocart(pbar), 1.0, h._tab)
-    grad -= sub
+    grad = scf + relaxed_terms(h, lib.cart2sph_matrix(h._tab, dev), d_scf.detach(), pbar, w2)
     t_sep = clock() - tic
     ns_times = {} if times is not None else None
-    grad += _nonseparable_gradient(parts["df"], gamma, bov, co, cv, natm, block, ns_times)
-    grad += _nuclei_gradient(mol).to(dev)
+    grad += _nonseparable_gradient(parts["df"], gamma, bov, co, cv, h._tab.natm, block, ns_times)
     if times is not None:
         times.update(ns_times, density=t_density, separable=t_sep)
     return dens, scf, grad
@@ -542,6 +514,7 @@ def mp2_gradient(qc, auxbasis=None, c_os=1.0, c_ss=1.0, tol=1e-9, block=None):
 mp2.pair_energies_reference = pair_energies_reference
 mp2.density_reference = density_reference
 mp2.three_index_densities = three_index_densities
+mp2.orbital_coupling = orbital_coupling
 
 __all__ = ["mp2", "MP2", "pair_energies_reference", "energies_reference", "components", "transform_ov", "mp2_density", "MP2Density",
-           "density_reference", "unrelaxed_blocks", "mp2_gradient", "MP2Gradient", "three_index_densities"]
+           "density_reference", "unrelaxed_blocks", "mp2_gradient", "MP2Gradient", "three_index_densities", "orbital_coupling"]

@@ -1,6 +1,10 @@
 """What the post-SCF methods on the density-fitted tensor share on the host (dqc_amd/mp2.py, rpa.py, gw.py): the refusals, the tensor B
 and its occupied-virtual transform, the orbitals of the converged Fock matrix, the memo on the converged state, and the two loops over
-the fused kernels that more than one method runs -- the response matrix in frequency batches and the MP2 pair-energy blocks."""
+the fused kernels that more than one method runs -- the response matrix in frequency batches and the MP2 pair-energy blocks.  And what
+the relaxed-density nuclear gradients share (mp2.py, excited.py): the relaxed MO density, its energy-weighted density, the Z-vector
+solve, the gradient terms of a relaxed difference density, and the stage clock."""
+import time
+
 import torch
 
 from . import lib
@@ -149,3 +153,68 @@ def pair_energy_blocks(bovs, spins):
         (_, _, eoa, eva), (_, _, eob, evb) = spins
         os_ab = lib.mp2_pair_energies(bovs[0], bovs[1], eoa, eob, eva, evb, False)[0]
     return os_ab, [lib.mp2_pair_energies(bov, bov, eo, eo, ev, ev, True) for bov, (_, _, eo, ev) in zip(bovs, spins)]
+
+
+# ------------------------------------------------------------------------------------------------ relaxed-density gradients
+def stage_clock(times, dev):
+    """clock() -> seconds, for the wall time of the stages of a gradient: synchronises the device first when `times` (the dict that
+    receives them) is asked for, and only then"""
+    def clock():
+        if times is not None:
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    return clock
+
+
+def relaxed_density_mo(t_oo, t_vv, z=None):
+    """P (n, n) in the MO basis: T in its diagonal blocks and, with z (nv, no) the Z-vector, 2 z in the off-diagonal ones"""
+    no, nv = int(t_oo.shape[0]), int(t_vv.shape[0])
+    p = torch.zeros((no + nv, no + nv), dtype=t_oo.dtype, device=t_oo.device)
+    p[:no, :no], p[no:, no:] = t_oo, t_vv
+    if z is not None:
+        p[no:, :no], p[:no, no:] = 2.0 * z, 2.0 * z.T
+    return p
+
+
+def energy_weighted(p, eps, coupling, g_pbar, co, cv):
+    """W (nao, nao) = C 1/4 (Gm + Gm^T) C^T, Gm[p, q] = C_p^T dLagrangian / dC_q = 2 eps_p P_pq + (4 C^T G[Pbar] C_o on the occupied
+    columns) + coupling: p the (relaxed) difference density in the MO basis, eps all orbital energies, coupling (n, n) the blocks of the
+    method (excited.lagrangian_rhs, mp2.orbital_coupling), g_pbar = G[C p C^T] in the AO basis (Kohn-Sham: G of the last section of the
+    docstring of dqc_amd/excited.py, J - a / 2 K + V1, plus 2 V2[S, S] -- `parts["g_t"]` of lagrangian_rhs(..., xc=...) holds both for Tbar)"""
+    no = int(co.shape[1])
+    c = torch.cat([co, cv], dim=1)
+    gm = 2.0 * eps.unsqueeze(1) * p + coupling
+    gm[:, :no] += 4.0 * (c.T @ g_pbar @ co)
+    w = c @ (0.25 * (gm + gm.T)) @ c.T
+    return 0.5 * (w + w.T)                    # (the two GEMMs leave round-off asymmetry: W is handed out exactly symmetric)
+
+
+def z_vector(qc, orbitals, rhs, tol, op=None):
+    """(z (nv, no), the relative residual the solve stopped at) of H z = -rhs, H the singlet orbital Hessian (response.OrbitalHessian)
+    on orbitals = (co, cv, eo, ev).  op: an OrbitalHessian that may hold these very orbitals; it is used when they are bit-identical,
+    otherwise (and with None) one is built on them"""
+    from .response import OrbitalHessian
+    co, cv, eo, ev = orbitals
+    if op is None or not (torch.equal(op.spins[0].co, co) and torch.equal(op.spins[0].cv, cv)):
+        op = OrbitalHessian(qc, orbitals=(torch.cat([co, cv], dim=1), torch.cat([eo, ev])))
+    z = op.solve(-rhs.reshape(1, -1), tol=tol).reshape(rhs.shape)
+    return z, float(op.last_residual)
+
+
+def cart_part(T, m, sign=1.0):
+    """the symmetric (sign = 1) or antisymmetric (-1) part of T^T m T, the Cartesian-basis image of the AO matrix m; contiguous and
+    EXACTLY of that parity: the gate of lib.eri_grad2"""
+    x = T.T @ m @ T
+    return (0.5 * (x + sign * x.T)).contiguous()
+
+
+def relaxed_terms(h, T, d_scf, pbar, w2, kfrac=1.0):
+    """(natm, 3): what every relaxed difference density Pbar = C P C^T with its energy-weighted density W2 adds to the gradient of the
+    SCF energy of density d_scf --  tr[Pbar dh] - tr[W2 dS]  (lib.int1e_grad)  +  the separable two-electron term
+    d_integrals tr[Pbar G[D]] = eri_grad2(D, Pbar, 2, 2 kfrac)  (one bilinear pass; kfrac: the exact-exchange fraction).
+    T = lib.cart2sph_matrix of the table."""
+    out = torch.zeros((h._tab.natm, 3), dtype=torch.float64, device=h.device)
+    pc = cart_part(T, pbar)
+    lib.int1e_grad(out, pc, cart_part(T, w2), h._tab, h._zs)
+    lib.eri_grad2(out, cart_part(T, d_scf), pc, 2.0, 2.0 * kfrac, h._tab)
+    return out

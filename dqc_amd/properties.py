@@ -38,15 +38,17 @@ def _total_ao_density(qc):
     return h, h._unconvert_dm(dm)
 
 
+def dipole_au(h, mol, dm_ao):
+    """-tr[r D] + sum_A Z_A R_A (3,) in atomic units: the dipole moment of the AO density dm_ao with the nuclei of mol"""
+    r = lib.int1e("r0", h._tab, h.device)  # (3, nao, nao)
+    pos = mol.atompos.to(h.device)
+    return -torch.einsum("dab,ba->d", r, dm_ao) + torch.einsum("ad,a->d", pos, mol.atomzs.to(pos.dtype).to(h.device))
+
+
 def edipole(qc, unit="Debye"):
     """electric dipole moment (3,), pointing from negative to positive charge (properties.py:162-198)"""
     h, dao = _total_ao_density(qc)
-    mol = qc.get_system()
-    r = lib.int1e("r0", h._tab, h.device)  # (3, nao, nao)
-    elec = -torch.einsum("dab,ba->d", r, dao)
-    pos = mol.atompos.to(h.device)
-    ion = torch.einsum("ad,a->d", pos, mol.atomzs.to(pos.dtype).to(h.device))
-    return (elec + ion) * _unit(_DIPOLE_UNITS, unit, "dipole")
+    return dipole_au(h, qc.get_system(), dao) * _unit(_DIPOLE_UNITS, unit, "dipole")
 
 
 def equadrupole(qc, unit="Debye*Angst"):

@@ -229,6 +229,12 @@ def test_mp2_gradient_against_finite_differences(dev):
     with lib.call_trace() as tr:
         g = dqc_amd.mp2_gradient(qc, auxbasis="etb", tol=ZTOL)
     assert any(row[0] == "dqc_df_grad3" for row in tr.rows)
+    # the separable term is ONE bilinear pass; the quadratic pass is reached through qc.nuclear_gradient() alone (restricted HF: once)
+    calls = [row[0] for row in tr.rows]
+    assert calls.count("dqc_eri_grad2") == 1 and calls.count("dqc_eri_grad") == 1
+    with lib.call_trace() as tr_scf:
+        qc.nuclear_gradient()
+    assert [row[0] for row in tr_scf.rows].count("dqc_eri_grad") == 1
     assert dqc_amd.mp2_gradient(qc, auxbasis="etb", tol=ZTOL) is g and not g.gradient.requires_grad
     assert isinstance(g, dqc_amd.MP2Gradient) and tuple(g.gradient.shape) == (3, 3)
     assert g.density.relaxed and g.z_residual <= ZTOL and g.naux == dqc_amd.mp2(qc, auxbasis="etb").naux

@@ -234,12 +234,43 @@ def test_tddft_relaxed_dipole_against_finite_field(dev, xc, tda):
         assert abs(along(mu_u, d) - fr) > bound
 
 
-@pytest.mark.parametrize("xc", ["lda_x+lda_c_pw", "gga_x_pbe+gga_c_pbe"])
-def test_xc_potential_gradient_reproduces_the_ground_state_terms(dev, xc):
-    """_xc_potential_gradient with M = D and the ground-state potentials, plus _xc_weight_gradient on the energy density, is the XC
-    part of nuclear_gradient (gradient._xc_gradient) to 1e-12: on the path it chooses (GGA: the fused kernel) and on the torch passes"""
+@pytest.mark.parametrize("xc,restricted", [pytest.param("lda_x+lda_c_pw", True, id="lda_x+lda_c_pw"),
+                                           pytest.param("gga_x_pbe+gga_c_pbe", True, id="gga_x_pbe+gga_c_pbe"),
+                                           pytest.param("mgga_x_scan", True, id="mgga_x_scan"),
+                                           pytest.param("gga_x_pbe+gga_c_pbe", False, id="gga_x_pbe+gga_c_pbe-unrestricted")])
+def test_xc_potential_gradient_reproduces_the_ground_state_terms(dev, xc, restricted):
+    """Restricted LDA and PBE: _xc_potential_gradient with M = D and the ground-state potentials, plus _xc_weight_gradient on the energy
+    density, is the XC part of nuclear_gradient (gradient._xc_gradient) to 1e-12: on the path it chooses (GGA: the fused kernel) and on
+    the torch passes.  Both names now run the one gradient._xc_grid_terms, so this comparison is partly true by construction; what
+    holds that function independently is (a) the two further cases here -- restricted SCAN (the tau terms) and unrestricted PBE on the
+    triplet of the same geometry (two spins): _xc_gradient on the fused kernel dqc_grid_xc_gradient_terms against _xc_gradient(fused=
+    False) on the torch passes, 1e-12, same molecule, basis and grid and so the same scale -- and (b) the finite-difference tests of
+    _xc_gradient through nuclear_gradient in tests/test_gpu_parity.py: test_nuclear_gradient_vs_oracle_finite_differences (LDA, PBE,
+    UKS PBE) and test_nuclear_gradient_water_ccpvdz_vs_gpu_finite_differences (SCAN, unrestricted SCAN)."""
+    import dqc_amd
     from dqc_amd import gradient as G, lib
     from dqc_amd.utils.datastruct import ValGrad
+    if xc == "mgga_x_scan" or not restricted:   # the two cases of (a)
+        if restricted:
+            qc = _run(xc, "3-21G")
+        else:  # a genuine open shell: the triplet
+            qc = dqc_amd.KS(dqc_amd.Mol((ZS, POS), basis="3-21G", grid=GRID, spin=2), xc=xc, restricted=False).run(fwd_options=TIGHT)
+        eng = qc._engine
+        d_aos, _, _ = G._pulay_densities(qc)
+        assert len(d_aos) == (1 if restricted else 2)
+        if not restricted:
+            assert float((d_aos[0] - d_aos[1]).abs().max()) > 1e-2
+        got = []
+        for fused in (None, False):
+            with lib.call_trace() as tr:
+                got.append(G._xc_gradient(eng, d_aos, fused=fused))
+            calls = [r[0] for r in tr.rows].count("dqc_grid_xc_gradient_terms")
+            assert calls == (len(d_aos) if fused is None else 0)
+        err = float((got[0] - got[1]).abs().max())
+        print("xc gradient %s %s: max |fused - torch passes| %.2e (max |g| %.3e)"
+              % (xc, "restricted" if restricted else "unrestricted", err, float(got[1].abs().max())))
+        assert err <= 1e-12
+        return
     qc = _run(xc, "3-21G")
     eng = qc._engine
     h = eng.hamilton

@@ -115,3 +115,58 @@ def test_three_index_densities_against_finite_differences():
                   % (c_os, c_ss, atom, d, grad[atom, d], rich, abs(grad[atom, d] - rich), bound))
             assert abs(grad[atom, d]) > 100.0 * bound, (atom, d, grad[atom, d], bound)
             assert abs(grad[atom, d] - rich) <= bound, (atom, d, grad[atom, d], rich, bound)
+
+
+def test_energy_weighted_with_orbital_coupling_is_the_inline_expression():
+    """postscf.energy_weighted(p, eps, mp2.orbital_coupling(...), g_pbar, co, cv) equals the expression mp2._gradient used to hold
+    inline -- written out below as the yardstick -- on random operands: no = 2, nv = 3, nao = 7, naux = 5, Bov and Gamma with one padded
+    virtual column (filled with numbers, so that a missed [:nv, :nv] slice shows).  Bound 1e-13 max |W2|: the two differ in the order of
+    at most four fp64 additions per element and in GEMMs of inner dimension <= 7.  W2 is exactly symmetric."""
+    from dqc_amd import excited, mp2
+    g = torch.Generator().manual_seed(5)
+    rnd = lambda *shape: torch.randn(*shape, dtype=torch.float64, generator=g)  # noqa: E731
+    no, nv, nao, naux = 2, 3, 7, 5
+    n = no + nv
+    q, _ = torch.linalg.qr(rnd(nao, n))
+    co, cv = q[:, :no].contiguous(), q[:, no:].contiguous()
+    p = rnd(n, n)
+    p = 0.5 * (p + p.t())
+    eps, g_pbar = rnd(n), rnd(nao, nao)
+    bov, gamma = rnd(no, naux, nv + 1), rnd(no, naux, nv + 1)
+    x, y = rnd(nv, no), rnd(nv, no)
+    got = excited.energy_weighted(p, eps, mp2.orbital_coupling(bov, gamma, x, y, nv), g_pbar, co, cv)
+    # the yardstick: the inline expression of the parent
+    c_all = torch.cat([co, cv], dim=1)
+    gm = 2.0 * eps.unsqueeze(1) * p
+    gm[:, :no] += 4.0 * (c_all.t() @ g_pbar @ co)
+    gm[:no, :no] += 4.0 * torch.einsum("kpa,ipa->ki", bov, gamma)
+    gm[no:, :no] += 4.0 * x
+    gm[:no, no:] += 4.0 * y.t()
+    gm[no:, no:] += 4.0 * torch.einsum("ipc,ipa->ca", bov, gamma)[:nv, :nv]
+    ref = c_all @ (0.25 * (gm + gm.t())) @ c_all.t()
+    err, scale = float((got - ref).abs().max()), float(ref.abs().max())
+    print("energy_weighted / orbital_coupling vs inline: max |diff| %.2e, max |W2| %.3e" % (err, scale))
+    assert got.shape == (nao, nao) and scale > 1.0
+    assert err <= 1e-13 * scale
+    assert torch.equal(got, got.t())
+
+
+def test_dipole_of_an_ao_density(monkeypatch):
+    """properties.dipole_au(h, mol, D) = -einsum("dab,ba->d", r, D) + einsum("ad,a->d", pos, Z), exactly: random symmetric D, a random
+    (3, n, n) r in place of the multipole integrals, three atoms"""
+    from types import SimpleNamespace
+    from dqc_amd import lib, properties
+    g = torch.Generator().manual_seed(9)
+    n = 6
+    d = torch.randn(n, n, dtype=torch.float64, generator=g)
+    d = 0.5 * (d + d.t())
+    r = torch.randn(3, n, n, dtype=torch.float64, generator=g)
+    pos = torch.randn(3, 3, dtype=torch.float64, generator=g)
+    zs = torch.tensor([8, 1, 1])
+    h = SimpleNamespace(_tab=object(), device=torch.device("cpu"))
+    asked = []
+    monkeypatch.setattr(lib, "int1e", lambda which, tab, device: (asked.append((which, tab is h._tab)), r)[1])
+    got = properties.dipole_au(h, SimpleNamespace(atompos=pos, atomzs=zs), d)
+    ref = -torch.einsum("dab,ba->d", r, d) + torch.einsum("ad,a->d", pos, zs.to(torch.float64))
+    assert asked == [("r0", True)]
+    assert got.shape == (3,) and torch.equal(got, ref)

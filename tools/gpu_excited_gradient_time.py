@@ -10,7 +10,8 @@ usage: python tools/gpu_excited_gradient_time.py [out.json] [--small]
             2 eri_grad2(D, P) and the three-call result over the largest component is reported too.  The antisymmetric pair (jscale 0:
             no Coulomb loads) is timed beside them.
   stages    excited_gradient (CIS singlet, state 0) on the converged RHF calculation, twice, the second run warm with the excitation
-            memo cleared: the excitations, the right-hand side with the Z-vector solve, the three dqc_eri_grad2 passes, the whole call.
+            memo cleared: the excitations, the right-hand side with the Z-vector solve, `passes` = the three dqc_eri_grad2 passes with the
+            one-electron call of the relaxed density (dqc_int1e_grad), the whole call.
 --small: H2O / 3-21G, to rehearse the script."""
 import json
 import os

@@ -7,8 +7,8 @@ usage: python tools/gpu_mp2_gradient_time.py [out.json] [--small]
             with Z alone and with G alone: after one warm-up of every side, three ALTERNATING repetitions, wall time around the call
             (both entry points end with a stream synchronise; their host work -- pair lists, uploads, the fold -- is the same and is
             inside both figures).  The largest difference of the two results over the largest component is reported too.
-  stages    mp2_gradient on the converged RHF calculation: the relaxed density with its Z-vector solve, the two separable eri_grad
-            calls, the formation of Z and G (triangular solves, back-transformation, Cartesian transform), the dqc_df_grad3 passes, and
+  stages    mp2_gradient on the converged RHF calculation: the relaxed density with its Z-vector solve, `separable` = the one-electron
+            call and the one bilinear eri_grad2 pass of the relaxed density, the formation of Z and G (triangular solves, back-transformation, Cartesian transform), the dqc_df_grad3 passes, and
             the whole call; the number of auxiliary-shell blocks Z was walked in.
 --small: H2O / 3-21G, to rehearse the script."""
 import json

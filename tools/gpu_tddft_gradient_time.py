@@ -7,7 +7,7 @@ usage: python tools/gpu_tddft_gradient_time.py [out.json] [--small]
             of the converged calculation and one response density on its grid: after one warm-up of either side, five ALTERNATING
             repetitions, HIP events around the call (lib.call_trace).
   stages    tddft_gradient (TDA singlet, state 0), twice, the second run warm with the excitation memo cleared: the excitations, the
-            right-hand side with the Z-vector solve, the dqc_eri_grad2 passes, the three grid passes (AO evaluation and the potentials
+            right-hand side with the Z-vector solve, the dqc_eri_grad2 passes (with dqc_int1e_grad), the three grid passes (AO evaluation and the potentials
             on the grid included), the weight term, the whole call.
 --small: H2O / 3-21G, to rehearse the script."""
 import json
