@@ -16,5 +16,6 @@ from .excited import excited_gradient, tddft_gradient, ExcitedGradient, ExcitedD
 from .rpa import rpa, RPA  # noqa: F401
 from .gw import gw, GW  # noqa: F401
 from .bse import bse, BSE  # noqa: F401
+from .ccsd import ccsd, CCSD  # noqa: F401
 
 __version__ = "0.1.0"

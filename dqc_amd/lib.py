@@ -113,6 +113,9 @@ def load():
     lib.dqc_bse_work_doubles.argtypes = [c_int] * 6
     lib.dqc_bse_work_doubles.restype = c_sz
     lib.dqc_bse_exchange.argtypes = [c_dp] * 4 + [c_int] * 8 + [c_dp, c_vp]
+    lib.dqc_cc_ladder_work_doubles.argtypes = [c_int] * 6
+    lib.dqc_cc_ladder_work_doubles.restype = c_sz
+    lib.dqc_cc_ladder.argtypes = [c_dp] * 4 + [c_int] * 8 + [c_dp, c_vp]
     lib.dqc_eri_tiles_to_dense.argtypes = [c_dp, c_dp, c_int, c_vp]
     lib.dqc_jk_from_tiles.argtypes = [c_dp, c_dp, c_dp, c_dp, c_int, c_dp, c_vp]
     lib.dqc_jk_multi_work_doubles.argtypes = [c_int, c_int, c_int]
@@ -589,6 +592,38 @@ def bse_exchange(l, r, x, nr, ns, out=None, work=None):
     with _on(l.device) as st_:
         _check(L.dqc_bse_exchange(_ptr(out), _ptr(l), _ptr(r), _ptr(x), np_, nq, nr, ns, ldr, lds, naux, nvec, _ptr(work) if need else None, st_),
                "dqc_bse_exchange")
+    return out
+
+
+def cc_ladder(l, r, x, nr, ns, out=None, work=None):
+    """the particle-particle ladder of coupled-cluster doubles, integral-driven (csrc/cc.hip: dqc_cc_ladder): l (np, naux, ldr) and
+    r (nq, naux, lds) as `postscf.transform_ov` makes them (they may be one tensor), nr <= ldr and ns <= lds real columns,
+    x (nr, ns, nvec) -- THE VECTOR INDEX LAST -- -> out (nvec, np, nq),
+    out[v, p, q] = sum_rs W[p, q, r, s] x[r, s, v], W[p, q, r, s] = sum_P l[p, P, r] r[q, P, s]: each tile of W is summed once and used
+    by every vector; no element of it is stored.  out: the tensor to write into; work: taken for the symmetry of the fused entry
+    points and never touched (dqc_cc_ladder_work_doubles is 0: no sum is split).  The kernel loads single doubles: no alignment is
+    asked of the tensors.  No atomics: bit-reproducible.  The arguments are checked before anything is launched"""
+    for name, t in (("l", l), ("r", r)):
+        if t.dim() != 3 or t.shape[2] % 16:
+            raise DqcAmdError("cc_ladder: %s must be (n, naux, ld) with ld a multiple of 16, got %s" % (name, tuple(t.shape)))
+    np_, naux, ldr = (int(n) for n in l.shape)
+    nq, lds = int(r.shape[0]), int(r.shape[2])
+    nr, ns = int(nr), int(ns)
+    if int(r.shape[1]) != naux:
+        raise DqcAmdError("cc_ladder: l holds %d auxiliary functions and r %d" % (naux, int(r.shape[1])))
+    if nr < 0 or nr > ldr or ns < 0 or ns > lds:
+        raise DqcAmdError("cc_ladder: (%d, %d) columns asked of slabs of (%d, %d)" % (nr, ns, ldr, lds))
+    if x.dim() != 3 or int(x.shape[0]) != nr or int(x.shape[1]) != ns:
+        raise DqcAmdError("cc_ladder: x must be (%d, %d, nvec), got %s" % (nr, ns, tuple(x.shape)))
+    nvec = int(x.shape[2])
+    for name, t in (("l", l), ("r", r), ("x", x)):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise DqcAmdError("cc_ladder: %s must be a contiguous float64 tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if l.device != r.device or l.device != x.device or l.device.type != "cuda":
+        raise DqcAmdError("cc_ladder: l, r and x must be on one GPU, got %s, %s and %s" % (l.device, r.device, x.device))
+    out = _out_like("cc_ladder", out, (nvec, np_, nq), l, "l")
+    with _on(l.device) as st_:
+        _check(load().dqc_cc_ladder(_ptr(out), _ptr(l), _ptr(r), _ptr(x), np_, nq, nr, ns, ldr, lds, naux, nvec, None, st_), "dqc_cc_ladder")
     return out
 
 

@@ -376,6 +376,19 @@ size_t dqc_bse_work_doubles(int np, int nq, int nr, int ns, int naux, int nvec);
 int dqc_bse_exchange(double *d_out, const double *d_l, const double *d_r, const double *d_x, int np, int nq, int nr, int ns, int ldr,
                      int lds, int naux, int nvec, double *d_work, void *stream);
 
+/* The particle-particle ladder of coupled-cluster doubles, integral-driven and fused (csrc/cc.hip): every tile of W is summed over P
+ * once, in MFMA accumulators, and used by every vector of the block's vector panel; no element of W is written to global memory.
+ *   out[v, p, q] = sum_{r < nr} sum_{s < ns} W[p, q, r, s] X[v, r, s],      W[p, q, r, s] = sum_P L[p, P, r] R[q, P, s]
+ * d_l (np, naux, ldr) and d_r (nq, naux, lds): one slab per p and per q as above (ldr >= nr and lds >= ns multiples of 16; the columns
+ * past nr and ns are padding: never used, whatever they hold); they may be one tensor.  d_x (nr, ns, nvec): THE VECTOR INDEX LAST,
+ * contiguous, no padding.  d_out (nvec, np, nq): contiguous, no padding.  nvec, np or nq zero: nothing to write; naux, nr or ns zero:
+ * zeros (no kernel).  No sum is split over blocks: dqc_cc_ladder_work_doubles is 0 for every shape and d_work is never touched (it
+ * may be null); no atomics, bit-reproducible.  Every argument is checked before anything is launched (negative counts, ldr or lds no
+ * multiple of 16 or too small, null pointers, more than 2^31 - 1 blocks: DQC_EINVAL).  Only enqueues. */
+size_t dqc_cc_ladder_work_doubles(int np, int nq, int nr, int ns, int naux, int nvec);
+int dqc_cc_ladder(double *d_out, const double *d_l, const double *d_r, const double *d_x, int np, int nq, int nr, int ns, int ldr,
+                  int lds, int naux, int nvec, double *d_work, void *stream);
+
 /* ---- nuclear gradients of the SCF energy   ------------------------------------
  * The reference differentiates through its "ip" derivative integrals (molintor.py:463-500) and the implicit-function
  * backward of the SCF fixed point (scf_qccalc.py:63-67, 109-113); at convergence that is
